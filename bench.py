@@ -12,9 +12,15 @@ Workloads (``--workload``; a "step" = zero_grad -> forward -> backward -> Adam s
 N > 1: pure data parallel, one rank per GPU (weak scaling), gradient buckets averaged over RCCL.  ``python bench.py --gpus N``
 starts the N ranks itself (torch.distributed.run) when it was not already started by a launcher (WORLD_SIZE unset).
 
-Prints ONE JSON line (rank 0) with the driver's contract fields plus
-  roofline     — dominant kernel family (bf16 MFMA GEMM, NT layout) timed live with HIP events on its launch stream
-  cpu_baseline — the oracle (CPU restatement of the reference, oracle/) timed on this host's cores (N=1 only)
+A plain run sets up, warms up, times ``--steps`` steps and prints ONE JSON line (rank 0) with the driver's contract fields
+(metric, value, unit, higher_is_better, dtype, ms_per_step) and the run's configuration.  ``--full`` adds the measurements and
+checks that take runs of their own:
+  roofline       — dominant kernel family (bf16 MFMA GEMM, NT layout) timed live with HIP events on its launch stream
+  cpu_baseline   — the oracle (CPU restatement of the reference, oracle/) timed on this host's cores (N=1 only)
+  ema_rmse_vs_ref — aptai: the build's eval forward against the oracle's on one B=2 batch (N=1 only)
+  index_exact    — force: the same step with the exact-index encoder (f32x3), measured by a child process (N=1 only)
+``--dump-outputs DIR`` writes what the last timed step returned (and a fixed sample of the updated parameters and their
+gradients) as DIR/<name>.npy, float32 / float64; inputs and weights are seeded, so two builds can be compared file by file.
 """
 import argparse
 import json
@@ -50,7 +56,11 @@ def parse():
     ap.add_argument("--seconds", type=float, default=10.0)
     ap.add_argument("--n-tv", type=int, default=12)
     ap.add_argument("--no-regularisers", action="store_true", help="dropout/LayerDrop/SpecAugment off (debug)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure roofline, cpu_baseline, ema_rmse_vs_ref and index_exact "
+                                                         "(runs of their own after the timed steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip cpu_baseline and ema_rmse_vs_ref")
     ap.add_argument("--cpu-baseline-steps", type=int, default=2)
     ap.add_argument("--torch-adam", action="store_true", help="torch.optim.Adam(fused=True) instead of aptai_amd.optim.Adam")
     ap.add_argument("--host-batch", action="store_true", help="hand the step a pinned HOST batch every iteration (PCIe-inclusive rate; "
@@ -59,9 +69,12 @@ def parse():
                     help="force workload: precision of the frozen encoder (mxfp8 = BASELINE configs[4]; bf16_f32res = bf16 GEMMs with an fp32 residual stream)")
     ap.add_argument("--plan-gpus", type=int, default=8, help="world size the JSON line's collective_plan is written for when the run itself is "
                                                              "one rank (dry plan of the gradient exchange; multi-rank runs describe their own)")
-    ap.add_argument("--no-exact-line", action="store_true", help="force workload: skip the second measurement in the index-exact encoder mode")
+    ap.add_argument("--no-exact-line", action="store_true", help="force workload, --full: skip the second measurement in the index-exact encoder mode")
     ap.add_argument("--eager", action="store_true", help="drive the step through autograd (the drop-in loop) instead of hipGraphs")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 # ------------------------------------------------------------------------------------------------- rank launcher
@@ -359,6 +372,96 @@ def ema_rmse_check(model, cfg, args, device):
                       "are ~1, so abs_diff is insensitive - rmse_between_predictions is the honest distance"}
 
 
+def roofline(args, cfg, B, dt, probe, probe_note):
+    """--full: the dominant kernel family's achieved rate (HIP events of the GemmProbe) against the MFMA peak, its PMC traffic
+    from the offline profile, and the whole step's algorithmic work over the step time."""
+    wl = args.workload
+    ps = probe.summary()
+    gemm_tflops = ps["flops"] / (ps["ms"] * 1e-3) / 1e12 if ps["ms"] > 0 else 0.0
+    traffic, traffic_src = None, None
+    for tag in (PROFILE_TAG, "r01"):   # PMC traffic of the dominant kernel, collected offline (tools/pmc_summary.py)
+        try:
+            pm = json.load(open(os.path.join(ROOT, "profiles", f"{tag}_pmc_traffic.json")))["kernels"]
+            nt = [v for k, v in pm.items() if "<false, false, false>" in k and "gemm" in k]      # the NT family the probe brackets
+            traffic = int(sum(v["hbm_bytes_per_launch_corrected"] * v["launches_in_trace"] for v in nt) /
+                          max(sum(v["launches_in_trace"] for v in nt), 1))
+            traffic_src = f"profiles/{tag}_pmc_traffic.json"
+            break
+        except Exception:
+            continue
+    if wl != "aptai":
+        traffic, traffic_src = None, None            # the PMC passes were collected on the aptai workload
+    gf = FWD_GF.get((args.model, args.seconds))
+    step_tf = step_tf_exec = None
+    if gf:
+        if wl == "aptai":          # conv stack frozen: fwd only; encoder fwd+bwd
+            step_tf = (gf["conv"] + 3 * gf["enc"]) * B / 1e3
+            # LayerDrop skips a layer's forward AND backward with probability p: the executed encoder work is (1 - p) of
+            # the layer share; `step_algorithmic_tflop` counts every layer (the reference's nominal work per step)
+            keep = 1.0 - (0.0 if args.no_regularisers else cfg.layerdrop)
+            step_tf_exec = (gf["conv"] + 3 * gf["enc"] * keep) * B / 1e3
+        elif wl == "pr":           # everything trainable: 3 x forward
+            step_tf = 3 * (gf["conv"] + gf["enc"]) * B / 1e3
+            keep = 1.0 - (0.0 if args.no_regularisers else cfg.layerdrop)
+            step_tf_exec = 3 * (gf["conv"] + gf["enc"] * keep) * B / 1e3
+        else:                      # encoder forward only (inference); heads < 0.1 %
+            step_tf = step_tf_exec = (gf["conv"] + gf["enc"]) * B / 1e3
+    return {"bound": "mfma", "kernel": "bf16 MFMA GEMM, NT layout (gemm_kernel / gemm192_kernel / gemm256_kernel <false,false,false>): every launch of the step",
+            "achieved": round(gemm_tflops, 2), "peak": 2500.0, "unit": "TFLOP/s",
+            "frac": round(gemm_tflops / 2500.0, 4), "traffic": traffic,
+            "traffic_note": (f"HBM-side bytes per launch, launch-weighted over the same NT kernels, rocprofv3 PMC (2 x FETCH_SIZE + "
+                             f"WRITE_SIZE, separate passes), {traffic_src}") if traffic else None,
+            "measured": probe_note, "launches": ps["launches"], "avg_launch_us": round(ps["ms"] * 1e3 / max(ps["launches"], 1), 2),
+            "step_algorithmic_tflop": step_tf,
+            "step_executed_tflop": round(step_tf_exec, 4) if step_tf_exec else None,
+            "whole_step_frac_of_peak": round(step_tf / (dt / args.steps) / 2500.0, 4) if step_tf else None,
+            "whole_step_frac_of_peak_executed": round(step_tf_exec / (dt / args.steps) / 2500.0, 4) if step_tf_exec else None,
+            "flop_note": "step_algorithmic_tflop counts every transformer layer (SURVEY.md 8d); LayerDrop (p = 0.1) skips "
+                         "10 % of the layer work in expectation: *_executed prices the expected executed work"}
+
+
+DUMP_MAX_ELEMS = 1 << 21        # per array: larger outputs are written as a fixed, seeded sample of this many elements
+DUMP_PARAM_SAMPLE = 1024        # elements sampled from each trainable parameter (and its gradient)
+DUMP_MAX_BYTES = 64 << 20
+
+
+def _sample_index(n: int, k: int, seed: int) -> "torch.Tensor":
+    import numpy as np
+    idx = np.arange(n) if n <= k else np.sort(np.random.RandomState(seed).choice(n, k, replace=False))
+    return torch.from_numpy(idx.astype(np.int64))
+
+
+def dump_outputs(out, params, path: str) -> None:
+    """--dump-outputs: the arrays the last timed step handed its caller (every tensor of its result; floating point as float32,
+    or float64 where the step computed in float64, integers as float64) and the state the step left behind (a seeded sample of
+    every trainable parameter after the optimiser step, `params.npy`, and of its gradient, `grads.npy`, zeros where a parameter
+    got none).  Arrays above DUMP_MAX_ELEMS elements are written as a fixed, seeded sample of their flattened elements."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {}
+    for name, t in out.items():
+        if not isinstance(t, torch.Tensor):
+            continue                                     # (Python lists of the eager force step: the same data is in its tensors)
+        t = t.detach()
+        dt = torch.float64 if (t.dtype == torch.float64 or not t.is_floating_point()) else torch.float32
+        if t.numel() > DUMP_MAX_ELEMS:
+            t = t.reshape(-1)[_sample_index(t.numel(), DUMP_MAX_ELEMS, 0).to(t.device)]
+        arrays[name] = t.to(dt).cpu().numpy()
+    pv, gv = [], []
+    for i, p in enumerate(params):
+        idx = _sample_index(p.numel(), DUMP_PARAM_SAMPLE, i).to(p.device)
+        pv.append(p.detach().reshape(-1)[idx].float().cpu())
+        gv.append(torch.zeros(len(idx)) if p.grad is None else p.grad.detach().reshape(-1)[idx].float().cpu())
+    arrays["params"] = torch.cat(pv).numpy()
+    arrays["grads"] = torch.cat(gv).numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (limit {DUMP_MAX_BYTES})")
+    for name, a in arrays.items():
+        np.save(os.path.join(path, f"{name}.npy"), a)
+    print(f"[bench] wrote {len(arrays)} arrays ({total / 2 ** 20:.1f} MiB) to {path}", file=sys.stderr, flush=True)
+
+
 # ------------------------------------------------------------------------------------------------- main
 def main():
     args = parse()
@@ -483,7 +586,8 @@ def main():
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
-    ops.set_gemm_probe(probe)
+    if args.full:
+        ops.set_gemm_probe(probe)
     t0 = time.perf_counter()
     for _ in range(args.steps):
         out = step()
@@ -492,11 +596,14 @@ def main():
         dist.barrier()
     dt = time.perf_counter() - t0
     ops.set_gemm_probe(None)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out, params, args.dump_outputs)
     probe_note = "HIP events around every launch inside the timed region"
     if use_graph:
+        runner.close()
+    if args.full and use_graph:
         # kernels inside a hipGraph replay cannot be bracketed one by one: re-issue the SAME step eagerly right after the
         # timed region (same model, batch, shapes, regularisers) with the event probe on
-        runner.close()
         # The probe's event pairs time a launch correctly only while the queue is never empty (an idle queue stamps the start
         # event at once and the kernel arrives a host call later): ~30 ms of unrelated launches first, so that the host stays
         # ahead of the GPU for the three host-bound eager steps that follow.
@@ -520,36 +627,6 @@ def main():
     loss = float(out["loss"].detach())
     if rank == 0:
         print(f"[bench] timed region: {dt / args.steps * 1e3:.2f} ms/step", file=sys.stderr, flush=True)
-        ps = probe.summary()
-        gemm_tflops = ps["flops"] / (ps["ms"] * 1e-3) / 1e12 if ps["ms"] > 0 else 0.0
-        traffic, traffic_src = None, None
-        for tag in (PROFILE_TAG, "r01"):   # PMC traffic of the dominant kernel, collected offline (tools/pmc_summary.py)
-            try:
-                pm = json.load(open(os.path.join(ROOT, "profiles", f"{tag}_pmc_traffic.json")))["kernels"]
-                nt = [v for k, v in pm.items() if "<false, false, false>" in k and "gemm" in k]      # the NT family the probe brackets
-                traffic = int(sum(v["hbm_bytes_per_launch_corrected"] * v["launches_in_trace"] for v in nt) /
-                              max(sum(v["launches_in_trace"] for v in nt), 1))
-                traffic_src = f"profiles/{tag}_pmc_traffic.json"
-                break
-            except Exception:
-                continue
-        if wl != "aptai":
-            traffic, traffic_src = None, None            # the PMC passes were collected on the aptai workload
-        gf = FWD_GF.get((args.model, args.seconds))
-        step_tf = step_tf_exec = None
-        if gf:
-            if wl == "aptai":          # conv stack frozen: fwd only; encoder fwd+bwd
-                step_tf = (gf["conv"] + 3 * gf["enc"]) * B / 1e3
-                # LayerDrop skips a layer's forward AND backward with probability p: the executed encoder work is (1 - p) of
-                # the layer share; `step_algorithmic_tflop` counts every layer (the reference's nominal work per step)
-                keep = 1.0 - (0.0 if args.no_regularisers else cfg.layerdrop)
-                step_tf_exec = (gf["conv"] + 3 * gf["enc"] * keep) * B / 1e3
-            elif wl == "pr":           # everything trainable: 3 x forward
-                step_tf = 3 * (gf["conv"] + gf["enc"]) * B / 1e3
-                keep = 1.0 - (0.0 if args.no_regularisers else cfg.layerdrop)
-                step_tf_exec = 3 * (gf["conv"] + gf["enc"] * keep) * B / 1e3
-            else:                      # encoder forward only (inference); heads < 0.1 %
-                step_tf = step_tf_exec = (gf["conv"] + gf["enc"]) * B / 1e3
         what = {"aptai": f"APTAI train step (models/aptai.py): wav2vec2-{args.model} + {args.n_tv}-dim EMA regression head + "
                          f"46-class frame phoneme head, conv feature encoder frozen",
                 "pr": f"Wav2Vec2_PR train step (models/w2v2_pr.py): wav2vec2-{args.model} + CTC head (40 phonemes), everything "
@@ -589,20 +666,10 @@ def main():
                                       if (wl == "force" and not args.no_pipeline) else "eager autograd loop")),
                        "inputs": "pinned host batch copied in every step (PCIe-inclusive)" if args.host_batch else "resident in HBM"},
             "loss": round(loss, 5),
-            "roofline": {"bound": "mfma", "kernel": "bf16 MFMA GEMM, NT layout (gemm_kernel / gemm192_kernel / gemm256_kernel <false,false,false>): every launch of the step",
-                         "achieved": round(gemm_tflops, 2), "peak": 2500.0, "unit": "TFLOP/s",
-                         "frac": round(gemm_tflops / 2500.0, 4), "traffic": traffic,
-                         "traffic_note": (f"HBM-side bytes per launch, launch-weighted over the same NT kernels, rocprofv3 PMC (2 x FETCH_SIZE + "
-                                          f"WRITE_SIZE, separate passes), {traffic_src}") if traffic else None,
-                         "measured": probe_note, "launches": ps["launches"], "avg_launch_us": round(ps["ms"] * 1e3 / max(ps["launches"], 1), 2),
-                         "step_algorithmic_tflop": step_tf,
-                         "step_executed_tflop": round(step_tf_exec, 4) if step_tf_exec else None,
-                         "whole_step_frac_of_peak": round(step_tf / (dt / args.steps) / 2500.0, 4) if step_tf else None,
-                         "whole_step_frac_of_peak_executed": round(step_tf_exec / (dt / args.steps) / 2500.0, 4) if step_tf_exec else None,
-                         "flop_note": "step_algorithmic_tflop counts every transformer layer (SURVEY.md 8d); LayerDrop (p = 0.1) skips "
-                                      "10 % of the layer work in expectation: *_executed prices the expected executed work"},
         }
-        if wl == "force" and world == 1 and not args.no_exact_line and args.encoder_precision in ("bf16", "bf16_f32res", "mxfp8"):
+        if args.full:
+            res["roofline"] = roofline(args, cfg, B, dt, probe, probe_note)
+        if args.full and wl == "force" and world == 1 and not args.no_exact_line and args.encoder_precision in ("bf16", "bf16_f32res", "mxfp8"):
             # Every Force_APTAI record carries BOTH figures (round-3 review): the line above is the bf16-operand encoder, whose alignment
             # indices agree with the reference's only outside the arithmetic noise (2-13 % of the decisions sit inside it); the
             # north_star-conformant figure ("alignment indices bit-exact") is the exact-index mode f32x3 (every index equal on the
@@ -620,7 +687,7 @@ def main():
                                       "bit-exact' refers to.  The headline value of this record is the bf16-operand encoder (margin-exact)."}
             except Exception as e:          # noqa: BLE001 - the headline measurement stands; say what is missing
                 res["index_exact"] = {"encoder_precision": "f32x3", "value": None, "note": f"second measurement failed: {e!r}"}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             if wl == "aptai":
                 res["ema_rmse_vs_ref"] = ema_rmse_check(model, cfg, args, device)
             res["cpu_baseline"] = cpu_baseline(args, cfg)

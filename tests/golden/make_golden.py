@@ -291,6 +291,9 @@ def case_force(name="force_aptai_1x2s", seed=0):
     save(name, dict(case=name, pr_cfg=pr_kw, seed=seed, vocab_len=len(vocab), model="Force_APTAI", blank_bias=2.5,
                     note="decoder = greedy best-path stand-in (parity unpinned); b1/pred_ctc_phn_seq is an INPUT"),
          arrays)
+    # the synthetic tables as computed here (float32 randn / exp / sin / cos vary in their last bits between CPU vector paths)
+    save(name + "_tables", dict(case=name, seed=seed, what="synthetic tables the fixture was generated with"),
+         {k: sd[k] for k in ("phn_emb_layer.weight", "pe_phn.pe")})
 
 
 def case_ops(name="ops_small"):

@@ -18,7 +18,7 @@ for k, c in acc.items():
     res[k] = {"launches_in_trace": len(c["GRBM_GUI_ACTIVE"]), "mfma_busy_cycles_avg": round(busy / len(c["GRBM_GUI_ACTIVE"])),
               "gui_active_cycles_avg": round(act / len(c["GRBM_GUI_ACTIVE"])), "mfma_util": round(busy / (act / 8 * 1024), 4)}
 json.dump({"method": "rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE over `python bench.py --steps 2 --warmup 1 "
-                     "--no-cpu-baseline --eager`; mfma_util = busy cycles / (GPU-active cycles x 1024 SIMDs), GUI_ACTIVE summed over 8 XCDs",
+                     "--full --no-cpu-baseline --eager`; mfma_util = busy cycles / (GPU-active cycles x 1024 SIMDs), GUI_ACTIVE summed over 8 XCDs",
            "kernels": dict(sorted(res.items(), key=lambda kv: -kv[1]["mfma_busy_cycles_avg"] * kv[1]["launches_in_trace"]))}, open(out, "w"), indent=1)
 for k, v in list(json.load(open(out))["kernels"].items())[:14]:
     print(f"{k[:70]:70s} util {v['mfma_util']:.3f}  active {v['gui_active_cycles_avg']}")

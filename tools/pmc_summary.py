@@ -23,7 +23,7 @@ for k in sorted(f):
     res[k] = {"launches_in_trace": n, "FETCH_SIZE_KiB_avg": round(fe, 1), "WRITE_SIZE_KiB_avg": round(wr, 1),
               "hbm_bytes_per_launch_corrected": int((2 * fe + wr) * 1024)}
 json.dump({"method": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in two separate passes over "
-                     "`python bench.py --steps 2 --warmup 1 --no-cpu-baseline --eager`; reads = 2 x FETCH_SIZE (gfx950), "
+                     "`python bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --eager`; reads = 2 x FETCH_SIZE (gfx950), "
                      "writes = WRITE_SIZE; Infinity-Cache hits are counted too, so re-reads beyond L2 show up here",
            "kernels": res}, open(out, "w"), indent=1)
 print("wrote", out, len(res), "kernels")

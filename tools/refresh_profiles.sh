@@ -11,13 +11,13 @@ O=$R/gpurun_out/profiles_$TAG
 mkdir -p "$O"
 # (each pass writes into a fresh directory: rocprofv3 adds files next to older ones)
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d "$O/stats" -- python3 "$R/bench.py" --steps 20 --warmup 5 --no-cpu-baseline > "$O/stats.log" 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d "$O/stats" -- python3 "$R/bench.py" --steps 20 --warmup 5 --full --no-cpu-baseline > "$O/stats.log" 2>&1
 echo "[refresh] stats done"
 for pass in FETCH_SIZE WRITE_SIZE; do
-    rocprofv3 --kernel-trace --pmc $pass --output-format csv -d "$O/$pass" -- python3 "$R/bench.py" --steps 2 --warmup 1 --no-cpu-baseline --eager > "$O/$pass.log" 2>&1
+    rocprofv3 --kernel-trace --pmc $pass --output-format csv -d "$O/$pass" -- python3 "$R/bench.py" --steps 2 --warmup 1 --full --no-cpu-baseline --eager > "$O/$pass.log" 2>&1
     echo "[refresh] $pass done"
 done
-rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -d "$O/mfma" -- python3 "$R/bench.py" --steps 2 --warmup 1 --no-cpu-baseline --eager > "$O/mfma.log" 2>&1
+rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -d "$O/mfma" -- python3 "$R/bench.py" --steps 2 --warmup 1 --full --no-cpu-baseline --eager > "$O/mfma.log" 2>&1
 echo "[refresh] mfma done"
-cd "$R" && python3 bench.py > "$O/bench.json" 2> "$O/bench.log"
+cd "$R" && python3 bench.py --full > "$O/bench.json" 2> "$O/bench.log"
 tail -1 "$O/bench.json" | cut -c1-300

@@ -9,7 +9,7 @@ mkdir -p "$O"
 # (each pass writes into a fresh directory: rocprofv3 adds files next to older ones)
 cd /tmp && export TMPDIR=/tmp
 for wl in force pr; do
-    rocprofv3 --kernel-trace --stats --output-format csv -d "$O/${wl}_stats" -- python3 "$R/bench.py" --workload $wl --steps 5 --warmup 2 --no-cpu-baseline > "$O/${wl}_stats.log" 2>&1
+    rocprofv3 --kernel-trace --stats --output-format csv -d "$O/${wl}_stats" -- python3 "$R/bench.py" --workload $wl --steps 5 --warmup 2 --full --no-cpu-baseline > "$O/${wl}_stats.log" 2>&1
     echo "[refresh2] $wl stats done"
 done
 for p in 0.0 0.1; do
@@ -20,6 +20,6 @@ for p in 0.0 0.1; do
 done
 cd "$R"
 for wl in force pr; do
-    python3 bench.py --workload $wl > "$O/bench_$wl.json" 2> "$O/bench_$wl.log"
+    python3 bench.py --workload $wl --full > "$O/bench_$wl.json" 2> "$O/bench_$wl.log"
     tail -1 "$O/bench_$wl.json" | cut -c1-200
 done
