@@ -47,6 +47,8 @@ ARGTYPES = {
     "aptai_conv0_fwd": [_P, _I64, _I64, _P, _P, _P, _P, _I, _F, _P, _I64, _I64, _I64, _I64, _I64, _P, _P, _P],
     "aptai_conv0_bwd": [_P, _I64, _I64, _P, _P, _P, _P, _I, _F, _P, _I64, _I64, _P, _P, _P, _P, _P, _P, _P],
     "aptai_conv0_bwd_workspace_bytes": [_I64, _I64],
+    "aptai_conv0_bwd_data": [_P, _I64, _I64, _P, _P, _P, _P, _I, _F, _P, _I64, _I64, _P, _P, _P, _P],
+    "aptai_conv0_bwd_data_workspace_bytes": [_I64, _I64],
     "aptai_conv0_workspace_bytes": [_I64, _I64],
     "aptai_head_act_fwd": [_P, _P, _P, _I64, _F, _F, _U64, _P],
     "aptai_head_act_bwd": [_P, _P, _P, _P, _I64, _F, _F, _U64, _P],

@@ -715,6 +715,205 @@ __global__ __launch_bounds__(1024) void conv0_bwd_reduce_kernel(const float* __r
     else { if (dbeta) dbeta[c] = (float)s; }
 }
 
+// ====================================================================================== data gradient of layer 0 (aptai_conv0_bwd_data)
+// daudio[b][s] = sum_{t in {s/5 - 1, s/5} n [0, T_real)} sum_c W[c][s - 5 t] du[b][t][c], du as in the weight passes above.
+// Pass C forms the per-frame tap sums g[b][t][k] = sum_c W[c][k] du[b][t][c] (the 512 -> 10 contraction) into a [B][T_real][10] fp32
+// workspace; pass D adds the two frames that overlap every sample (fixed order, no atomics) and writes every sample of daudio.
+
+// group mode, pass C on the fp32 matrix pipe.  The weight kernel's layout has the FRAMES on the lane's K index (q), so here the layout is
+// transposed (as in conv0_group_mfma_kernel): channels on the rows, frames on the columns, which puts the channel sum on the K index:
+//   (1) xhat[c][f]  = sum_k w'[c][k] x~[k][f]     A = taps folded with rstd (k = 10: (bias - mean) rstd against x~ = 1), B = waveform
+//   (2) g^T[k][f]  += sum_c W^T[k][c] du[c][f]    register r of (1) (channel ch(G, 4 q + r)) IS the B operand of K-step r; A = the taps
+//                                                  of those channels, from LDS ([pair][half][q][tap] order: one conflict-free 16-byte read)
+// Channel map ch(G, 4 q + r) = 32 (G / 2) + 8 q + 4 (G % 2) + r: a lane's rows of a PAIR of groups are 8 consecutive channels = one 16-byte
+// dy load per frame.  One wave = all 512 channels of 16 frames; the per-channel affine constants come from LDS (4 distinct addresses per read).
+__global__ __launch_bounds__(256) void conv0_bwd_data_group_mfma_kernel(Conv0BwdArgs a, float* __restrict__ gtap) {
+    __shared__ f32x4 wl[16 * 2 * 4 * 16];
+    __shared__ float cst[5][C0];                         // gamma, beta, gamma rstd, gamma rstd mean(dgn), gamma rstd mean(dgn xhat)
+    const Conv0Args& f = a.f;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int q = lane >> 4, i = lane & 15;
+    const int b = blockIdx.y, chunk = blockIdx.x;
+    for (int idx = threadIdx.x; idx < 16 * 2 * 4 * 16; idx += 256) {
+        const int ti = idx & 15, qq = (idx >> 4) & 3, h = (idx >> 6) & 1, P = idx >> 7;
+        const int c = 32 * P + 8 * qq + 4 * h;
+        f32x4 v;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[r] = ti < KW ? f.w[(c + r) * KW + ti] : 0.f;
+        wl[idx] = v;
+    }
+    for (int c = threadIdx.x; c < C0; c += 256) {
+        const float gm = f.gamma[c], gr = gm * f.stats[((long)b * 2 + 1) * C0 + c];
+        cst[0][c] = gm;
+        cst[1][c] = f.beta[c];
+        cst[2][c] = gr;
+        cst[3][c] = gr * a.gmean[((long)b * 2 + 0) * C0 + c];
+        cst[4][c] = gr * a.gmean[((long)b * 2 + 1) * C0 + c];
+    }
+    float w1[32][3];                                     // A operand of (1): row i = channel ch(G, i), k = 4 s + q
+#pragma unroll
+    for (int G = 0; G < 32; ++G) {
+        const int c = 32 * (G >> 1) + 8 * (i >> 2) + 4 * (G & 1) + (i & 3);
+        const float mu = f.stats[((long)b * 2 + 0) * C0 + c], rs = f.stats[((long)b * 2 + 1) * C0 + c];
+#pragma unroll
+        for (int s = 0; s < 3; ++s) {
+            const int k = 4 * s + q;
+            w1[G][s] = k < KW ? f.w[c * KW + k] * rs : (k == KW ? ((f.bias ? f.bias[c] : 0.f) - mu) * rs : 0.f);
+        }
+    }
+    __syncthreads();
+    const float* xb = f.audio + (long)b * f.S;
+    const bf16_t* dyb = a.dy + (long)b * f.T_alloc * C0 + 8 * q;
+    const long last = f.S - 1;
+    const int tb = chunk * BWD_FRAMES_PER_BLOCK;
+    int t1 = tb + BWD_FRAMES_PER_BLOCK;
+    t1 = t1 < f.T_real ? t1 : f.T_real;
+    int te = frames_collated(f.bounds, f.T_real);
+    te = te < t1 ? te : t1;
+    for (int t0 = tb + 16 * wave; t0 < t1; t0 += 64) {
+        // the LDS operands are loop-invariant: without this fence the compiler hoists all 32 groups' reads (768 registers) out of the loop
+        asm volatile("" ::: "memory");
+        const int t = t0 + i;                            // this lane's frame: the column of both products
+        const bool live = t < te;
+        float xt[3];
+#pragma unroll
+        for (int s = 0; s < 3; ++s) {
+            const int k = 4 * s + q;
+            long idx = (long)t * STRIDE + k;
+            idx = idx < last ? idx : last;
+            const float v = xb[idx];
+            xt[s] = k < KW ? v : (k == KW ? 1.0f : 0.f);
+        }
+        const bf16_t* drow = dyb + (long)(t < f.T_real ? t : f.T_real - 1) * C0;      // rows >= T_real are never read
+        u32x4 dq[16];
+#pragma unroll
+        for (int P = 0; P < 16; ++P) dq[P] = *(const u32x4*)(drow + 32 * P);
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int P = 0; P < 16; ++P) {
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int G = 2 * P + h, cb = 32 * P + 8 * q + 4 * h;
+                f32x4 xh = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int s = 0; s < 3; ++s) xh = __builtin_amdgcn_mfma_f32_16x16x4f32(w1[G][s], xt[s], xh, 0, 0, 0);
+                const f32x4 gm = *(const f32x4*)&cst[0][cb], bt = *(const f32x4*)&cst[1][cb], gr = *(const f32x4*)&cst[2][cb];
+                const f32x4 m1g = *(const f32x4*)&cst[3][cb], m2g = *(const f32x4*)&cst[4][cb];
+                float du[4];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const uint32_t pair = dq[P][2 * h + (r >> 1)];
+                    const float d = (r & 1) ? hi_bf(pair) : lo_bf(pair);
+                    const float dgn = d * gelu_fast_grad(fmaf(xh[r], gm[r], bt[r]));
+                    const float v = fmaf(dgn, gr[r], -fmaf(xh[r], m2g[r], m1g[r]));
+                    du[r] = live ? v : 0.f;
+                }
+                const f32x4 wt = wl[((P * 2 + h) * 4 + q) * 16 + i];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wt[r], du[r], acc, 0, 0, 0);
+            }
+        }
+        // acc[r] = g[t][4 q + r] (rows 10..15 met zero taps)
+        if (t < t1) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int k = 4 * q + r;
+                if (k < KW) gtap[((long)b * f.T_real + t) * KW + k] = acc[r];
+            }
+        }
+    }
+}
+
+// sum over the 64 lanes of 16 values at once: each butterfly step halves the values a lane keeps (15 shuffles, against 6 per value for
+// sixteen wave_sum calls); then the 4 lanes that hold the same index finish it.  Returns the total of value `idx` (lane bits 5..2).
+__device__ __forceinline__ float wave_sum16(const float (&p)[16], int lane, int& idx) {
+    float p8[8], p4[4], p2[2];
+    const bool h5 = lane & 32, h4 = lane & 16, h3 = lane & 8, h2 = lane & 4;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) p8[k] = (h5 ? p[k + 8] : p[k]) + __shfl_xor(h5 ? p[k] : p[k + 8], 32, 64);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) p4[k] = (h4 ? p8[k + 4] : p8[k]) + __shfl_xor(h4 ? p8[k] : p8[k + 4], 16, 64);
+#pragma unroll
+    for (int k = 0; k < 2; ++k) p2[k] = (h3 ? p4[k + 2] : p4[k]) + __shfl_xor(h3 ? p4[k] : p4[k + 2], 8, 64);
+    float v = (h2 ? p2[1] : p2[0]) + __shfl_xor(h2 ? p2[0] : p2[1], 4, 64);
+    v += __shfl_xor(v, 2, 64);
+    v += __shfl_xor(v, 1, 64);
+    idx = (h5 ? 8 : 0) + (h4 ? 4 : 0) + (h3 ? 2 : 0) + (h2 ? 1 : 0);
+    return v;
+}
+
+// layer mode, pass C on the vector pipe: one wave per frame (the per-frame LayerNorm backward of conv0_bwd_weight_kernel<1>), then the
+// lane's 8 channels contracted against the taps it holds in registers and the 10 sums reduced by wave_sum16.
+__global__ __launch_bounds__(256) void conv0_bwd_data_layer_kernel(Conv0BwdArgs a, float* __restrict__ gtap) {
+    const Conv0Args& f = a.f;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int b = blockIdx.y, chunk = blockIdx.x;
+    float w[8][KW], bias[8], gm[8], bt[8];
+    load_weights(f, lane, w, bias);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { gm[j] = f.gamma[lane * 8 + j]; bt[j] = f.beta[lane * 8 + j]; }
+    const float* xb = f.audio + (long)b * f.S;
+    const bf16_t* dyb = a.dy + (long)b * f.T_alloc * C0;
+    const int t0 = chunk * BWD_FRAMES_PER_BLOCK;
+    int t1 = t0 + BWD_FRAMES_PER_BLOCK;
+    t1 = t1 < f.T_real ? t1 : f.T_real;
+    for (int t = t0 + wave; t < t1; t += 4) {
+        float v[8], d[8], du[8];
+        conv_frame(xb + (long)t * STRIDE, w, bias, v);
+        load8bf(dyb + (long)t * C0 + lane * 8, d);
+        float s = 0.f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) s += v[j];
+        const float mean = wave_sum(s) * (1.0f / C0);
+        float qv = 0.f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { const float e = v[j] - mean; qv += e * e; }
+        const float rstd = rsqrtf(wave_sum(qv) * (1.0f / C0) + f.eps);
+        float xh[8], gd[8], s1 = 0.f, s2 = 0.f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            xh[j] = (v[j] - mean) * rstd;
+            gd[j] = d[j] * gelu_fast_grad(fmaf(xh[j], gm[j], bt[j])) * gm[j];
+            s1 += gd[j];
+            s2 = fmaf(gd[j], xh[j], s2);
+        }
+        s1 = wave_sum(s1) * (1.0f / C0);
+        s2 = wave_sum(s2) * (1.0f / C0);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) du[j] = rstd * (gd[j] - s1 - xh[j] * s2);
+        float p[16];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) p[k] = 0.f;
+#pragma unroll
+        for (int k = 0; k < KW; ++k)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) p[k] = fmaf(w[j][k], du[j], p[k]);
+        int k;
+        const float g = wave_sum16(p, lane, k);
+        if ((lane & 3) == 0 && k < KW) gtap[((long)b * f.T_real + t) * KW + k] = g;
+    }
+}
+
+// pass D: every sample of daudio from the tap sums of the (at most two) frames whose windows hold it; zero where no window reaches
+__global__ __launch_bounds__(256) void conv0_bwd_data_samples_kernel(const float* __restrict__ gtap, float* __restrict__ daudio, long S,
+                                                                     int T_real) {
+    const int b = blockIdx.y;
+    const float* g = gtap + (long)b * T_real * KW;
+    for (long s = (long)blockIdx.x * 256 + threadIdx.x; s < S; s += (long)gridDim.x * 256) {
+        const long t = s / STRIDE;
+        const int r = (int)(s - t * STRIDE);
+        float v = t < T_real ? g[t * KW + r] : 0.f;
+        if (t >= 1 && t - 1 < T_real) v += g[(t - 1) * KW + r + STRIDE];
+        daudio[(long)b * S + s] = v;
+    }
+}
+
+// both group-mode passes' contractions on the fp32 matrix pipe (APTAI_CONV0_BWD_MFMA=0: the all-vector kernels, A/B)
+bool conv0_bwd_mfma() {
+    static const bool on = !(getenv("APTAI_CONV0_BWD_MFMA") && atoi(getenv("APTAI_CONV0_BWD_MFMA")) == 0);
+    return on;
+}
+
 }  // namespace
 
 extern "C" int64_t aptai_conv0_workspace_bytes(int64_t B, int64_t T_real) {
@@ -806,8 +1005,7 @@ extern "C" int aptai_conv0_bwd(const float* audio, int64_t B, int64_t S, const f
     a.wpart = gmean + (long)B * 2 * C0;
     dim3 grid((unsigned)a.f.nchunks, (unsigned)B);
     if (mode == 0) {
-        // both passes' contractions on the fp32 matrix pipe (APTAI_CONV0_BWD_MFMA=0: the all-vector kernels, A/B)
-        static const bool bwd_mfma = !(getenv("APTAI_CONV0_BWD_MFMA") && atoi(getenv("APTAI_CONV0_BWD_MFMA")) == 0);
+        const bool bwd_mfma = conv0_bwd_mfma();
         if (bwd_mfma) APTAI_LAUNCH(conv0_bwd_group_stats_mfma_kernel, grid, dim3(256), 0, stream, a);
         else APTAI_LAUNCH(conv0_bwd_group_stats_kernel, grid, dim3(256), 0, stream, a);
         APTAI_CHECK_LAUNCH("conv0_bwd_group_stats_kernel");
@@ -823,5 +1021,55 @@ extern "C" int aptai_conv0_bwd(const float* audio, int64_t B, int64_t S, const f
     APTAI_LAUNCH(conv0_bwd_reduce_kernel, dim3((unsigned)ceil_div(C0 * 13, 64)), dim3(1024), 0, stream, (const float*)a.wpart,
                  (int)(B * a.f.nchunks), dweight, bias ? dbias : nullptr, mode == 1 ? dgamma : nullptr, mode == 1 ? dbeta : nullptr);
     APTAI_CHECK_LAUNCH("conv0_bwd_reduce_kernel");
+    return APTAI_OK;
+}
+
+extern "C" int64_t aptai_conv0_bwd_data_workspace_bytes(int64_t B, int64_t T_real) {
+    const long nch = ceil_div(T_real, BWD_FRAMES_PER_BLOCK);
+    return (B * nch * 2 * C0 + B * 2 * C0 + B * T_real * KW) * 4;
+}
+
+/* Gradient w.r.t. the waveform.  Arguments as aptai_conv0_bwd; daudio fp32 [B][S], every sample written.  dy rows >= T_real are not read
+   by the data passes (group mode's statistics pass, shared with aptai_conv0_bwd, masks them). */
+extern "C" int aptai_conv0_bwd_data(const float* audio, int64_t B, int64_t S, const float* weight, const float* bias, const float* gamma,
+                                    const float* beta, int mode, float eps, const void* dy, int64_t T_real, int64_t T_alloc,
+                                    const float* fwd_stats, float* daudio, void* workspace, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    APTAI_REQUIRE(audio && weight && gamma && beta && dy && daudio && workspace, "aptai_conv0_bwd_data: null pointer");
+    APTAI_REQUIRE(mode == 0 || mode == 1, "aptai_conv0_bwd_data: mode");
+    APTAI_REQUIRE(mode == 1 || fwd_stats, "aptai_conv0_bwd_data: group mode needs the forward statistics");
+    APTAI_REQUIRE(B > 0 && T_real > 0 && (T_real - 1) * STRIDE + KW <= S && T_alloc >= T_real, "aptai_conv0_bwd_data: bad frame counts");
+    Conv0BwdArgs a;
+    memset(&a, 0, sizeof(a));
+    a.f.audio = audio; a.f.S = S; a.f.w = weight; a.f.bias = bias; a.f.gamma = gamma; a.f.beta = beta; a.f.B = (int)B;
+    a.f.T_real = (int)T_real; a.f.T_alloc = (int)T_alloc; a.f.eps = eps; a.f.stats = fwd_stats;
+    a.f.nchunks = (int)ceil_div(T_real, BWD_FRAMES_PER_BLOCK);
+    a.f.bounds = mode == 0 ? (const int*)aptai_frame_bounds(stream_) : nullptr;
+    a.dy = (const bf16_t*)dy;
+    float* ws = (float*)workspace;
+    a.gpart = ws;
+    float* gmean = ws + (long)B * a.f.nchunks * 2 * C0;
+    a.gmean = gmean;
+    float* gtap = gmean + (long)B * 2 * C0;
+    dim3 grid((unsigned)a.f.nchunks, (unsigned)B);
+    if (mode == 0) {
+        // pass A and its reduction exactly as aptai_conv0_bwd runs them (same means, same frame bounds); no dgamma / dbeta
+        if (conv0_bwd_mfma()) APTAI_LAUNCH(conv0_bwd_group_stats_mfma_kernel, grid, dim3(256), 0, stream, a);
+        else APTAI_LAUNCH(conv0_bwd_group_stats_kernel, grid, dim3(256), 0, stream, a);
+        APTAI_CHECK_LAUNCH("conv0_bwd_group_stats_kernel");
+        APTAI_LAUNCH(conv0_bwd_group_final_kernel, dim3(C0 / 64), dim3(1024), 0, stream, (const float*)a.gpart, gmean, (float*)nullptr,
+                     (float*)nullptr, (int)B, a.f.nchunks, (int)T_real, (const int*)aptai_frame_bounds((const void*)stream));
+        APTAI_CHECK_LAUNCH("conv0_bwd_group_final_kernel");
+        APTAI_LAUNCH(conv0_bwd_data_group_mfma_kernel, grid, dim3(256), 0, stream, a, gtap);
+        APTAI_CHECK_LAUNCH("conv0_bwd_data_group_mfma_kernel");
+    } else {
+        APTAI_LAUNCH(conv0_bwd_data_layer_kernel, grid, dim3(256), 0, stream, a, gtap);
+        APTAI_CHECK_LAUNCH("conv0_bwd_data_layer_kernel");
+    }
+    long sb = ceil_div(S, 256);
+    if (sb > 1024) sb = 1024;
+    APTAI_LAUNCH(conv0_bwd_data_samples_kernel, dim3((unsigned)sb, (unsigned)B), dim3(256), 0, stream, (const float*)gtap, daudio, (long)S,
+                 (int)T_real);
+    APTAI_CHECK_LAUNCH("conv0_bwd_data_samples_kernel");
     return APTAI_OK;
 }

@@ -375,7 +375,7 @@ class GraphedAPTAIStep:
         self.g_front_bwd = mk()
         with torch.cuda.graph(self.g_front_bwd, pool=pool, stream=self._cap_stream, capture_error_mode=_CAPTURE_MODE):
             dfeats, fg = self.front.bwd(self.s_front, (self.dX[0],), self.train_conv)
-            conv_grads = w._conv_backward(self.sv_conv, g, dfeats.contiguous()) if self.train_conv else []
+            conv_grads = w._conv_backward(self.sv_conv, g, dfeats.contiguous())[1] if self.train_conv else []
         for p, gt in zip(self.fparams, fg):
             if p is not None and gt is not None:
                 self.grads[p] = gt

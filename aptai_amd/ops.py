@@ -692,6 +692,17 @@ def conv0_bwd(audio, weight, bias, gamma, beta, mode, dy, T_real, T_alloc, stats
     return dw, db, dg, dbt
 
 
+def conv0_bwd_data(audio, weight, bias, gamma, beta, mode, dy, T_real, T_alloc, stats, eps=1e-5):
+    """Gradient w.r.t. the waveform of the first conv layer (aptai_conv0_bwd_data): daudio fp32 [B][S], arguments as conv0_bwd."""
+    _dev(audio, weight, bias, gamma, beta, dy, stats)
+    B, S = audio.shape
+    daudio = torch.empty((B, S), device=audio.device, dtype=torch.float32)
+    ws = _ws(_lib.lib().aptai_conv0_bwd_data_workspace_bytes(B, T_real), audio.device)
+    _lib.call("aptai_conv0_bwd_data", audio.data_ptr(), B, S, weight.data_ptr(), _ptr(bias), gamma.data_ptr(), beta.data_ptr(), mode, eps,
+              dy.data_ptr(), T_real, T_alloc, _ptr(stats), daudio.data_ptr(), ws.data_ptr(), _stream())
+    return daudio
+
+
 # ----------------------------------------------------------------------------- APTAI heads
 def head_act_fwd(h, p_tv, p_ph, seed):
     _dev(h)

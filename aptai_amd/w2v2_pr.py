@@ -187,7 +187,8 @@ class Wav2Vec2_PR(nn.Module):
         """models/w2v2_pr.py:91-122: the encoder in whatever mode the module is in, WITH gradients (probing / saliency use):
         the last, an intermediate and a latter hidden state as (batch, feat, time), and `pr_head` applied to each of the three.
         `features_hidden` (the reference's separate `feature_extractor` pass, :93) is the conv stack's output (batch, 512, time).
-        Gradients flow from every returned tensor into the encoder's trainable parameters."""
+        Gradients flow from every returned tensor into the encoder's trainable parameters and, when `audio_inputs.requires_grad`,
+        into the waveform (`audio_inputs.grad`: saliency / attribution), `features_hidden` included."""
         out = self.wav2vec2(audio_inputs, attention_mask=audio_lengths[:, None], return_dict=True, output_hidden_states=True)
         g = out._geom
         W, bvec = self.pr_head.weight, self.pr_head.bias

@@ -94,8 +94,8 @@ def _run(impl, x, *params):
 
 
 class _ConvStackFn(torch.autograd.Function):
-    """Trainable feature encoder (Wav2Vec2_PR fine-tuning, train/train_phoneme_recognizer.py): forward saves the layer
-    outputs / pre-activations, backward = Wav2Vec2Model._conv_backward."""
+    """Feature encoder under autograd: trainable conv stack (Wav2Vec2_PR fine-tuning, train/train_phoneme_recognizer.py) and/or a
+    waveform that requires grad.  Forward saves the layer outputs / pre-activations, backward = Wav2Vec2Model._conv_backward."""
 
     @staticmethod
     def forward(ctx, audio, model, g, *params):
@@ -105,9 +105,13 @@ class _ConvStackFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dfeats):
-        grads = ctx.model._conv_backward(ctx.sv, ctx.g, dfeats.contiguous())
+        want_audio = ctx.needs_input_grad[0]
+        want_params = any(ctx.needs_input_grad[3:])
+        daudio, grads = ctx.model._conv_backward(ctx.sv, ctx.g, dfeats.contiguous(), want_params=want_params, want_audio=want_audio)
         ctx.sv = None
-        return (None, None, None) + tuple(grads)
+        if not want_params:
+            grads = [None] * (len(ctx.needs_input_grad) - 3)
+        return (daudio, None, None) + tuple(grads)
 
 
 def _seed(base: int, *ids: int) -> int:
@@ -813,10 +817,11 @@ class Wav2Vec2Model(nn.Module):
                 sv.bufs.append(buf)
         return buf[:g.M], sv
 
-    def _conv_backward(self, sv, g, dfeats):
-        """Gradients of every conv-stack parameter (order of _conv_params).  dgrad of a strided conv = the weight GEMM on the
-        SAME overlapping-row view: columns [0, s*C) of the virtual-row gradient own frames s*t .. s*t+s-1 outright, the
-        remaining (k-s)*C columns are accumulated one virtual row later."""
+    def _conv_backward(self, sv, g, dfeats, want_params=True, want_audio=False):
+        """(gradient w.r.t. the waveform | None, gradients of every conv-stack parameter in the order of _conv_params | None).
+        dgrad of a strided conv = the weight GEMM on the SAME overlapping-row view: columns [0, s*C) of the virtual-row gradient own
+        frames s*t .. s*t+s-1 outright, the remaining (k-s)*C columns are accumulated one virtual row later.  want_params=False
+        (frozen conv stack, waveform requires grad): only the data gradients run - no weight GEMMs, column sums or aptai_conv0_bwd."""
         cfg = self.config
         cl = self.feature_extractor.conv_layers
         C = 512
@@ -837,11 +842,12 @@ class Wav2Vec2Model(nn.Module):
                 grads[(i, "ln_w")], grads[(i, "ln_b")] = dgam, dbet
             else:
                 du = dy[:Mi] if du_ready else ops.dgelu(dy[:Mi].contiguous(), sv.pre[i][:Mi])
-            if cfg.conv_bias:
-                grads[(i, "b")] = ops.colsum(du, Mi, C)
-            sk = max(1, min(16, Mi // 4096))
-            dw = ops.gemm(du, x_in, C, k * C, Mi, a_kmajor=True, b_kmajor=True, out_f32=True, ldb=s * C, split_k=sk)
-            grads[(i, "w")] = dw.view(C, k, C).permute(0, 2, 1).contiguous()          # [N][kw][c] -> nn.Conv1d's [N][c][kw]
+            if want_params:
+                if cfg.conv_bias:
+                    grads[(i, "b")] = ops.colsum(du, Mi, C)
+                sk = max(1, min(16, Mi // 4096))
+                dw = ops.gemm(du, x_in, C, k * C, Mi, a_kmajor=True, b_kmajor=True, out_f32=True, ldb=s * C, split_k=sk)
+                grads[(i, "w")] = dw.view(C, k, C).permute(0, 2, 1).contiguous()      # [N][kw][c] -> nn.Conv1d's [N][c][kw]
             # ---- dgrad into the output of layer i-1
             dx = _rows_with_zero_slack(g.B * g.alloc[i - 1] + 8, C, dev)
             fuse = (not layer_mode) and (i - 1 >= 1)         # base: fold gelu'(u_{i-1}) into the epilogue
@@ -855,8 +861,12 @@ class Wav2Vec2Model(nn.Module):
             dy = dx
             du_ready = fuse
         l0 = cl[0]
-        dw0, db0, dg0, dbt0 = ops.conv0_bwd(sv.audio, l0.conv.weight, l0.conv.bias if cfg.conv_bias else None, l0.layer_norm.weight,
-                                            l0.layer_norm.bias, 1 if layer_mode else 0, dy, g.Tl[0], g.alloc[0], sv.stats0)
+        args0 = (sv.audio, l0.conv.weight, l0.conv.bias if cfg.conv_bias else None, l0.layer_norm.weight, l0.layer_norm.bias,
+                 1 if layer_mode else 0, dy, g.Tl[0], g.alloc[0], sv.stats0)
+        daudio = ops.conv0_bwd_data(*args0) if want_audio else None
+        if not want_params:
+            return daudio, None
+        dw0, db0, dg0, dbt0 = ops.conv0_bwd(*args0)
         grads[(0, "w")], grads[(0, "b")], grads[(0, "ln_w")], grads[(0, "ln_b")] = dw0, db0, dg0, dbt0
         out = []
         for i in range(len(cl)):
@@ -865,11 +875,12 @@ class Wav2Vec2Model(nn.Module):
                 out.append(grads[(i, "b")])
             if layer_mode or i == 0:
                 out += [grads[(i, "ln_w")], grads[(i, "ln_b")]]
-        return out
+        return daudio, out
 
     def _feature_encoder(self, audio: torch.Tensor, g) -> torch.Tensor:
         params = self._conv_params()
-        trainable = torch.is_grad_enabled() and any(p.requires_grad for p in params)
+        # autograd path when a conv parameter OR the waveform requires grad (input gradients: saliency, attribution)
+        trainable = torch.is_grad_enabled() and (audio.requires_grad or any(p.requires_grad for p in params))
         if not trainable:
             with torch.no_grad():
                 return self._conv_forward(audio, g, save=False)[0]

@@ -290,6 +290,13 @@ int aptai_conv0_bwd(const float* audio, int64_t B, int64_t S, const float* weigh
                     const float* fwd_stats, float* dweight, float* dbias, float* dgamma, float* dbeta, void* workspace,
                     void* stream);
 int64_t aptai_conv0_bwd_workspace_bytes(int64_t B, int64_t T_real);
+/* gradient w.r.t. the waveform of the same fused layer: du as in aptai_conv0_bwd (group mode: the same statistics pass), then
+ * daudio[b][s] = sum over the frames t in {s/5 - 1, s/5} below T_real of sum_c W[c][s - 5 t] du[b][t][c].  daudio fp32 [B][S]: every
+ * sample written (0 where no window reaches); dy rows >= T_real are not read by the data passes; deterministic (no atomics). */
+int aptai_conv0_bwd_data(const float* audio, int64_t B, int64_t S, const float* weight, const float* bias, const float* gamma,
+                         const float* beta, int mode, float eps, const void* dy, int64_t T_real, int64_t T_alloc,
+                         const float* fwd_stats, float* daudio, void* workspace, void* stream);
+int64_t aptai_conv0_bwd_data_workspace_bytes(int64_t B, int64_t T_real);
 
 /* ------------------------------------------------------------------------------------------------ APTAI heads
  * a_tv = tanh(dropout(h)), a_ph = leaky_relu(dropout(h)) — the activations in front of the two head Linears
