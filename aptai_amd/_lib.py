@@ -33,6 +33,8 @@ ARGTYPES = {
     "aptai_layernorm_fwd_f32in_split": [_P, _P, _P, _P, _P, _I, _I64, _I64, _F, _P],
     "aptai_attention_fwd": [_P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _F, _F, _U64, _I, _P],
     "aptai_attention_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _F, _F, _U64, _I, _I, _P],
+    "aptai_attention_probs_fwd": [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _F, _F, _U64, _I, _P],
+    "aptai_attention_probs_bwd": [_P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _F, _F, _U64, _I, _I, _P],
     "aptai_cast_f32_to_bf16": [_P, _P, _I64, _I64, _I64, _P],
     "aptai_conv_weight_to_bf16": [_P, _P, _I64, _I64, _I64, _P],
     "aptai_posconv_weight": [_P, _P, _P, _P, _P, _I64, _I64, _I64, _P],

@@ -948,6 +948,392 @@ __global__ __launch_bounds__(256, NPQ == 2 ? 2 : 1) void attn_exact_fwd_kernel(A
     }
 }
 
+// ================================================================================== attention probabilities (output_attentions)
+// The map the fused forward never writes, rebuilt from what it saved: P[q][k] = exp2(x[q][k] - lse2[q]) needs no row reduction, so
+// one launch is S^T = K Q^T on the matrix pipe plus one fp32 write of [B][heads][Tp][Tp] (row pitch Tp: every row starts on a
+// 2-KB boundary).  Same semantics as HF's eager attention: the returned tensor is the softmax AFTER dropout (keep * P / (1 - p),
+// the mask of the fused kernels: same row hash, same pair mix), masked key columns are exactly 0, query rows beyond lens[b] are
+// computed like all others.  The kernel is bound by its write: a lane of the S^T accumulator owns one QUERY (16 keys at a row
+// stride), so the tile goes through the wave's own LDS staging area and leaves as 16-byte chunks of whole 128-byte row segments.
+struct ProbsArgs {
+    AttnArgs a;
+    float* probs;                   // forward: [B][heads][Tp][Tp] fp32
+    const float* dprobs;            // backward: gradient of the loss w.r.t. the returned tensor, same layout
+    float* rowsum;                  // backward: [B][heads][Tp] fp32, sum_k keep * dprobs * P of every query row (dQ kernel -> dK kernel)
+    int accumulate;                 // backward: add to the Q and K thirds of dqkv instead of overwriting them
+};
+constexpr int PROBS_KBUF = 64 * 128;                            // one K tile of the forward (64 keys)
+
+// grid (Tp/128, heads, B), 256 threads; wave w: queries q0 = qt*128 + w*32 .. +31, all keys
+template <bool DROP>
+__global__ __launch_bounds__(256, 3) void attn_probs_fwd_kernel(ProbsArgs pa) {
+    __shared__ __attribute__((aligned(16))) char smem[2 * PROBS_KBUF + STAGE_BYTES];      // 2-deep K ring; [32][OUT_PITCH] staging per wave
+    if (DROP) apply_salt(pa.a.salt, pa.a.seed0, pa.a.seed1);
+    const AttnArgs& a = pa.a;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, r31 = lane & 31;
+    int tile_x, hd, b;
+    attn_block(a, tile_x, hd, b);
+    const int q0 = tile_x * 128 + wave * 32;
+    int len = a.lens[b];
+    len = len < 1 ? 1 : (len > a.Tp ? a.Tp : len);
+    const int ntiles = (len + 63) >> 6;
+    const long rowbase = (long)b * a.Tp, bh = (long)b * a.heads + hd;
+    const int q = q0 + r31;
+    const bf16_t* Qg = a.qkv + (rowbase + q) * a.ld + hd * HD;
+    const bf16_t* Kg = a.qkv + rowbase * a.ld + a.H + hd * HD;
+    const LaneOffs lo = lane_offs(lane);
+    bf16x8 qf[4];
+#pragma unroll
+    for (int ds = 0; ds < 4; ++ds) qf[ds] = *(const bf16x8*)(Qg + ds * 16 + h * 8);
+    const float nlse = -a.lse2[bh * a.Tp + q];
+    float* out0 = pa.probs + (bh * a.Tp + q0) * a.Tp;           // row q0 (the wave's first query), key 0
+    // key tiles wholly beyond the utterance: exact zeros, 4 rows x 256 bytes per instruction
+    {
+        const f32x4 z = (f32x4)(0.f);
+        for (int kt = ntiles * 64; kt < a.Tp; kt += 64) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const int idx = i * 64 + lane, r = idx >> 4, ch = idx & 15;
+                *(f32x4*)(out0 + (long)r * a.Tp + kt + ch * 4) = z;
+            }
+        }
+    }
+    int soff[2];
+    long goff[2];
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+        const int cid = it * 256 + tid, row = cid >> 3, ch = cid & 7;
+        soff[it] = tile_off(row, ch);
+        goff[it] = (long)row * a.ld + ch * 8;
+    }
+    u32x4 kreg[2];
+    const long tile_stride = 64 * a.ld;
+#pragma unroll
+    for (int it = 0; it < 2; ++it) kreg[it] = *(const u32x4*)(Kg + goff[it]);
+    uint32_t hbase = 0;                      // dropout: row hash of this lane's query + 2 h K1 (see attn_fwd_kernel)
+    if (DROP) hbase = rng_hash((uint32_t)(bh * a.Tp + q), a.seed0, a.seed1) + (uint32_t)(2 * h) * ATTN_K1;
+    const float c = a.c, dscale = a.dscale;
+#pragma unroll
+    for (int it = 0; it < 2; ++it) *(u32x4*)(smem + soff[it]) = kreg[it];
+    if (ntiles > 1) {
+#pragma unroll
+        for (int it = 0; it < 2; ++it) kreg[it] = *(const u32x4*)(Kg + tile_stride + goff[it]);
+    }
+    __syncthreads();
+    char* sw = smem + 2 * PROBS_KBUF + wave * (32 * OUT_PITCH);
+    for (int t = 0; t < ntiles; ++t) {
+        const char* sK = smem + (t & 1) * PROBS_KBUF;
+        bf16x8 kfr[2][4];
+#pragma unroll
+        for (int kt2 = 0; kt2 < 2; ++kt2)
+#pragma unroll
+            for (int ds = 0; ds < 4; ++ds) kfr[kt2][ds] = rd_row(sK, lo, kt2, ds);
+        if (t + 1 < ntiles) {
+            char* nb = smem + ((t + 1) & 1) * PROBS_KBUF;
+#pragma unroll
+            for (int it = 0; it < 2; ++it) *(u32x4*)(nb + soff[it]) = kreg[it];
+            if (t + 2 < ntiles) {
+                const bf16_t* kn = Kg + (long)(t + 2) * tile_stride;
+#pragma unroll
+                for (int it = 0; it < 2; ++it) kreg[it] = *(const u32x4*)(kn + goff[it]);
+            }
+        }
+        const bool last = t + 1 == ntiles;
+#pragma unroll
+        for (int kt2 = 0; kt2 < 2; ++kt2) {
+            // S^T tile: keys (t*64 + kt2*32 + acc_row) x queries (lane&31)
+            f32x16 sT = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfr[kt2][0], qf[0], (f32x16)(0.f), 0, 0, 0);
+#pragma unroll
+            for (int ds = 1; ds < 4; ++ds) sT = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfr[kt2][ds], qf[ds], sT, 0, 0, 0);
+            const int kb = t * 64 + kt2 * 32;
+            float x[16];
+#pragma unroll
+            for (int r = 0; r < 16; ++r) x[r] = fast_exp2(fmaf(sT[r], c, nlse));
+            if (last) {                                         // block-uniform: only the tile holding key len-1 masks
+#pragma unroll
+                for (int r = 0; r < 16; ++r) x[r] = (kb + acc_row(r, h) >= len) ? 0.f : x[r];
+            }
+            if (DROP) {
+#pragma unroll
+                for (int r = 0; r < 16; r += 2) {              // registers r, r+1 are consecutive keys: one hash per pair
+                    const uint32_t hsh = attn_mix(hbase + (uint32_t)(kb / 2 + acc_row(r, 0) / 2) * ATTN_K1);
+                    x[r] = (hsh & 0xffffu) >= a.thr16 ? x[r] * dscale : 0.f;
+                    x[r + 1] = (hsh >> 16) >= a.thr16 ? x[r + 1] * dscale : 0.f;
+                }
+            }
+#pragma unroll
+            for (int g4 = 0; g4 < 4; ++g4)
+                *(f32x4*)(sw + r31 * OUT_PITCH + (8 * g4 + 4 * h) * 4) = (f32x4){x[4 * g4], x[4 * g4 + 1], x[4 * g4 + 2], x[4 * g4 + 3]};
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");      // same wave, LDS in order: only the compiler must not reorder
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int idx = i * 64 + lane, r = idx >> 3, ch = idx & 7;
+                const f32x4 v = *(const f32x4*)(sw + r * OUT_PITCH + ch * 16);
+                *(f32x4*)(out0 + (long)r * a.Tp + kb + ch * 4) = v;      // (non-temporal stores measured the same: DESIGN.md section 8)
+            }
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        }
+        __syncthreads();           // every wave has read buffer t&1; buffer (t+1)&1 is written
+    }
+}
+
+// the wave's transposed accumulator pair (see store_rows_bf16) as bf16 rows, optionally ADDED to what the rows hold: through the
+// wave's staging area in fp32 (32 features at a time), so the sum is rounded once; every element is read and written by one lane
+__device__ __forceinline__ void store_rows_bf16_acc(char* sw, const f32x16 (&acc)[2], float scale, bf16_t* g_row0, long ld, int lane,
+                                                    int accumulate) {
+    const int r31 = lane & 31, h = lane >> 5;
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt) {
+#pragma unroll
+        for (int g4 = 0; g4 < 4; ++g4)
+            *(f32x4*)(sw + r31 * OUT_PITCH + (8 * g4 + 4 * h) * 4) =
+                (f32x4){acc[dt][4 * g4] * scale, acc[dt][4 * g4 + 1] * scale, acc[dt][4 * g4 + 2] * scale, acc[dt][4 * g4 + 3] * scale};
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int idx = i * 64 + lane, r = idx >> 3, ch = idx & 7;
+            f32x4 v = *(const f32x4*)(sw + r * OUT_PITCH + ch * 16);
+            bf16_t* gp = g_row0 + (long)r * ld + dt * 32 + ch * 4;
+            if (accumulate) {
+                const u32x2 o = *(const u32x2*)gp;
+                v[0] += lo_bf(o[0]); v[1] += hi_bf(o[0]); v[2] += lo_bf(o[1]); v[3] += hi_bf(o[1]);
+            }
+            *(u32x2*)gp = (u32x2){pack2bf(v[0], v[1]), pack2bf(v[2], v[3])};
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+}
+
+// ---- backward of the map: dS = P (dP - rowsum(dP P)), dP = keep * dprobs / (1 - p); dQ = scale dS K, dK = scale dS^T Q.
+// Both kernels work with dP / dscale and apply dscale = 1 / (1 - p) once in their epilogues (as the fused backward does).
+// dQ kernel: grid (Tp/128, heads, B); wave w owns queries qt*128 + w*32 .. +31 (one per lane, S^T = K Q^T) and walks the 32-key
+// tiles of the utterance TWICE: the first walk forms the row sums (fp32, left in pa.rowsum for the dK kernel), the second dS and
+// dQ^T += K^T dS^T.  The dprobs tile arrives as whole 128-byte row segments and is turned to the lane-owns-a-query layout
+// through the wave's staging area (the mirror image of the forward's store path); the next tile's loads fly under this tile.
+template <bool DROP>
+__global__ __launch_bounds__(256, 3) void attn_probs_bwd_dq_kernel(ProbsArgs pa) {
+    __shared__ __attribute__((aligned(16))) char smem[32 * 128 + STAGE_BYTES];            // K tile (32 keys); staging per wave
+    if (DROP) apply_salt(pa.a.salt, pa.a.seed0, pa.a.seed1);
+    const AttnArgs& a = pa.a;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, r31 = lane & 31;
+    int tile_x, hd, b;
+    attn_block(a, tile_x, hd, b);
+    const int q0 = tile_x * 128 + wave * 32, q = q0 + r31;
+    int len = a.lens[b];
+    len = len < 1 ? 1 : (len > a.Tp ? a.Tp : len);
+    const int nk = (len + 31) >> 5;
+    const long rowbase = (long)b * a.Tp, bh = (long)b * a.heads + hd;
+    const LaneOffs lo = lane_offs(lane);
+    const bf16_t* Qg = a.qkv + (rowbase + q) * a.ld + hd * HD;
+    const bf16_t* Kb = a.qkv + rowbase * a.ld + a.H + hd * HD;
+    bf16x8 qf[4];
+#pragma unroll
+    for (int ds = 0; ds < 4; ++ds) qf[ds] = *(const bf16x8*)(Qg + ds * 16 + h * 8);
+    const float nlse = -a.lse2[bh * a.Tp + q];
+    const float* dP0 = pa.dprobs + (bh * a.Tp + q0) * a.Tp;
+    char* sK = smem;
+    char* sw = smem + 32 * 128 + wave * (32 * OUT_PITCH);
+    const int srow = tid >> 3, sch = tid & 7;
+    const int soff = tile_off(srow, sch);
+    const long gk = (long)srow * a.ld + sch * 8;
+    int dsoff[4];
+    long dgoff[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int idx = i * 64 + lane, r = idx >> 3, ch = idx & 7;
+        dsoff[i] = r * OUT_PITCH + ch * 16;
+        dgoff[i] = (long)r * a.Tp + ch * 4;
+    }
+    uint32_t hbase = 0;
+    if (DROP) hbase = rng_hash((uint32_t)(bh * a.Tp + q), a.seed0, a.seed1) + (uint32_t)(2 * h) * ATTN_K1;
+    const float c = a.c;
+    f32x16 dQT[2];
+    dQT[0] = dQT[1] = (f32x16)(0.f);
+    float rs = 0.f;
+
+    auto walk = [&](auto second_flag) {
+        constexpr bool SECOND = decltype(second_flag)::value;
+        u32x4 kreg = *(const u32x4*)(Kb + gk);
+        f32x4 dreg[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) dreg[i] = *(const f32x4*)(dP0 + dgoff[i]);
+        float part = 0.f;
+        for (int t = 0; t < nk; ++t) {
+            __syncthreads();
+            *(u32x4*)(sK + soff) = kreg;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) *(f32x4*)(sw + dsoff[i]) = dreg[i];
+            __syncthreads();
+            if (t + 1 < nk) {
+                kreg = *(const u32x4*)(Kb + (long)(t + 1) * 32 * a.ld + gk);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) dreg[i] = *(const f32x4*)(dP0 + dgoff[i] + (t + 1) * 32);
+            }
+            f32x16 sT = __builtin_amdgcn_mfma_f32_32x32x16_bf16(rd_row(sK, lo, 0, 0), qf[0], (f32x16)(0.f), 0, 0, 0);
+#pragma unroll
+            for (int ds = 1; ds < 4; ++ds) sT = __builtin_amdgcn_mfma_f32_32x32x16_bf16(rd_row(sK, lo, 0, ds), qf[ds], sT, 0, 0, 0);
+            float dp[16];
+#pragma unroll
+            for (int g4 = 0; g4 < 4; ++g4) {
+                const f32x4 d4 = *(const f32x4*)(sw + r31 * OUT_PITCH + (8 * g4 + 4 * h) * 4);
+#pragma unroll
+                for (int rr = 0; rr < 4; ++rr) dp[4 * g4 + rr] = d4[rr];
+            }
+            if (DROP) {
+#pragma unroll
+                for (int r = 0; r < 16; r += 2) {
+                    const uint32_t hsh = attn_mix(hbase + (uint32_t)(t * 16 + acc_row(r, 0) / 2) * ATTN_K1);
+                    dp[r] = (hsh & 0xffffu) >= a.thr16 ? dp[r] : 0.f;
+                    dp[r + 1] = (hsh >> 16) >= a.thr16 ? dp[r + 1] : 0.f;
+                }
+            }
+            const bool boundary = t * 32 + 32 > len;
+            float dsv[16];
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const float p = fast_exp2(fmaf(sT[r], c, nlse));
+                const float v = SECOND ? p * (dp[r] - rs) : p * dp[r];
+                dsv[r] = (boundary && (t * 32 + acc_row(r, h) >= len)) ? 0.f : v;       // select: masked P may be inf, dprobs anything
+            }
+            if (SECOND) {
+#pragma unroll
+                for (int sstep = 0; sstep < 2; ++sstep) {
+                    const bf16x8 dsf = pack8(&dsv[8 * sstep]);
+#pragma unroll
+                    for (int dt = 0; dt < 2; ++dt)
+                        dQT[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(rd_tr(sK, lo, sstep, dt), dsf, dQT[dt], 0, 0, 0);
+                }
+            } else {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) part += dsv[r];
+            }
+        }
+        return part;
+    };
+    rs = walk(Flag<false>{});
+    rs += __shfl_xor(rs, 32, 64);
+    if (h == 0) pa.rowsum[bh * a.Tp + q] = rs;
+    walk(Flag<true>{});
+    __syncthreads();
+    store_rows_bf16_acc(sw, dQT, a.scale * a.dscale, a.dqkv + (rowbase + q0) * a.ld + hd * HD, a.ld, lane, pa.accumulate);
+}
+
+// dK kernel: grid (Tp/128, heads, B); wave w owns keys kt*128 + w*32 .. +31 (one per lane, S = Q K^T, its K fragment in registers)
+// and walks ALL 32-query tiles (padded query rows carry whatever gradient the caller put there, like the reference).  A lane's
+// dprobs values are one column: each load instruction reads two whole 128-byte row segments.
+template <bool DROP>
+__global__ __launch_bounds__(256, 3) void attn_probs_bwd_dk_kernel(ProbsArgs pa) {
+    __shared__ __attribute__((aligned(16))) char smem[STAGE_BYTES + 384];     // Q tile (32 queries) / epilogue staging; row statistics
+    char* sQ = smem;
+    float* sL = (float*)(smem + STAGE_BYTES);           // [0,32) lse2, [32,64) row sums, [64,96) dropout row hash of the tile's queries
+    if (DROP) apply_salt(pa.a.salt, pa.a.seed0, pa.a.seed1);
+    const AttnArgs& a = pa.a;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, r31 = lane & 31;
+    int tile_x, hd, b;
+    attn_block(a, tile_x, hd, b);
+    const int kb0 = tile_x * 128, key0 = kb0 + wave * 32, key = key0 + r31;
+    int len = a.lens[b];
+    len = len < 1 ? 1 : (len > a.Tp ? a.Tp : len);
+    const long rowbase = (long)b * a.Tp, bh = (long)b * a.heads + hd;
+    bf16_t* dK0 = a.dqkv + (rowbase + kb0) * a.ld + a.H + hd * HD;
+    if (kb0 >= len) {                       // whole block beyond the utterance: gradients are exactly zero
+        if (!pa.accumulate) {
+            const u32x4 z = {0u, 0u, 0u, 0u};
+#pragma unroll
+            for (int it = 0; it < 4; ++it) {
+                const int cid = it * 256 + tid, row = cid >> 3, ch = cid & 7;
+                *(u32x4*)(dK0 + (long)row * a.ld + ch * 8) = z;
+            }
+        }
+        return;
+    }
+    const LaneOffs lo = lane_offs(lane);
+    const bf16_t* Kg = a.qkv + (rowbase + key) * a.ld + a.H + hd * HD;
+    bf16x8 kf[4];
+#pragma unroll
+    for (int ds = 0; ds < 4; ++ds) kf[ds] = *(const bf16x8*)(Kg + ds * 16 + h * 8);
+    f32x16 dKT[2];
+    dKT[0] = dKT[1] = (f32x16)(0.f);
+    const int nq = a.Tp >> 5;
+    const bf16_t* Qb = a.qkv + rowbase * a.ld + hd * HD;
+    const float* lse = a.lse2 + bh * a.Tp;
+    const float* rsum = pa.rowsum + bh * a.Tp;
+    const int srow = tid >> 3, sch = tid & 7;
+    const int soff = tile_off(srow, sch);
+    const long gq = (long)srow * a.ld + sch * 8;
+    u32x4 qreg = *(const u32x4*)(Qb + gq);
+    const float* stat = (tid < 8 ? lse : rsum) + (tid & 7) * 4;    // threads 0..7 carry lse2, 8..15 the row sums (one float4 each)
+    f32x4 sreg = (f32x4)(0.f);
+    if (tid < 16) sreg = *(const f32x4*)stat;
+    const bool key_ok = key < len;
+    const uint32_t hshift = (key & 1) ? 16u : 0u;
+    const uint32_t pairk = (uint32_t)(key >> 1) * ATTN_K1;
+    const uint32_t rowid0 = (uint32_t)(bh * a.Tp) + (uint32_t)(tid & 31);
+    uint32_t hreg = 0;
+    if (DROP && tid >= 32 && tid < 64) hreg = rng_hash(rowid0, a.seed0, a.seed1);
+    const float c = a.c;
+    // register r of a tile <-> query t*32 + acc_row(r, h), this lane's key column
+    // (wave-uniform row pointer + one 32-bit lane offset: the 16 addresses of a tile cost no vector registers)
+    const float* dPk = pa.dprobs + bh * a.Tp * a.Tp;
+    const long tp = a.Tp;
+    const uint32_t loff = (uint32_t)(4 * h * a.Tp + key);
+    float dreg[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) dreg[r] = (dPk + acc_row(r, 0) * tp)[loff];
+#pragma unroll 1
+    for (int t = 0; t < nq; ++t) {
+        __syncthreads();
+        *(u32x4*)(sQ + soff) = qreg;
+        if (tid < 16) *(f32x4*)(sL + tid * 4) = sreg;
+        if (DROP && tid >= 32 && tid < 64) ((uint32_t*)sL)[64 + (tid & 31)] = hreg;
+        __syncthreads();
+        if (t + 1 < nq) {
+            qreg = *(const u32x4*)(Qb + (long)(t + 1) * 32 * a.ld + gq);
+            if (tid < 16) sreg = *(const f32x4*)(stat + (t + 1) * 32);
+            if (DROP && tid >= 32 && tid < 64) hreg = rng_hash(rowid0 + (uint32_t)((t + 1) * 32), a.seed0, a.seed1);
+        }
+        f32x16 s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(rd_row(sQ, lo, 0, 0), kf[0], (f32x16)(0.f), 0, 0, 0);
+#pragma unroll
+        for (int ds = 1; ds < 4; ++ds) s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(rd_row(sQ, lo, 0, ds), kf[ds], s, 0, 0, 0);
+        float dsv[16];
+#pragma unroll
+        for (int g4 = 0; g4 < 4; ++g4) {
+            const f32x4 l4 = *(const f32x4*)(sL + 8 * g4 + 4 * h);
+            const f32x4 r4 = *(const f32x4*)(sL + 32 + 8 * g4 + 4 * h);
+            u32x4 rh = {0u, 0u, 0u, 0u};
+            if (DROP) rh = *(const u32x4*)((const uint32_t*)sL + 64 + 8 * g4 + 4 * h);
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr) {
+                const int r = 4 * g4 + rr;
+                const float p = fast_exp2(fmaf(s[r], c, -l4[rr]));
+                float d = dreg[r];
+                if (DROP) {
+                    const uint32_t y = attn_mix(rh[rr] + pairk);
+                    d = ((y >> hshift) & 0xffffu) >= a.thr16 ? d : 0.f;
+                }
+                dsv[r] = key_ok ? p * (d - r4[rr]) : 0.f;       // select: masked P may be inf, dprobs anything
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);                     // dreg is consumed: only now may its registers take the next tile
+        if (t + 1 < nq) {                                      // the next tile's column values fly under the dK products and the staging
+            const float* dn = dPk + (long)(t + 1) * 32 * tp;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) dreg[r] = (dn + acc_row(r, 0) * tp)[loff];
+        }
+#pragma unroll
+        for (int sstep = 0; sstep < 2; ++sstep) {
+            const bf16x8 df = pack8(&dsv[8 * sstep]);
+#pragma unroll
+            for (int dt = 0; dt < 2; ++dt)
+                dKT[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(rd_tr(sQ, lo, sstep, dt), df, dKT[dt], 0, 0, 0);
+        }
+    }
+    __syncthreads();                                           // the Q tile becomes the epilogue staging area
+    // dK = scale * dS^T Q; with a pre-scaled Q the staged rows are Q' = scale * log2(e) * Q, so the factor left over is ln 2
+    store_rows_bf16_acc(smem + wave * (32 * OUT_PITCH), dKT, (a.q_prescaled ? 0.6931471805599453f : a.scale) * a.dscale,
+                        dK0 + (long)(wave * 32) * a.ld, a.ld, lane, pa.accumulate);
+}
+
 int fill_args(AttnArgs& a, const char* who, const void* qkv, const int32_t* lens, int64_t B, int64_t Tp, int64_t H,
               int64_t heads, float scale, float dropout_p, uint64_t seed, int q_prescaled, const void* stream) {
     APTAI_REQUIRE(qkv && lens, "%s: null pointer", who);
@@ -1018,6 +1404,54 @@ extern "C" int aptai_attention_bwd(const void* qkv, const int32_t* lens, const v
         APTAI_LAUNCH(attn_bwd_dkdv_kernel<false>, grid, dim3(256), 0, stream, a);
     }
     APTAI_CHECK_LAUNCH("attn_bwd_dkdv_kernel");
+    return APTAI_OK;
+}
+
+extern "C" int aptai_attention_probs_fwd(const void* qkv, const int32_t* lens, const float* lse2, float* probs, int64_t B, int64_t Tp,
+                                         int64_t H, int64_t heads, float scale, float dropout_p, uint64_t seed, int q_prescaled,
+                                         void* stream_) {
+    ProbsArgs pa;
+    memset(&pa, 0, sizeof(pa));
+    int rc = fill_args(pa.a, "aptai_attention_probs_fwd", qkv, lens, B, Tp, H, heads, scale, dropout_p, seed, q_prescaled, stream_);
+    if (rc) return rc;
+    APTAI_REQUIRE(lse2 && probs, "aptai_attention_probs_fwd: null pointer");
+    APTAI_REQUIRE((uintptr_t)probs % 16 == 0, "aptai_attention_probs_fwd: probs must be 16-byte aligned");
+    APTAI_REQUIRE(B * heads * Tp < (1L << 31), "aptai_attention_probs_fwd: B * heads * Tp (%ld) exceeds the 32-bit dropout row index",
+                  (long)(B * heads * Tp));
+    pa.a.lse2 = (float*)lse2; pa.probs = probs;
+    const dim3 grid((unsigned)(Tp / 128), (unsigned)heads, (unsigned)B);
+    if (pa.a.thr16) {
+        APTAI_LAUNCH(attn_probs_fwd_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream_, pa);
+    } else {
+        APTAI_LAUNCH(attn_probs_fwd_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream_, pa);
+    }
+    APTAI_CHECK_LAUNCH("attn_probs_fwd_kernel");
+    return APTAI_OK;
+}
+
+extern "C" int aptai_attention_probs_bwd(const void* qkv, const int32_t* lens, const float* lse2, const float* dprobs, float* rowsum_ws,
+                                         void* dqkv, int64_t B, int64_t Tp, int64_t H, int64_t heads, float scale, float dropout_p,
+                                         uint64_t seed, int q_prescaled, int accumulate, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    ProbsArgs pa;
+    memset(&pa, 0, sizeof(pa));
+    int rc = fill_args(pa.a, "aptai_attention_probs_bwd", qkv, lens, B, Tp, H, heads, scale, dropout_p, seed, q_prescaled, stream_);
+    if (rc) return rc;
+    APTAI_REQUIRE(lse2 && dprobs && rowsum_ws && dqkv, "aptai_attention_probs_bwd: null pointer");
+    APTAI_REQUIRE((uintptr_t)dprobs % 16 == 0, "aptai_attention_probs_bwd: dprobs must be 16-byte aligned");
+    pa.a.lse2 = (float*)lse2; pa.a.dqkv = (bf16_t*)dqkv; pa.dprobs = dprobs; pa.rowsum = rowsum_ws; pa.accumulate = accumulate;
+    const dim3 grid((unsigned)(Tp / 128), (unsigned)heads, (unsigned)B);
+    // dQ first: it leaves the row sums in rowsum_ws for the dK kernel
+    if (pa.a.thr16) {
+        APTAI_LAUNCH(attn_probs_bwd_dq_kernel<true>, grid, dim3(256), 0, stream, pa);
+        APTAI_CHECK_LAUNCH("attn_probs_bwd_dq_kernel");
+        APTAI_LAUNCH(attn_probs_bwd_dk_kernel<true>, grid, dim3(256), 0, stream, pa);
+    } else {
+        APTAI_LAUNCH(attn_probs_bwd_dq_kernel<false>, grid, dim3(256), 0, stream, pa);
+        APTAI_CHECK_LAUNCH("attn_probs_bwd_dq_kernel");
+        APTAI_LAUNCH(attn_probs_bwd_dk_kernel<false>, grid, dim3(256), 0, stream, pa);
+    }
+    APTAI_CHECK_LAUNCH("attn_probs_bwd_dk_kernel");
     return APTAI_OK;
 }
 

@@ -512,6 +512,32 @@ def attention_bwd(qkv, lens_i32, ctx, dctx, stats, B, Tp, H, heads, *, dropout_p
     return dqkv
 
 
+def attention_probs_fwd(qkv, lens_i32, lse2, B, Tp, H, heads, *, dropout_p=0.0, seed=0, q_prescaled=False):
+    """The attention map of one layer, fp32 [B][heads][Tp][Tp] (aptai_attention_probs_fwd): softmax after dropout, from the ``lse2`` that
+    attention_fwd saved for the same qkv / seed / q_prescaled.  Callers view [:, :, :T, :T]."""
+    _dev(qkv, lens_i32, lse2)
+    probs = torch.empty((B, heads, Tp, Tp), device=qkv.device, dtype=torch.float32)
+    _lib.call("aptai_attention_probs_fwd", qkv.data_ptr(), lens_i32.data_ptr(), lse2.data_ptr(), probs.data_ptr(), B, Tp, H, heads,
+              (H // heads) ** -0.5, dropout_p, seed, int(q_prescaled), _stream())
+    return probs
+
+
+def attention_probs_bwd(qkv, lens_i32, lse2, dprobs, B, Tp, H, heads, *, dropout_p=0.0, seed=0, q_prescaled=False, dqkv=None):
+    """Gradient of a loss on the map (aptai_attention_probs_bwd).  ``dprobs`` fp32 [B][heads][Tp][Tp] contiguous.  With ``dqkv`` (what
+    attention_bwd returned for the same layer) dQ and dK are ADDED to its Q and K thirds in place; without, a new tensor with a zero V
+    third is returned."""
+    _dev(qkv, lens_i32, lse2, dprobs)
+    if dprobs.dtype != torch.float32 or tuple(dprobs.shape) != (B, heads, Tp, Tp) or not dprobs.is_contiguous():
+        raise _lib.AptaiHipError("attention_probs_bwd: dprobs must be contiguous fp32 [B][heads][Tp][Tp]")
+    accumulate = dqkv is not None
+    if dqkv is None:
+        dqkv = torch.zeros_like(qkv)
+    rowsum = torch.empty((B, heads, Tp), device=qkv.device, dtype=torch.float32)
+    _lib.call("aptai_attention_probs_bwd", qkv.data_ptr(), lens_i32.data_ptr(), lse2.data_ptr(), dprobs.data_ptr(), rowsum.data_ptr(),
+              dqkv.data_ptr(), B, Tp, H, heads, (H // heads) ** -0.5, dropout_p, seed, int(q_prescaled), int(accumulate), _stream())
+    return dqkv
+
+
 # ----------------------------------------------------------------------------- parameter prep
 def cast_bf16(src: torch.Tensor, dst: Optional[torch.Tensor] = None, ld_dst: Optional[int] = None) -> torch.Tensor:
     """fp32 [rows][cols] -> bf16 (optionally into a row slice of a wider buffer)."""

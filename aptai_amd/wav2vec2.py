@@ -79,6 +79,8 @@ class _OpFn(torch.autograd.Function):
     def forward(ctx, impl, need, x, *params):
         outs, saved = impl.fwd(x, params, need)          # grad mode is off in here: `need` is decided by the caller
         ctx.impl, ctx.saved = impl, saved
+        if len(outs) > 1 and getattr(impl, "want_attn", False):
+            ctx.set_materialize_grads(False)             # a map no loss touches arrives as None, not as 200 MB of zeros
         return outs if len(outs) > 1 else outs[0]
 
     @staticmethod
@@ -130,6 +132,8 @@ class _LayerImpl:
 
     def __init__(self, cfg: W2V2Config, geom, lens_i32, w, training: bool, seed: int):
         self.cfg, self.g, self.lens, self.w, self.training, self.seed = cfg, geom, lens_i32, w, training, seed
+        self.want_attn = False      # output_attentions: fwd returns the layer's attention map as a second output
+        self.attn_state = None      # shared by the layers of one forward call: .seen = a layer above got a gradient on its map
 
     # params: ln1.w ln1.b ln2.w ln2.b, then the 12 fp32 linear parameters (q,k,v weights; q,k,v biases; out w,b;
     # ffn1 w,b; ffn2 w,b).  The forward reads their cached bf16 copies in `w`; the backward returns their gradients.
@@ -156,7 +160,11 @@ class _LayerImpl:
         # their exp2 arguments directly (q_prescaled)
         s.qkv = ops.gemm(attn_in, w.wqkv, M, 3 * H, H, bias=w.bqkv, colscale=(H, ops.attention_qscale(H, cfg.num_attention_heads)))
         s.ctx, s.lse = ops.attention_fwd(s.qkv, self.lens, g.B, g.Tp, H, cfg.num_attention_heads, q_prescaled=True, dropout_p=p_att,
-                                         seed=_seed(self.seed, 1), save_lse=need)
+                                         seed=_seed(self.seed, 1), save_lse=need or self.want_attn)
+        probs = None
+        if self.want_attn:          # HF eager attention's second result: the softmax after dropout, with the fused kernel's own mask
+            probs = ops.attention_probs_fwd(s.qkv, self.lens, s.lse[0], g.B, g.Tp, H, cfg.num_attention_heads, q_prescaled=True,
+                                            dropout_p=p_att, seed=_seed(self.seed, 1))
         s.s1 = ops.gemm(s.ctx, w.wo, M, H, H, bias=w.bo, residual=x, dropout_p=p_h, seed=_seed(self.seed, 2))
         if pre:
             ffn_in, s.m2, s.r2 = ops.layernorm_fwd(s.s1, ln2w, ln2b, cfg.layer_norm_eps, save_stats=need)
@@ -176,12 +184,13 @@ class _LayerImpl:
             y, s.m2, s.r2 = ops.layernorm_fwd(s.s2, ln2w, ln2b, cfg.layer_norm_eps, save_stats=need)
         s.p = (p_h, p_a, p_att)
         s.ln = (ln1w, ln1b, ln2w, ln2b)
-        return (y,), (s if need else None)
+        return ((y,) if probs is None else (y, probs)), (s if need else None)
 
     def fwd_f32res(self, x, x32, params):
         """Inference only, opt-in (set_encoder_precision("bf16_f32res")): the residual stream stays in fp32 - out-proj and FFN2
         write fp32 and add the fp32 residual in their epilogues, LayerNorm reads fp32 and hands the next GEMM a bf16 copy and the
-        next residual add an fp32 one.  GEMM operands and attention stay bf16.  Returns (y_bf16 | None, y_f32)."""
+        next residual add an fp32 one.  GEMM operands and attention stay bf16.  Returns (y_bf16 | None, y_f32); with want_attn the layer's
+        attention map is left in self.probs."""
         cfg, g, w = self.cfg, self.g, self.w
         M, H, I = g.M, cfg.hidden_size, cfg.intermediate_size
         ln1w, ln1b, ln2w, ln2b = params[:4]
@@ -190,13 +199,17 @@ class _LayerImpl:
         if cfg.do_stable_layer_norm:                       # pre-LN (large): x32 is the un-normalised stream
             n1, _ = ops.layernorm_fwd_f32in(x32, ln1w, ln1b, cfg.layer_norm_eps, want_f32=False)
             qkv = ops.gemm(n1, w.wqkv, M, 3 * H, H, bias=w.bqkv, colscale=qs)
-            ctx, _ = ops.attention_fwd(qkv, self.lens, g.B, g.Tp, H, heads, save_lse=False, q_prescaled=True)
+            ctx, st = ops.attention_fwd(qkv, self.lens, g.B, g.Tp, H, heads, save_lse=self.want_attn, q_prescaled=True)
+            if self.want_attn:
+                self.probs = ops.attention_probs_fwd(qkv, self.lens, st[0], g.B, g.Tp, H, heads, q_prescaled=True)
             s1 = ops.gemm(ctx, w.wo, M, H, H, bias=w.bo, out_f32=True, residual_f32=x32, tile=128)
             n2, _ = ops.layernorm_fwd_f32in(s1, ln2w, ln2b, cfg.layer_norm_eps, want_f32=False)
             u = ops.gemm(n2, w.w1, M, I, H, bias=w.b1, gelu=True)
             return None, ops.gemm(u, w.w2, M, H, I, bias=w.b2, out_f32=True, residual_f32=s1, tile=128)
         qkv = ops.gemm(x, w.wqkv, M, 3 * H, H, bias=w.bqkv, colscale=qs)
-        ctx, _ = ops.attention_fwd(qkv, self.lens, g.B, g.Tp, H, heads, save_lse=False, q_prescaled=True)
+        ctx, st = ops.attention_fwd(qkv, self.lens, g.B, g.Tp, H, heads, save_lse=self.want_attn, q_prescaled=True)
+        if self.want_attn:
+            self.probs = ops.attention_probs_fwd(qkv, self.lens, st[0], g.B, g.Tp, H, heads, q_prescaled=True)
         s1 = ops.gemm(ctx, w.wo, M, H, H, bias=w.bo, out_f32=True, residual_f32=x32, tile=128)
         n1, n1_32 = ops.layernorm_fwd_f32in(s1, ln1w, ln1b, cfg.layer_norm_eps)
         u = ops.gemm(n1, w.w1, M, I, H, bias=w.b1, gelu=True)
@@ -239,7 +252,9 @@ class _LayerImpl:
         heads = cfg.num_attention_heads
         p_h, p_a, p_att = s.p
         ln1w, ln1b, ln2w, ln2b = s.ln
-        dy = grads[0].contiguous()
+        dprobs = grads[1] if len(grads) > 1 else None          # gradient of a loss on the attention map (output_attentions)
+        # (a loss that reaches this layer through its map alone leaves the hidden state's gradient undefined: zero)
+        dy = grads[0].contiguous() if grads[0] is not None else torch.zeros_like(s.x)
         pre = cfg.do_stable_layer_norm
         sk = w.split_k
         main = torch.cuda.current_stream()
@@ -286,8 +301,17 @@ class _LayerImpl:
             dwo, dbo = on_side(lambda: (ops.gemm(d_att_out, s.ctx, H, H, M, a_kmajor=True, b_kmajor=True, out_f32=True, split_k=sk[1]),
                                         ops.colsum(d_att_out, M, H)))
         dctx = ops.gemm(d_att_out, w.wo, M, H, H, b_kmajor=True)
+        # no loss term of the models touches padded frames, so their context gradient is exactly zero and the kernel skips them - unless
+        # a layer above had a gradient on its map: the maps' padded QUERY rows are part of the returned tensor (as in the reference), and
+        # what a loss puts on them reaches the padded frames of every layer below
+        st = self.attn_state
         dqkv = ops.attention_bwd(s.qkv, self.lens, s.ctx, dctx, s.lse, g.B, g.Tp, H, heads, q_prescaled=True, dropout_p=p_att,
-                                 seed=_seed(self.seed, 1), dctx_zero_beyond_len=True)
+                                 seed=_seed(self.seed, 1), dctx_zero_beyond_len=st is None or not st.seen)
+        if dprobs is not None:      # dQ and dK of the map's gradient, summed into what the fused backward wrote
+            ops.attention_probs_bwd(s.qkv, self.lens, s.lse[0], dprobs.contiguous(), g.B, g.Tp, H, heads, q_prescaled=True,
+                                    dropout_p=p_att, seed=_seed(self.seed, 1), dqkv=dqkv)
+            if st is not None:
+                st.seen = True
         attn_in = s.n1 if pre else s.x
         if not grouped:
             dwqkv, dbqkv = on_side(lambda: (ops.gemm(dqkv, attn_in, 3 * H, H, M, a_kmajor=True, b_kmajor=True, out_f32=True, split_k=sk[0]),
@@ -1064,8 +1088,10 @@ class Wav2Vec2Model(nn.Module):
         cfg = self.config
         if not input_values.is_cuda:
             raise ops._lib.AptaiHipError("Wav2Vec2Model runs on the MI355X only (no CPU fallback)")
-        if output_attentions:
-            raise NotImplementedError("attention probabilities never leave the fused kernel")
+        want_attn = bool(output_attentions)
+        if want_attn and getattr(self, "_encoder_precision", "bf16") not in ("bf16", "bf16_f32res"):
+            raise NotImplementedError(f"output_attentions is not available with encoder precision {self._encoder_precision!r}: "
+                                      "the attention maps come from the bf16 attention kernels ('bf16', 'bf16_f32res')")
         audio = input_values.float().contiguous()
         B, S = audio.shape
         g = self._geometry(B, S)
@@ -1125,6 +1151,8 @@ class Wav2Vec2Model(nn.Module):
         # ---- transformer layers with LayerDrop (HF:694-707 / 767-780)
         self._refresh_layer_copies()
         hidden = []
+        attn = []                    # output_attentions: one [B, heads, T, T] fp32 map per layer (None where LayerDrop skipped it)
+        attn_state = SimpleNamespace(seen=False) if want_attn else None
         if getattr(self, "_encoder_precision", "bf16") == "bf16_f32res" and not training and not torch.is_grad_enabled():
             # fp32 residual stream (inference only, see set_encoder_precision)
             h32 = h.float()
@@ -1132,25 +1160,36 @@ class Wav2Vec2Model(nn.Module):
                 hidden.append(h if h is not None else h32)
                 wt, _lin = self._layer_weights(i, g.M)
                 impl = _LayerImpl(cfg, g, lens_i32, wt, False, 0)
+                impl.want_attn = want_attn
                 h, h32 = impl.fwd_f32res(h, h32, [layer.layer_norm.weight, layer.layer_norm.bias, layer.final_layer_norm.weight,
                                                    layer.final_layer_norm.bias])
+                if want_attn:
+                    attn.append(impl.probs[:, :, :g.T, :g.T])
             if cfg.do_stable_layer_norm:
                 h, h32 = ops.layernorm_fwd_f32in(h32, self.encoder.layer_norm.weight, self.encoder.layer_norm.bias, cfg.layer_norm_eps)
             hidden.append(h)
             out = Wav2Vec2BaseModelOutput(last_hidden_state=h.view(B, g.Tp, -1)[:, :g.T], extract_features=None,
                                           hidden_states=tuple(t.view(B, g.Tp, -1)[:, :g.T] for t in hidden) if output_hidden_states else None,
-                                          attentions=None)
+                                          attentions=tuple(attn) if want_attn else None)
             out._geom, out._frame_lens, out._flat_last, out._flat_last_f32 = g, frame_lens, h, h32
             return out
         for i, layer in enumerate(self.encoder.layers):
             hidden.append(h)
             skip = training and cfg.layerdrop > 0 and (float(torch.rand([], generator=self._layerdrop_gen)) < cfg.layerdrop)
             if skip:
+                if want_attn:
+                    attn.append(None)
                 continue
             w, lin_params = self._layer_weights(i, g.M)
             impl = _LayerImpl(cfg, g, lens_i32, w, training, _seed(seed, 100 + i))
             if getattr(self, "_encoder_precision", "bf16") == "mxfp8" and not training:
                 impl.mx = self._mx_layer_weights(i)
+            if want_attn:
+                impl.want_attn, impl.attn_state = True, attn_state
+                h, probs = _run(impl, h, layer.layer_norm.weight, layer.layer_norm.bias, layer.final_layer_norm.weight,
+                                layer.final_layer_norm.bias, *lin_params)
+                attn.append(probs[:, :, :g.T, :g.T])
+                continue
             h = _run(impl, h, layer.layer_norm.weight, layer.layer_norm.bias, layer.final_layer_norm.weight,
                             layer.final_layer_norm.bias, *lin_params)
         if cfg.do_stable_layer_norm:
@@ -1164,7 +1203,7 @@ class Wav2Vec2Model(nn.Module):
             last_hidden_state=view(h),
             extract_features=None,
             hidden_states=tuple(view(t) for t in hidden) if output_hidden_states else None,
-            attentions=None)
+            attentions=tuple(attn) if want_attn else None)
         out._geom = g
         out._frame_lens = frame_lens
         out._flat_last = h

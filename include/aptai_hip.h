@@ -210,6 +210,24 @@ int aptai_attention_bwd(const void* qkv, const int32_t* lens, const void* ctx, c
                         const float* lse2, float* delta_ws, void* dqkv, int64_t B, int64_t Tp, int64_t H, int64_t heads, float scale,
                         float dropout_p, uint64_t seed, int dctx_zero_beyond_len, int q_prescaled, void* stream);
 
+/* The attention probabilities the fused forward never writes (HF eager_attention_forward's second result, output_attentions=True),
+ * rebuilt from what it saved.  qkv, lens, scale, dropout_p, seed, q_prescaled exactly as given to aptai_attention_fwd, lse2 as that call
+ * wrote it.  probs fp32 [B][heads][Tp][Tp] (row pitch Tp, 16-byte aligned; callers view [:, :, :T, :T]): the softmax AFTER dropout,
+ * keep * P / (1 - p) with the keep mask the fused kernels used (plain softmax when dropout_p == 0); key columns >= lens[b] are exactly
+ * 0, query rows >= lens[b] are computed like all others.  One QK^T product and one streaming write, no row reduction. */
+int aptai_attention_probs_fwd(const void* qkv, const int32_t* lens, const float* lse2, float* probs, int64_t B, int64_t Tp, int64_t H,
+                              int64_t heads, float scale, float dropout_p, uint64_t seed, int q_prescaled, void* stream);
+/* Its backward.  dprobs fp32, layout of probs: gradient of the loss with respect to the RETURNED tensor (all Tp query rows are read;
+ * key columns >= lens[b] are ignored).  dS = P (dP - rowsum(dP P)) with dP = keep * dprobs / (1 - p); dQ = scale dS K and
+ * dK = scale dS^T Q go to the Q and K thirds of dqkv [B*Tp][3H] bf16, the V third is not touched.  accumulate != 0 adds them to what
+ * the thirds hold (what aptai_attention_bwd wrote for the same layer: sum in fp32, one rounding; every element is owned by one lane,
+ * so same inputs give the same bits), accumulate == 0 overwrites them; gradients of keys >= lens[b] are exactly zero either way.
+ * q_prescaled != 0: the Q third of dqkv is the gradient with respect to the UNSCALED projection output, as for aptai_attention_bwd.
+ * rowsum_ws: fp32 [B][heads][Tp] scratch. */
+int aptai_attention_probs_bwd(const void* qkv, const int32_t* lens, const float* lse2, const float* dprobs, float* rowsum_ws, void* dqkv,
+                              int64_t B, int64_t Tp, int64_t H, int64_t heads, float scale, float dropout_p, uint64_t seed,
+                              int q_prescaled, int accumulate, void* stream);
+
 /* ------------------------------------------------------------------------------------------------ parameter prep
  * fp32 master parameters -> bf16 compute copies (and the layouts the kernels want). */
 int aptai_cast_f32_to_bf16(const float* src, void* dst, int64_t rows, int64_t cols, int64_t ld_dst, void* stream);
