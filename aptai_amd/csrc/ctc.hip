@@ -409,3 +409,297 @@ extern "C" int aptai_ctc_greedy_decode(const float* logits, int64_t ldl, int64_t
     APTAI_CHECK_LAUNCH("ctc_greedy_decode_kernel");
     return APTAI_OK;
 }
+
+// ================================================================================================ forced alignment (Viterbi)
+// aptai_ctc_viterbi: the best path of a KNOWN transcript through the lattice the recursions above sum over (topology 0), or
+// through the blank-free monotonic lattice l1 .. lL (topology 1: the read-out of a forward-sum trained attention).  Three launches:
+//   1. vit_gather_kernel (parallel, one wave per frame): xe[b][t][s] = RAW logit of extended state s, lz[b][t] = the frame's
+//      log-normaliser.  The path does not depend on lz (the same constant for every state of a frame), so the recursion runs on
+//      raw logits: ONE fp32 addition per state and frame, max is exact -> the path is reproducible bit for bit on the host
+//      (hostlogic.ctc_forced_align).  lz only enters score / token_score.
+//   2. vit_recur_kernel (one wave per utterance): max-plus recursion with the register-resident states, lane shuffles and
+//      four-deep row prefetch of ctc_recur_kernel; two-bit backpointers (0 stay, 1 from s-1, 2 from s-2), one word per lane and
+//      frame.  The backtrace is a chain of T dependent reads, so it walks LDS: utterances of at most VIT_LDS_BYTES / row bytes
+//      frames keep their backpointers in LDS from the start; longer ones write them to the workspace and the backtrace stages
+//      them back chunk by chunk with wide coalesced loads - the dependent chain never touches global memory either way.
+//   3. vit_spans_kernel (parallel, one workgroup per utterance): spans, score and token_score from frame_token, fixed order.
+// Tie rule (include/aptai_hip.h): stay is the incumbent; s-1 replaces it only if strictly greater; then s-2 likewise; the path
+// ends in the last state unless the one before it is strictly greater.  No atomics; same inputs -> same bits.
+namespace {
+
+constexpr int VIT_LDS_BYTES = 65536;
+
+struct VitArgs {
+    const float* logits; long ldl; long rows_per_b;
+    const int* targets; long ldt;
+    const int* input_lens; const int* target_lens; const int* vocab_sizes;
+    int B, T, V, blank, S_max, topology;
+};
+
+__device__ __forceinline__ void vit_sizes(const VitArgs& a, int b, int& Tb, int& L, int& S) {
+    Tb = a.input_lens[b];
+    Tb = Tb < 0 ? 0 : (Tb < a.T ? Tb : a.T);
+    L = a.target_lens[b];
+    L = L < 0 ? 0 : (L < (int)a.ldt ? L : (int)a.ldt);
+    S = a.topology == 0 ? 2 * L + 1 : L;
+}
+
+// ---- 1. raw logit per extended state + log-normaliser per frame.  grid = ceil(B*T/4) blocks of 4 waves, one frame per wave.
+__global__ __launch_bounds__(256) void vit_gather_kernel(VitArgs a, float* __restrict__ xe, float* __restrict__ lz) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long f = (long)blockIdx.x * 4 + wave;
+    if (f >= (long)a.B * a.T) return;
+    const int b = (int)(f / a.T), t = (int)(f % a.T);
+    int Tb, L, S;
+    vit_sizes(a, b, Tb, L, S);
+    if (t >= Tb) return;                                          // the recursion never reads frames beyond the utterance
+    int Vb = a.vocab_sizes ? a.vocab_sizes[b] : a.V;
+    Vb = Vb < 0 ? 0 : (Vb < a.V ? Vb : a.V);
+    const float* row = a.logits + ((long)b * a.rows_per_b + t) * a.ldl;
+    float x[MAXV / 64];
+    float mx = NEG_INF;
+#pragma unroll
+    for (int j = 0; j < MAXV / 64; ++j) {
+        const int v = j * 64 + lane;
+        x[j] = v < Vb ? row[v] : NEG_INF;
+        mx = fmaxf(mx, x[j]);
+    }
+    mx = wave_max(mx);
+    float se = 0.f;
+#pragma unroll
+    for (int j = 0; j < MAXV / 64; ++j) se += (j * 64 + lane < Vb) ? expf(x[j] - mx) : 0.f;
+    se = wave_sum(se);
+    if (lane == 0) lz[f] = mx + logf(se);
+    float* out = xe + f * a.S_max;
+    for (int s = lane; s < a.S_max; s += 64) {
+        float l = NEG_INF;
+        if (s < S) {
+            const int e = a.topology == 0 ? ((s & 1) ? a.targets[(long)b * a.ldt + (s >> 1)] : a.blank) : a.targets[(long)b * a.ldt + s];
+            if (e >= 0 && e < Vb) l = row[e];                    // a label outside the utterance's vocabulary has no path
+        }
+        out[s] = l;
+    }
+}
+
+// ---- 2. max-plus recursion + backtrace.  grid B, one wave each; NS states per lane, one backpointer word per lane and frame.
+template <int NS> struct VitWord { typedef uint8_t type; };
+template <> struct VitWord<8> { typedef uint16_t type; };
+
+template <int NS, int TOPO>
+__global__ __launch_bounds__(64) void vit_recur_kernel(VitArgs a, const float* __restrict__ xe, void* __restrict__ bp_ws_,
+                                                       int* __restrict__ frame_token) {
+    typedef typename VitWord<NS>::type word_t;
+    constexpr int CH = VIT_LDS_BYTES / (64 * (int)sizeof(word_t));    // frames per LDS chunk: 1024 (NS <= 4) or 512 (NS = 8)
+    constexpr int SH = NS == 2 ? 1 : (NS == 4 ? 2 : 3);
+    __shared__ __attribute__((aligned(16))) word_t bpl[CH * 64];
+    const int b = blockIdx.x, lane = threadIdx.x;
+    int Tb, L, S;
+    vit_sizes(a, b, Tb, L, S);
+    int* ft = frame_token + (long)b * a.T;
+    const bool in_lds = Tb <= CH;                                 // wave-uniform
+    word_t* bp_ws = (word_t*)bp_ws_ + (long)b * a.T * 64;
+    bool skip[NS];
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+        const int s = lane * NS + i;
+        bool sk = false;
+        if (TOPO == 0 && s < S && (s & 1) && s >= 3)
+            sk = a.targets[(long)b * a.ldt + (s >> 1)] != a.targets[(long)b * a.ldt + (s >> 1) - 1];
+        skip[i] = sk;
+    }
+    const long base = (long)b * a.T;
+    float st[NS];
+#pragma unroll
+    for (int i = 0; i < NS; ++i) st[i] = NEG_INF;
+    float r0[NS], r1[NS], r2[NS], r3[NS];                         // four-deep prefetch ring, static names (see ctc_recur_kernel)
+    auto fetch = [&](int step, float (&dst)[NS]) {
+        if (step < Tb) load_row<NS>(xe, base + step, a.S_max, lane, dst);
+    };
+    fetch(0, r0); fetch(1, r1); fetch(2, r2); fetch(3, r3);
+    auto advance = [&](int step, const float (&x)[NS]) {
+        float nw[NS];
+        unsigned word = 0;
+        if (step == 0) {
+#pragma unroll
+            for (int i = 0; i < NS; ++i) {
+                const int s = lane * NS + i;
+                const bool init = TOPO == 0 ? (s < 2) : (s == 0);
+                nw[i] = (init && s < S) ? x[i] : NEG_INF;
+            }
+        } else {
+            float p1 = __shfl_up(st[NS - 1], 1, 64), p2 = __shfl_up(st[NS - 2], 1, 64);
+            if (lane == 0) { p1 = NEG_INF; p2 = NEG_INF; }
+#pragma unroll
+            for (int i = 0; i < NS; ++i) {
+                const int s = lane * NS + i;
+                const float a1 = i >= 1 ? st[i >= 1 ? i - 1 : 0] : p1;
+                const float a2 = i >= 2 ? st[i >= 2 ? i - 2 : 0] : (i == 1 ? p1 : p2);
+                float best = st[i];
+                unsigned c = 0;
+                if (a1 > best) { best = a1; c = 1; }
+                if (TOPO == 0 && skip[i] && a2 > best) { best = a2; c = 2; }
+                nw[i] = s < S ? best + x[i] : NEG_INF;           // the ONE fp32 addition per state and frame
+                word |= c << (2 * i);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < NS; ++i) st[i] = nw[i];
+        if (in_lds) bpl[step * 64 + lane] = (word_t)word;
+        else bp_ws[(long)step * 64 + lane] = (word_t)word;
+    };
+    for (int step = 0; step < Tb; step += 4) {
+        advance(step, r0);
+        fetch(step + 4, r0);
+        if (step + 1 < Tb) { advance(step + 1, r1); fetch(step + 5, r1); }
+        if (step + 2 < Tb) { advance(step + 2, r2); fetch(step + 6, r2); }
+        if (step + 3 < Tb) { advance(step + 3, r3); fetch(step + 7, r3); }
+    }
+    // final state: the last one unless the one before it is strictly greater
+    float vlast = NEG_INF, vprev = NEG_INF;
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+        const int s = lane * NS + i;
+        if (s == S - 1) vlast = st[i];
+        if (TOPO == 0 && s == S - 2) vprev = st[i];
+    }
+    vlast = wave_max(vlast);                                      // one lane holds the value, the others -inf: exact
+    vprev = wave_max(vprev);
+    int s = S - 1;
+    float best = vlast;
+    if (vprev > vlast) { s = S - 2; best = vprev; }
+    const bool feasible = Tb > 0 && S > 0 && best > NEG_INF;
+    for (int t = (feasible ? Tb : 0) + lane; t < a.T; t += 64) ft[t] = -2;
+    if (!feasible) return;                                        // wave-uniform
+    if (!in_lds) __threadfence();                                 // this wave's backpointer stores before its own loads below
+    __syncthreads();
+    int mine = -2;
+    for (int c0 = ((Tb - 1) / CH) * CH; c0 >= 0; c0 -= CH) {
+        const int c1 = Tb < c0 + CH ? Tb : c0 + CH;
+        if (!in_lds) {
+            const uint4* src = (const uint4*)(bp_ws + (long)c0 * 64);
+            uint4* dst = (uint4*)bpl;
+            const int n16 = (c1 - c0) * 64 * (int)sizeof(word_t) / 16;
+            for (int i = lane; i < n16; i += 64) dst[i] = src[i];
+            __syncthreads();
+        }
+        for (int t = c1 - 1; t >= c0; --t) {
+            const int tok = TOPO == 0 ? ((s & 1) ? (s >> 1) : -1) : s;
+            if (lane == (t & 63)) mine = tok;
+            if ((t & 63) == 0 && t + lane < Tb) ft[t + lane] = mine;
+            if (t > 0) {
+                const unsigned w = bpl[(t - c0) * 64 + (s >> SH)];
+                s -= (int)((w >> (2 * (s & (NS - 1)))) & 3u);
+                s = __builtin_amdgcn_readfirstlane(s < 0 ? 0 : s);
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// ---- 3. spans, score, token_score from frame_token.  grid B, 256 threads; every sum in a fixed order.
+__global__ __launch_bounds__(256) void vit_spans_kernel(VitArgs a, const float* __restrict__ xe, const float* __restrict__ lz,
+                                                        const int* __restrict__ frame_token, int* __restrict__ spans,
+                                                        float* __restrict__ score, float* __restrict__ token_score) {
+    __shared__ int sp[256][2];
+    __shared__ float red[256];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    int Tb, L, S;
+    vit_sizes(a, b, Tb, L, S);
+    const int* ft = frame_token + (long)b * a.T;
+    const long base = (long)b * a.T;
+    sp[tid][0] = -1;
+    sp[tid][1] = -1;
+    __syncthreads();
+    const bool feasible = Tb > 0 ? ft[0] != -2 : L == 0;
+    float part = 0.f;
+    if (feasible) {
+        for (int t = tid; t < Tb; t += 256) {
+            const int k = ft[t];
+            const int state = a.topology == 0 ? (k < 0 ? 0 : 2 * k + 1) : k;     // every blank state carries the same logit
+            part += xe[(base + t) * a.S_max + state] - lz[base + t];
+            if (k >= 0) {
+                if (t == 0 || ft[t - 1] != k) sp[k][0] = t;
+                if (t == Tb - 1 || ft[t + 1] != k) sp[k][1] = t + 1;
+            }
+        }
+    }
+    red[tid] = part;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o) red[tid] += red[tid + o];
+        __syncthreads();
+    }
+    if (tid == 0) score[b] = feasible ? red[0] : NEG_INF;
+    if (tid < (int)a.ldt) {
+        const int f0 = sp[tid][0], f1 = sp[tid][1];
+        spans[((long)b * a.ldt + tid) * 2] = f0;
+        spans[((long)b * a.ldt + tid) * 2 + 1] = f1;
+        if (token_score) {
+            float v = NEG_INF;
+            if (f0 >= 0) {
+                const int state = a.topology == 0 ? 2 * tid + 1 : tid;
+                float acc = 0.f;
+                for (int t = f0; t < f1; ++t) acc += xe[(base + t) * a.S_max + state] - lz[base + t];
+                v = acc / (float)(f1 - f0);
+            }
+            token_score[(long)b * a.ldt + tid] = v;
+        }
+    }
+}
+
+// workspace: xe [B*T][S_max] fp32 | lz [B*T] fp32 | backpointers [B*T][64] words of at most 2 bytes; every part 16-byte aligned
+struct VitLayout { int64_t xe, lz, bp, total; };
+VitLayout vit_layout(int64_t B, int64_t T, int64_t ldt) {
+    VitLayout l;
+    const int64_t S_max = 2 * ldt + 1;
+    l.xe = 0;
+    l.lz = (B * T * S_max * 4 + 15) / 16 * 16;
+    l.bp = l.lz + (B * T * 4 + 15) / 16 * 16;
+    l.total = l.bp + B * T * 64 * 2;
+    return l;
+}
+
+template <int NS>
+void launch_vit(const VitArgs& a, const float* xe, void* bp, int32_t* frame_token, hipStream_t stream) {
+    if (a.topology == 0) APTAI_LAUNCH((vit_recur_kernel<NS, 0>), dim3((unsigned)a.B), dim3(64), 0, stream, a, xe, bp, frame_token);
+    else APTAI_LAUNCH((vit_recur_kernel<NS, 1>), dim3((unsigned)a.B), dim3(64), 0, stream, a, xe, bp, frame_token);
+}
+
+}  // namespace
+
+extern "C" int64_t aptai_ctc_viterbi_workspace_bytes(int64_t B, int64_t T, int64_t ldt) { return vit_layout(B, T, ldt).total; }
+
+extern "C" int aptai_ctc_viterbi(const float* logits, int64_t ldl, int64_t rows_per_b, const int32_t* targets, int64_t ldt,
+                                 const int32_t* input_lens, const int32_t* target_lens, const int32_t* vocab_sizes, int64_t B,
+                                 int64_t T, int64_t V, int blank, int topology, void* workspace, int32_t* frame_token,
+                                 int32_t* spans, float* score, float* token_score, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    const char* who = "aptai_ctc_viterbi";
+    APTAI_REQUIRE(logits && targets && input_lens && target_lens && workspace && frame_token && spans && score, "%s: null pointer", who);
+    APTAI_REQUIRE(B > 0 && T > 0 && V > 0 && V <= MAXV && ldl >= V && rows_per_b >= T, "%s: bad sizes (V=%ld, max %d)", who, (long)V, MAXV);
+    APTAI_REQUIRE(ldt >= 1 && 2 * ldt + 1 <= 512, "%s: at most 255 labels per utterance (got row length %ld)", who, (long)ldt);
+    APTAI_REQUIRE(topology == 0 || topology == 1, "%s: topology must be 0 (CTC) or 1 (monotonic, no blank)", who);
+    APTAI_REQUIRE(topology == 1 || (blank >= 0 && blank < V), "%s: blank out of range", who);
+    APTAI_REQUIRE(((uintptr_t)workspace & 15) == 0, "%s: workspace must be 16-byte aligned", who);
+    VitArgs a;
+    memset(&a, 0, sizeof(a));
+    a.logits = logits; a.ldl = ldl; a.rows_per_b = rows_per_b; a.targets = targets; a.ldt = ldt;
+    a.input_lens = input_lens; a.target_lens = target_lens; a.vocab_sizes = vocab_sizes;
+    a.B = (int)B; a.T = (int)T; a.V = (int)V; a.blank = blank; a.topology = topology;
+    a.S_max = (int)(topology == 0 ? 2 * ldt + 1 : ldt);
+    const VitLayout l = vit_layout(B, T, ldt);
+    float* xe = (float*)((char*)workspace + l.xe);
+    float* lz = (float*)((char*)workspace + l.lz);
+    void* bp = (char*)workspace + l.bp;
+    APTAI_LAUNCH(vit_gather_kernel, dim3((unsigned)ceil_div(B * T, 4)), dim3(256), 0, stream, a, xe, lz);
+    APTAI_CHECK_LAUNCH("vit_gather_kernel");
+    const int ns = (a.S_max + 63) / 64;
+    if (ns <= 2) launch_vit<2>(a, xe, bp, frame_token, stream);
+    else if (ns <= 4) launch_vit<4>(a, xe, bp, frame_token, stream);
+    else launch_vit<8>(a, xe, bp, frame_token, stream);
+    APTAI_CHECK_LAUNCH("vit_recur_kernel");
+    APTAI_LAUNCH(vit_spans_kernel, dim3((unsigned)B), dim3(256), 0, stream, a, (const float*)xe, (const float*)lz,
+                 (const int*)frame_token, spans, score, token_score);
+    APTAI_CHECK_LAUNCH("vit_spans_kernel");
+    return APTAI_OK;
+}

@@ -75,8 +75,16 @@ def force_heads_fwd(ac, st, P):
     tv_loss = s.sc[1].clone()
     align_loss = s.fs_loss.reshape(()).clone()
     loss = 0.4 * tv_loss + 0.6 * align_loss
-    frame_phns = ops.gather_alignment(st.ids, s.align, st.frame_lens, B, Tp, _NPHN)
-    return (loss, tv_loss, align_loss, s.tvs, frame_phns, s.att_log, s.att_out, s.hout, s.align), s
+    align = s.align
+    if getattr(st, "readout", "argmax") == "monotonic":
+        # Viterbi read-out of the trellis the forward-sum loss trains (topology 1: every phoneme owns >= 1 frame, no jumps back):
+        # the att_log rows sit at column 1 of the 64-float forward-sum rows.  More phonemes than frames -> the argmax indices stay.
+        ft, _, score, _ = ops.ctc_viterbi(s.pad[:, 1:], 64, Tp, st.mono_targets, st.frame_lens, st.text_lens, B, T, _NPHN,
+                                          topology="monotonic", vocab_sizes_i32=st.text_lens, want_token_score=False)
+        align = s.align.clone()
+        align[:, :T] = torch.where((ft >= 0) & torch.isfinite(score)[:, None], ft.long(), s.align[:, :T])
+    frame_phns = ops.gather_alignment(st.ids, align, st.frame_lens, B, Tp, _NPHN)
+    return (loss, tv_loss, align_loss, s.tvs, frame_phns, s.att_log, s.att_out, s.hout, align), s
 
 
 def force_heads_bwd(s, st, P, ac, gloss=None):
@@ -200,6 +208,16 @@ class Force_APTAI(nn.Module):
         self._enc_seen = {}
         self._prefetched = None
 
+    # how `pred_frame_phns` is read out of the attention: "argmax" (the reference, models/force_aptai.py:148: per-frame argmax, may
+    # jump backwards and skip phonemes) or "monotonic" (opt-in: the best monotonic path through the same att_log rows, the Viterbi
+    # read-out that belongs to the forward-sum loss; aptai_ctc_viterbi topology 1).  Losses, tvs_pred and gradients do not depend on it.
+    alignment_readout = "argmax"
+
+    def _readout(self) -> str:
+        if self.alignment_readout not in ("argmax", "monotonic"):
+            raise ValueError(f"Force_APTAI.alignment_readout must be 'argmax' or 'monotonic', not {self.alignment_readout!r}")
+        return self.alignment_readout
+
     # ------------------------------------------------------------------ shared body
     def _encode(self, audio_inputs, audio_lengths, phn_pred_list=None):
         """Frozen recogniser (inference) + device best-path decode on the CURRENT stream: everything the heads read from it."""
@@ -308,7 +326,7 @@ class Force_APTAI(nn.Module):
                              p_hid=self.hidden_drop if tr else 0.0, p_rnn=self.rnn_drop if tr else 0.0,
                              seed=_seed(pr.wav2vec2.base_seed, step, 4242),
                              tv_tgt=tv_targets.contiguous(), fs_targets=consts["fs_targets"], frame_lens=frame_lens, rnn_lens=rnn_lens,
-                             text_lens=nlen, vocab_sizes=nlen + 1)
+                             text_lens=nlen, vocab_sizes=nlen + 1, readout=self._readout(), mono_targets=consts["mono_targets"])
         if getattr(self, "dp_loss_norm", None) is not None and tr:
             # the TV loss is a masked mean over the batch (models/force_aptai.py:137-141); the alignment and CTC terms are
             # means over utterances, which equal-sized shards already average exactly
@@ -351,6 +369,7 @@ class Force_APTAI(nn.Module):
                     full[T] = torch.full((B,), T, dtype=torch.int32, device=dev)
                 return full[T]
             c = {"fs_targets": torch.arange(1, _NPHN + 1, dtype=torch.int32, device=dev)[None, :].repeat(B, 1).contiguous(),
+                 "mono_targets": torch.arange(_NPHN, dtype=torch.int32, device=dev)[None, :].repeat(B, 1).contiguous(),
                  "full_T": full_T}
             self._const_cache = dict(getattr(self, "_const_cache", {}))
             self._const_cache[key] = c

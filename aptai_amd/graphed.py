@@ -654,7 +654,8 @@ class GraphedForceStep:
     step() as `next_batch`, or the same batch again) replays on the side stream.  Same kernels and the same two Python functions
     (force_heads_fwd / force_heads_bwd) as the eager autograd path; dropout draws fresh masks per replay through the per-stream
     salt; nothing synchronises host and device (`lists()` makes the Python lists of the reference's return value on demand).
-    The optimiser step is issued eagerly after the heads graph."""
+    The optimiser step is issued eagerly after the heads graph.  The captured heads keep the ARGMAX read-out of `pred_frame_phns`
+    whatever `Force_APTAI.alignment_readout` says (the monotonic read-out is an eager-path option)."""
 
     def __init__(self, model, optimizer, batch: Dict[str, torch.Tensor]):
         from .force_aptai import Force_APTAI, force_heads_bwd, force_heads_fwd
@@ -699,6 +700,7 @@ class GraphedForceStep:
         e = self.enc
         self.h_ac, self.h_ids, self.h_nlen, self.h_fl = (torch.empty_like(t) for t in (e.ac, e.ids, e.nlen, e.frame_lens))
         self.st, self.P = model._heads_state(g, self.h_ids, self.h_nlen, self.h_fl, self.tv_tgt, 0xF0)
+        self.st.readout = "argmax"
         self.g_heads = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.g_heads, pool=pool, stream=self._cap_stream, capture_error_mode=_CAPTURE_MODE):
             self.st.vocab_sizes = self.h_nlen + 1             # derived from a static input: recomputed on every replay

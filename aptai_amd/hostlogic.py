@@ -306,6 +306,111 @@ def _merge_and_prune(cands, floor, beam_size, log_add):
     return merged[:beam_size]
 
 
+# ----------------------------------------------------------------------------- forced alignment of a known transcript
+def ctc_forced_align(logits: np.ndarray, length: int, targets, blank: int = 0, topology: str = "ctc"):
+    """Best (Viterbi) path of the label sequence `targets` through the first `length` frames of `logits` [T][V]:
+    (frame_token int32 [T], score).  The contract of aptai_ctc_viterbi (include/aptai_hip.h), restated with the same order of
+    operations so that the device kernel can be checked against it bit for bit; also the CPU route for host-side tools.
+
+    topology "ctc": states blank, l1, blank, ..., lL, blank; transitions stay, +1, and +2 where the two labels differ.
+    topology "monotonic": states l1 .. lL, transitions stay and +1, start in l1, end in lL (`blank` is ignored).
+    frame_token[t] = transcript position 0..L-1, -1 on a blank frame, -2 at t >= length and everywhere when no path exists.
+
+    The path does not depend on the per-frame normaliser (one constant for every state of a frame), so the recursion runs on
+    the RAW logits in their own dtype: new[s] = best + x_t[ext_s], one addition per state and frame; max is exact.
+    Tie rule: stay is the incumbent; the s-1 predecessor replaces it only if strictly greater; then the s-2 predecessor
+    replaces that only if strictly greater; the path ends in the last state unless the one before it is strictly greater.
+    score = log-probability of the path under the per-frame log-softmax (float64 sum; -inf when no path exists, 0.0 for
+    length == 0 and no labels).  A label outside [0, V) has no path."""
+    if topology not in ("ctc", "monotonic"):
+        raise ValueError(f"topology must be 'ctc' or 'monotonic', not {topology!r}")
+    x = np.asarray(logits)
+    if not np.issubdtype(x.dtype, np.floating):
+        x = x.astype(np.float32)
+    T, V = x.shape
+    Tb = max(0, min(int(length), T))
+    tg = np.asarray(targets, dtype=np.int64).reshape(-1)
+    L = len(tg)
+    ctc = topology == "ctc"
+    ext = np.full(2 * L + 1, blank, dtype=np.int64) if ctc else tg.copy()
+    if ctc:
+        ext[1::2] = tg
+    S = len(ext)
+    frame_token = np.full(T, -2, dtype=np.int32)
+    if Tb == 0 or S == 0:
+        return frame_token, (0.0 if (Tb == 0 and L == 0) else -np.inf)
+    ninf = x.dtype.type(-np.inf)
+    ok = (ext >= 0) & (ext < V)
+    xe = np.where(ok[None, :], x[:Tb][:, np.where(ok, ext, 0)], ninf)             # [Tb][S] raw logit per extended state
+    skip = np.zeros(S, dtype=bool)                                                # s-2 -> s allowed
+    if ctc and S >= 4:
+        skip[3::2] = tg[1:] != tg[:-1]
+    bp = np.zeros((Tb, S), dtype=np.int8)
+    cur = np.full(S, ninf)
+    n_init = min(2, S) if ctc else 1
+    cur[:n_init] = xe[0, :n_init]
+    for t in range(1, Tb):
+        best, c = cur.copy(), bp[t]
+        a1 = np.concatenate([[ninf], cur[:-1]])
+        m = a1 > best
+        best[m], c[m] = a1[m], 1
+        if ctc:
+            a2 = np.concatenate([[ninf, ninf], cur[:-2]])[:S]
+            m = skip & (a2 > best)
+            best[m], c[m] = a2[m], 2
+        with np.errstate(invalid="ignore"):
+            cur = best + xe[t]
+    s = S - 1
+    if ctc and S >= 2 and cur[S - 2] > cur[S - 1]:
+        s = S - 2
+    if not cur[s] > ninf:
+        return frame_token, -np.inf
+    states = np.empty(Tb, dtype=np.int64)
+    for t in range(Tb - 1, -1, -1):
+        states[t] = s
+        s -= int(bp[t, s])
+    frame_token[:Tb] = (np.where(states & 1, states >> 1, -1) if ctc else states).astype(np.int32)
+    x64 = x[:Tb].astype(np.float64)
+    mx = x64.max(axis=1)
+    lz = mx + np.log(np.exp(x64 - mx[:, None]).sum(axis=1))
+    score = float((x64[np.arange(Tb), ext[states]] - lz).sum())
+    return frame_token, score
+
+
+def alignment_spans(frame_token, n_tokens: int) -> np.ndarray:
+    """int32 [n_tokens][2]: first and one-past-last frame of every transcript position of a `frame_token` row (-1, -1 = the
+    position owns no frame) - the `spans` output of aptai_ctc_viterbi."""
+    ft = np.asarray(frame_token).reshape(-1)
+    spans = np.full((int(n_tokens), 2), -1, dtype=np.int32)
+    for k in range(int(n_tokens)):
+        hit = np.nonzero(ft == k)[0]
+        if hit.size:
+            spans[k] = (hit[0], hit[-1] + 1)
+    return spans
+
+
+def fill_blank_frames(frame_token) -> np.ndarray:
+    """A transcript position for EVERY valid frame of a CTC alignment (what per-frame labels such as `phn_frames_49hz` need).
+    This is OUR rule - the reference takes its frame labels from MAUS boundaries, which are not reproducible here: a run of
+    blank frames between two tokens is split at its midpoint, the earlier token taking the extra frame of an odd run; leading
+    blanks go to the first token and trailing blanks to the last.  Frames marked -2 (padding / no path) stay -2; a row without
+    any token is returned unchanged."""
+    out = np.array(frame_token, dtype=np.int32).reshape(-1).copy()
+    tok = np.nonzero(out >= 0)[0]
+    if tok.size == 0:
+        return out
+    valid = np.nonzero(out != -2)[0]
+    out[valid[valid < tok[0]]] = out[tok[0]]
+    out[valid[valid > tok[-1]]] = out[tok[-1]]
+    for a, b in zip(tok[:-1], tok[1:]):
+        n = b - a - 1                                  # blank run a+1 .. b-1
+        if n > 0:
+            h = (n + 1) // 2
+            out[a + 1:a + 1 + h] = out[a]
+            out[a + 1 + h:b] = out[b]
+    return out
+
+
 # ----------------------------------------------------------------------------- target preparation (SURVEY.md §8f-4)
 def interpolate_signal(org_sig, tar_len: int) -> np.ndarray:
     """Linear resampling of a [frames] or [frames][channels] track to ``tar_len`` points that span the same time range

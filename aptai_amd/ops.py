@@ -816,6 +816,30 @@ def ctc_greedy_decode(logits, ldl, rows_per_b, B, T, V, blank, max_n):
     return ids, n
 
 
+_TOPOLOGY = {"ctc": 0, "monotonic": 1}
+
+
+def ctc_viterbi(logits, ldl, rows_per_b, targets_i32, input_lens_i32, target_lens_i32, B, T, V, *, blank=0, topology="ctc",
+                vocab_sizes_i32=None, want_token_score=True):
+    """Forced alignment on the device (aptai_ctc_viterbi): (frame_token int32 [B][T], spans int32 [B][ldt][2], score fp32 [B],
+    token_score fp32 [B][ldt] | None).  `logits` may be a view that starts inside a row (its data pointer is what the kernel
+    reads, with row stride ldl).  Nothing here synchronises host and device."""
+    _dev(logits, targets_i32, input_lens_i32, target_lens_i32, vocab_sizes_i32)
+    dev = logits.device
+    if targets_i32.shape[1] == 0:                      # an all-empty batch still needs one (unread) label slot per row
+        targets_i32 = torch.zeros((B, 1), device=dev, dtype=torch.int32)
+    ldt = targets_i32.shape[1]
+    ws = torch.empty(_lib.lib().aptai_ctc_viterbi_workspace_bytes(B, T, ldt), device=dev, dtype=torch.uint8)
+    frame_token = torch.empty((B, T), device=dev, dtype=torch.int32)
+    spans = torch.empty((B, ldt, 2), device=dev, dtype=torch.int32)
+    score = torch.empty(B, device=dev, dtype=torch.float32)
+    token_score = torch.empty((B, ldt), device=dev, dtype=torch.float32) if want_token_score else None
+    _lib.call("aptai_ctc_viterbi", logits.data_ptr(), ldl, rows_per_b, targets_i32.data_ptr(), ldt, input_lens_i32.data_ptr(),
+              target_lens_i32.data_ptr(), _ptr(vocab_sizes_i32), B, T, V, blank, _TOPOLOGY[topology], ws.data_ptr(),
+              frame_token.data_ptr(), spans.data_ptr(), score.data_ptr(), _ptr(token_score), _stream())
+    return frame_token, spans, score, token_score
+
+
 # ----------------------------------------------------------------------------- Force_APTAI heads (fp32)
 _SCRATCH32 = {}
 

@@ -251,6 +251,66 @@ class Wav2Vec2_PR(nn.Module):
             return {'phn_seq_idx': idx, 'phn_seq_ipa': [inv.get(int(i), '?') for i in idx],
                     'phn_seq_dur': [t * frame_sec_ratio for t in ts]}
 
+    # ------------------------------------------------------------------ forced alignment of a known transcript
+    def force_align(self, audio_inputs, audio_lengths, phoneme_labels):
+        """Hard alignment of KNOWN phoneme sequences to the frames, on the device (aptai_ctc_viterbi, CTC topology): what
+        torchaudio.functional.forced_align does for a CTC recogniser (torchaudio is not in the image: *parity unpinned*).
+        The batch has the layout of `forward`: waveforms, their lengths, labels padded with -100 (at most 255 per row).  Runs in
+        eval mode without gradients, in the encoder precision that is set.  Returns DEVICE tensors and never synchronises:
+          frame_token    int32 [B][T]     transcript position of each frame, -1 blank, -2 padding / no path
+          frame_phns     int32 [B][T]     vocabulary ids: the label of the position, the blank id on blank frames, 0 beyond the length
+          spans          int32 [B][L][2]  first and one-past-last frame of each position (-1, -1: none)
+          score          fp32  [B]        log-probability of the path (-inf: the transcript does not fit the utterance)
+          token_score    fp32  [B][L]     mean log-probability of each label over its span
+          frame_seq_lens int32 [B]
+        Tie rule and limits: include/aptai_hip.h; hostlogic.ctc_forced_align is the same contract in numpy."""
+        self.eval()
+        with torch.no_grad():
+            out, _ = self._logits_eval(audio_inputs, audio_lengths[:, None] if audio_lengths.dim() == 1 else audio_lengths)
+            g, full = out._geom, out._logits_full                     # [B*Tp][Np] fp32 with its padded pitches
+            dev = full.device
+            V = self.pr_head.weight.shape[0]
+            labels = phoneme_labels.to(dev).to(torch.int32)
+            if labels.shape[1] == 0:
+                labels = torch.full((g.B, 1), -100, device=dev, dtype=torch.int32)
+            if labels.shape[1] > 255:
+                raise ValueError(f"force_align: at most 255 labels per utterance (got rows of {labels.shape[1]})")
+            labels = labels.contiguous()
+            target_lens = (labels >= 0).sum(dim=-1).to(torch.int32)    # hostlogic.ctc_target_lengths, on the device
+            frame_lens = self.wav2vec2._get_feat_extract_output_lengths(audio_lengths.reshape(-1).to(dev)).to(torch.int32).contiguous()
+            blank = self._blank()
+            ft, spans, score, token_score = ops.ctc_viterbi(full, full.shape[1], g.Tp, labels, frame_lens, target_lens, g.B, g.T, V,
+                                                            blank=blank, topology="ctc")
+            lab = torch.gather(labels, 1, ft.clamp(min=0).long())
+            frame_phns = torch.where(ft >= 0, lab, torch.where(ft == -1, blank, 0)).to(torch.int32)
+            return {'frame_token': ft, 'frame_phns': frame_phns, 'spans': spans, 'score': score, 'token_score': token_score,
+                    'frame_seq_lens': frame_lens}
+
+    def align_phonemes_durations(self, wav, phn_seq_idx, vocab):
+        """`predict_phonemes_durations` for a KNOWN phoneme sequence: start and end of every phoneme in seconds (same
+        `frame_sec_ratio`), its mean log-probability, and a phoneme id for every frame (`phn_frames`: blank frames assigned by
+        hostlogic.fill_blank_frames).  Raises ValueError when the sequence does not fit the utterance."""
+        self.eval()
+        with torch.no_grad():
+            wav, wav_input, wav_len = self._wav(wav)
+            idx = np.asarray(phn_seq_idx, dtype=np.int64).reshape(-1)
+            res = self.force_align(wav_input, wav_len.reshape(-1), torch.as_tensor(idx[None].astype(np.int32)))
+            n_frames = res['frame_token'].shape[1]
+            frame_sec_ratio = len(wav) / n_frames / 16000
+            score = float(res['score'][0].cpu())
+            if not np.isfinite(score):
+                raise ValueError(f"align_phonemes_durations: {len(idx)} phonemes do not fit the utterance's "
+                                 f"{int(res['frame_seq_lens'][0].cpu())} frames (or a phoneme id is outside the vocabulary)")
+            spans = res['spans'][0, :len(idx)].cpu().numpy()
+            ft = res['frame_token'][0, :int(res['frame_seq_lens'][0].cpu())].cpu().numpy()
+            filled = hostlogic.fill_blank_frames(ft)
+            inv = {v: k for k, v in vocab.items()}
+            return {'phn_seq_idx': idx, 'phn_seq_ipa': [inv.get(int(i), '?') for i in idx],
+                    'phn_start': [int(a) * frame_sec_ratio for a in spans[:, 0]],
+                    'phn_end': [int(b) * frame_sec_ratio for b in spans[:, 1]],
+                    'phn_score': res['token_score'][0, :len(idx)].cpu().numpy().tolist(), 'score': score,
+                    'phn_frames': [int(idx[k]) if k >= 0 else self._blank() for k in filled]}
+
     def get_config(self):
         return {'huggingface_model_id': self.huggingface_model_id, 'cache_dir': self.cache_dir, 'pretrain_cfg': self.pretrain_cfg}
 

@@ -383,6 +383,30 @@ int aptai_ctc_bwd(const float* logits, int64_t ldl, int64_t rows_per_b, const in
                   int64_t V, int blank, int reduction, int zero_infinity, const float* workspace, const float* nll,
                   const float* grad_out, float extra_scale, void* dlogits, int64_t ldd, int out_bf16, int beta_ready, void* stream);
 int64_t aptai_ctc_workspace_bytes(int64_t B, int64_t T, int64_t ldt);
+/* Forced alignment of a KNOWN transcript: the best (Viterbi) path through the lattice aptai_ctc_fwd sums over.  Operands and
+ * conventions of aptai_ctc_fwd (logits fp32 rows (b*rows_per_b + t) stride ldl; targets int32 [B][ldt]; input_lens, target_lens,
+ * optional vocab_sizes; V <= 256; at most 255 labels; caller-owned workspace of aptai_ctc_viterbi_workspace_bytes, 16-byte
+ * aligned; the passed stream; no synchronisation, no atomics, same inputs -> same bits), plus `topology`:
+ *   0 = CTC: states blank, l1, blank, ..., lL, blank; transitions stay, +1, and +2 where the two labels differ;
+ *   1 = monotonic, no blank: states l1 .. lL; transitions stay and +1; the path starts in l1 and ends in lL, so every label
+ *       owns at least one frame (`blank` is ignored).
+ * The path does not depend on the per-frame normaliser, so the recursion runs on the RAW logits of the extended states:
+ * new[s] = best + x_t[ext_s], one fp32 addition per state and frame, first frame new[s] = x_0[ext_s] for the start states.
+ * TIE RULE: the current state (stay) is the incumbent; the s-1 predecessor replaces it only if strictly greater; then the s-2
+ * predecessor replaces that only if strictly greater.  The final state is the last one unless the one before it is strictly
+ * greater (topology 1: always the last).  With that frame_token is a pure function of the fp32 inputs
+ * (aptai_amd/hostlogic.py ctc_forced_align restates it in numpy).
+ * Outputs: frame_token int32 [B][T]: transcript position 0..L-1 of each frame, -1 = blank frame, -2 = frame at or beyond
+ * input_lens[b] and every frame of an utterance without a feasible path.  spans int32 [B][ldt][2]: first and one-past-last frame
+ * of each position, -1, -1 = none.  score fp32 [B]: log-probability of the path under the per-frame log-softmax over the
+ * utterance's classes (a sum over frames in a fixed order); -inf when no path exists (T_b too short, a label outside the
+ * vocabulary, T_b == 0 with L > 0) - a result, not an error status; 0 for T_b == 0 and L == 0.  token_score fp32 [B][ldt] (may be
+ * null): mean log-probability of the label over the frames of its span, -inf where the position has no span. */
+int aptai_ctc_viterbi(const float* logits, int64_t ldl, int64_t rows_per_b, const int32_t* targets, int64_t ldt,
+                      const int32_t* input_lens, const int32_t* target_lens, const int32_t* vocab_sizes, int64_t B, int64_t T,
+                      int64_t V, int blank, int topology, void* workspace, int32_t* frame_token, int32_t* spans, float* score,
+                      float* token_score, void* stream);
+int64_t aptai_ctc_viterbi_workspace_bytes(int64_t B, int64_t T, int64_t ldt);
 /* Best-path CTC decode on the device (stand-in for the torchaudio beam decoder the reference calls at models/w2v2_pr.py:143-159,
  * which is absent here: parity unpinned): per utterance, frame argmax (first maximum) over ALL T rows, repeats collapsed, blank
  * dropped.  ids_out int32 [B][max_n] zero-padded (the aligner's phoneme slots, models/force_aptai.py:109-115), n_out int32 [B] =
