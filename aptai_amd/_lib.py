@@ -23,7 +23,7 @@ _lib = None
 _lock = threading.Lock()
 
 _P, _I64, _I, _F, _U64 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_float, ctypes.c_uint64
-# argument types of every entry point except aptai_gemm_bf16 (descriptor struct, see ops.GemmDesc)
+# argument types of every entry point except aptai_gemm_bf16 / _grouped (descriptor struct, see ops.GemmDesc)
 ARGTYPES = {
     "aptai_layernorm_fwd": [_P, _P, _P, _P, _P, _P, _I64, _I64, _F, _I, _P],
     "aptai_layernorm_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _F, _U64, _P, _P, _P, _I64, _I64, _P, _P],
@@ -58,6 +58,7 @@ ARGTYPES = {
     "aptai_aptai_loss_fwd": [_P, _P, _P, _I64, _I64, _P, _I64, _I64, _I64, _I64, _F, _F, _P, _P, _P, _P],
     "aptai_aptai_loss_bwd": [_P, _P, _P, _I64, _I64, _P, _I64, _I64, _I64, _I64, _F, _F, _P, _P, _P, _P, _I64, _P],
     "aptai_aptai_loss_workspace_bytes": [],
+    "aptai_gemm_plan": [_P, _P],
     "aptai_gemm_workspace_bytes": [_I64, _I64, _I],
     "aptai_gemm_sk_workspace_bytes": [],
     "aptai_gemm_sk_status": [_P, _P, _P],

@@ -17,6 +17,7 @@
 
 #include <mutex>
 #include <set>
+#include <type_traits>
 
 #include "common.h"
 #include "gemm_common.h"
@@ -517,26 +518,10 @@ __global__ void splitk_reduce_kernel(const float* __restrict__ slabs, float* __r
     }
 }
 
-template <bool B_KM, bool OUT_F32>
-int launch_gemm_m64(GemmArgs g, int nbatch, int nsplit, hipStream_t stream) {
-    auto kern = gemm_kernel_m64<B_KM, OUT_F32>;
-    g.tiles_m = (int)ceil_div(g.M, 64);
-    dim3 grid(g.tiles_m * g.tiles_n, nbatch, nsplit);
-    APTAI_LAUNCH(kern, grid, dim3(NTHREADS), SMEM_M64_BYTES, stream, g);
-    APTAI_CHECK_LAUNCH("gemm_kernel_m64");
-    return APTAI_OK;
-}
-
 template <bool A_KM, bool B_KM, bool OUT_F32>
-int launch_gemm(const GemmArgs& g, int nbatch, int nsplit, hipStream_t stream) {
-    auto kern = gemm_kernel<A_KM, B_KM, OUT_F32>;
+int launch_gemm128(const GemmArgs& g, dim3 grid, hipStream_t stream) {
+    constexpr auto kern = gemm_kernel<A_KM, B_KM, OUT_F32>;
     constexpr int smem = smem_for<A_KM, B_KM>();
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-        attr_set = true;
-    }
-    dim3 grid(g.tiles_m * g.tiles_n, nbatch, nsplit);
 #ifdef APTAI_EXP_STAGGER
     {   // development: per-call sleep and LDS request (occupancy) from the environment (tools/stagger_probe.py)
         GemmArgs ge = g;
@@ -552,9 +537,7 @@ int launch_gemm(const GemmArgs& g, int nbatch, int nsplit, hipStream_t stream) {
         return APTAI_OK;
     }
 #endif
-    APTAI_LAUNCH(kern, grid, dim3(NTHREADS), smem, stream, g);
-    APTAI_CHECK_LAUNCH("gemm_kernel");
-    return APTAI_OK;
+    return launch_kernel<kern>({NTHREADS, smem, "gemm_kernel"}, grid, stream, g);
 }
 
 
@@ -1054,36 +1037,12 @@ __global__ __launch_bounds__(T2_THREADS, 2) void gemm256_sk_kernel(GemmArgs g, S
     }
 }
 
-template <bool A_KM, bool B_KM, bool OUT_F32>
-int launch_gemm256(GemmArgs g, int nbatch, int nsplit, hipStream_t stream) {
-    auto kern = gemm256_kernel<A_KM, B_KM, OUT_F32>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, T2_SMEM);
-        attr_set = true;
-    }
-    g.tiles_m = (int)ceil_div(g.M, T2_BM);
-    g.tiles_n = (int)ceil_div(g.N, T2_BN);
-    dim3 grid(g.tiles_m * g.tiles_n, nbatch, nsplit);
-    APTAI_LAUNCH(kern, grid, dim3(T2_THREADS), T2_SMEM, stream, g);
-    APTAI_CHECK_LAUNCH("gemm256_kernel");
-    return APTAI_OK;
-}
-
 constexpr int SK_MAX_GRID = 256;                         // one workgroup per CU of an MI355X
 constexpr int64_t SK_HEADER_BYTES = 4096;                // status word @0, flags @256 .. 256 + 4 * SK_MAX_GRID
 static inline int64_t sk_workspace_bytes() { return SK_HEADER_BYTES + (int64_t)SK_MAX_GRID * SK_SLAB_FLOATS * 4; }
 
 template <bool A_KM, bool B_KM, bool OUT_F32>
-int launch_gemm256_sk(GemmArgs g, void* ws, hipStream_t stream) {
-    auto kern = gemm256_sk_kernel<A_KM, B_KM, OUT_F32>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, T2_SMEM);
-        attr_set = true;
-    }
-    g.tiles_m = (int)ceil_div(g.M, T2_BM);
-    g.tiles_n = (int)ceil_div(g.N, T2_BN);
+int launch_gemm256_sk(const GemmArgs& g, void* ws, hipStream_t stream) {
     SkArgs sk;
     sk.status = (unsigned*)ws;
     sk.flags = (unsigned*)((char*)ws + 256);
@@ -1093,9 +1052,7 @@ int launch_gemm256_sk(GemmArgs g, void* ws, hipStream_t stream) {
     if (total >= (1L << 23)) APTAI_FAIL(APTAI_ERR_INVALID, "aptai_gemm_bf16: stream-K iteration count %ld out of range", total);
     sk.total_iters = (int)total;
     const int grid = total < SK_MAX_GRID ? (int)total : SK_MAX_GRID;
-    APTAI_LAUNCH(kern, dim3(grid), dim3(T2_THREADS), T2_SMEM, stream, g, sk);
-    APTAI_CHECK_LAUNCH("gemm256_sk_kernel");
-    return APTAI_OK;
+    return launch_kernel<gemm256_sk_kernel<A_KM, B_KM, OUT_F32>>({T2_THREADS, T2_SMEM, "gemm256_sk_kernel"}, dim3(grid), stream, g, sk);
 }
 
 // =====================================================================================================================
@@ -1462,26 +1419,46 @@ __global__ __launch_bounds__(T3_THREADS, 1) void gemm192_kernel(GemmArgs g) {
 #endif
 }
 
-template <bool A_KM, bool B_KM, bool OUT_F32>
-int launch_gemm192(GemmArgs g, int nbatch, int nsplit, hipStream_t stream) {
-    auto kern = gemm192_kernel<A_KM, B_KM, OUT_F32>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, T3_SMEM);
-        attr_set = true;
-    }
-    g.tiles_m = (int)ceil_div(g.M, T3_BM);
-    g.tiles_n = (int)ceil_div(g.N, T3_BN);
-    dim3 grid(g.tiles_m * g.tiles_n, nbatch, nsplit);
-    APTAI_LAUNCH(kern, grid, dim3(T3_THREADS), T3_SMEM, stream, g);
-    APTAI_CHECK_LAUNCH("gemm192_kernel");
-    return APTAI_OK;
-}
-
 }  // namespace
 
-// validates one descriptor and fills the kernel arguments (tiles for the 128-tile kernel; the others recompute them)
-static int build_args(const aptai_gemm_desc* d, GemmArgs& g, int& nbatch, int& nsplit, const void* stream) {
+// ===================================================================================================================== host side
+// aptai_gemm_plan (validate_desc -> plan_gemm, a pure function of the descriptor and the process's knobs; no device) -> fill_args ->
+// launch_plan.  tests/test_cpu_gemm_plan.py pins the planner.
+
+// Environment knobs (A/B switches), read once per process at the first GEMM call; `= x` is what unset means.
+struct GemmKnobs {
+    int tile;               // APTAI_GEMM_TILE = 0: what `tile = 0` in a descriptor means (0 = the rule in auto_tile)
+    double f256;            // APTAI_GEMM_F256 = 1.25: the 256-tile advantage factor of the wave-quantisation model
+    int m64;                // APTAI_GEMM_M64 = 1: 0 disables the 64-row rule, 2 restricts it to single-round shapes
+    int raster;             // APTAI_GEMM_RASTER = -1: tile rows per raster group for every kernel, 0 = row-major, negative = the entry's default
+    bool splitn;            // APTAI_GEMM_SPLITN = 0: the two-launch column split (splitn_column); a set APTAI_GEMM_TILE disables it
+    bool epi_runtime;       // APTAI_EPI_RUNTIME = 0: every epilogue runs its run-time form (EPX_RUNTIME)
+};
+static const GemmKnobs& gemm_knobs() {
+    static const auto env = [](const char* name, const char* unset) { const char* e = getenv(name); return e ? e : unset; };
+    static const GemmKnobs k = {atoi(env("APTAI_GEMM_TILE", "0")), atof(env("APTAI_GEMM_F256", "1.25")), atoi(env("APTAI_GEMM_M64", "1")),
+                                atoi(env("APTAI_GEMM_RASTER", "-1")), atoi(env("APTAI_GEMM_SPLITN", "0")) != 0 && !getenv("APTAI_GEMM_TILE"),
+                                atoi(env("APTAI_EPI_RUNTIME", "0")) != 0};
+    return k;
+}
+static int raster_group(const GemmKnobs& k, int entry_default) { return k.raster >= 0 ? k.raster : entry_default; }
+
+// aptai_gemm_plan_info (everything a launch needs beyond the raw operands; tile values other than 64 / 192 / 256 / 257 / 448 run as 128),
+// or why no kernel runs the descriptor as asked: the error text
+struct GemmPlan : aptai_gemm_plan_info { const char* refusal; };
+// rows / columns of the kernel behind a tile value (448: T4_BM x T4_BN of gemm_t4.hip)
+static constexpr int tile_rows(int t) { return t == 64 ? 64 : (t == 256 || t == 257) ? T2_BM : t == 448 ? 256 : t == 192 ? T3_BM : BM; }
+static constexpr int tile_cols(int t) { return t == 192 ? T3_BN : (t == 256 || t == 257) ? T2_BN : t == 448 ? 192 : BN; }
+// batch count, and split-K as launched: at most one slab per K-tile, equal K-tile counts, no empty slab (K >= 64)
+static void launch_shape(const aptai_gemm_desc& d, int& nbatch, int& nsplit, int& ktiles_per_split) {
+    nbatch = (d.batch_outer > 1 || d.batch_inner > 1) ? (d.batch_outer > 0 ? d.batch_outer : 1) * (d.batch_inner > 0 ? d.batch_inner : 1) : 1;
+    const int total_kt = (int)(d.K / BK);
+    nsplit = d.split_k > 0 ? (d.split_k < total_kt ? d.split_k : total_kt) : 1;
+    ktiles_per_split = (int)ceil_div(total_kt, nsplit);
+    nsplit = (int)ceil_div(total_kt, ktiles_per_split);
+}
+
+static int validate_desc(const aptai_gemm_desc* d) {
     APTAI_REQUIRE(d != nullptr, "aptai_gemm_bf16: null descriptor");
     APTAI_REQUIRE(d->M > 0 && d->N > 0 && d->K > 0, "aptai_gemm_bf16: empty problem M=%ld N=%ld K=%ld", (long)d->M,
                   (long)d->N, (long)d->K);
@@ -1514,6 +1491,141 @@ static int build_args(const aptai_gemm_desc* d, GemmArgs& g, int& nbatch, int& n
                       "aptai_gemm_bf16: EPI_SPLIT_OUT needs out_f32, tile 128 / 192 / 256, 3 or 6 pieces and ldc >= pieces * N (bf16 elements)");
     APTAI_REQUIRE(d->colscale_n >= 0 && d->colscale_n % 8 == 0 && d->colscale_n <= d->N && (d->colscale_n == 0 || !d->out_f32),
                   "aptai_gemm_bf16: colscale_n must be a multiple of 8 within N, bf16 output only");
+    int nbatch, nsplit, ktiles_per_split;
+    launch_shape(*d, nbatch, nsplit, ktiles_per_split);
+    if (nbatch > 1) {
+        for (int l = 0; l < 2; ++l)
+            APTAI_REQUIRE(d->batch_stride_a[l] % 8 == 0 && d->batch_stride_b[l] % 8 == 0 && d->batch_stride_c[l] % 8 == 0 &&
+                              d->batch_stride_bias[l] % 4 == 0 && d->batch_stride_res[l] % 8 == 0 && d->batch_stride_aux[l] % 8 == 0,
+                          "aptai_gemm_bf16: batch strides must keep vector alignment");
+        APTAI_REQUIRE(nbatch <= 65535, "aptai_gemm_bf16: too many batches");
+    }
+    const bool f32 = d->out_f32 != 0;
+    if (nbatch > 1) APTAI_REQUIRE(!(f32 && (d->split_k > 1 || d->accumulate)), "aptai_gemm_bf16: batched GEMM cannot split-K/accumulate");
+    if (!f32) APTAI_REQUIRE(nsplit == 1, "aptai_gemm_bf16: split-K needs fp32 output");
+    if (f32 && (nsplit > 1 || d->accumulate)) {
+        APTAI_REQUIRE(d->workspace != nullptr, "aptai_gemm_bf16: split-K / accumulate needs a workspace");
+        APTAI_REQUIRE(d->ldc == d->N, "aptai_gemm_bf16: split-K output must be dense (ldc == N)");
+        APTAI_REQUIRE((size_t)d->workspace_bytes >= (size_t)nsplit * d->M * d->N * 4, "aptai_gemm_bf16: workspace too small");
+    }
+    return APTAI_OK;
+}
+
+// Outputs that make x.5 rounds of 256 x 256 tiles (base FFN1 forward / FFN2 dgrad: 8192 x 3072 = 384 tiles on 256 CUs) run as TWO
+// launches over column ranges: whole rounds of 256-row tiles (0.63 of the MFMA rate in the loop), then the remainder as one round of
+// 128-row tiles - instead of three rounds of 128-row tiles (0.34).  Measured both ways in one call: standalone the single launch is the
+// faster one since the 128-row kernels walk the tiles in 2-D groups (FFN1 forward 56-58 vs 60.8 us), in the step the split is (8.82-8.85
+// -> 8.78-8.79 ms, three interleaved pairs).  OFF by default (APTAI_GEMM_SPLITN=1 turns it on): 0.5 % is not worth a whole-CU 256-row launch
+// in the backward pass, where anything that runs beside it - Force_APTAI's BiLSTM clusters did, a gradient all-reduce would - cannot get a CU.  Bit-identical outputs and dropout masks
+// (tests/test_gpu_gemm.py: a tile's K walk does not depend on its size; the element index is the whole output's, hash_ld / hash_n0).
+// Returns the first column of the 128-row part, or 0 for one launch.
+static long splitn_column(const aptai_gemm_desc& d, const GemmKnobs& k) {
+    if (!(k.splitn && d.tile == 0 && !d.out_f32 && !d.a_kmajor && d.split_k <= 1 && !d.accumulate && d.batch_outer <= 1 &&
+          d.batch_inner <= 1 && d.colscale_n == 0 && d.sk_workspace == nullptr && d.M % 256 == 0 && d.N % 256 == 0 && d.K <= 1024))
+        return 0;
+    const long tm = d.M / 256, tn = d.N / 256, T = tm * tn;
+    if (!(T > 256 && T % 256 == 128 && (T - 128) % tm == 0)) return 0;
+    const long n1 = (T - 128) / tm * 256, rem = d.N - n1;
+    return (d.M / 128) * (rem / 128) <= 512 ? n1 : 0;
+}
+
+// The tile rule (descriptor and APTAI_GEMM_TILE both say 0): a base choice between the 256- and the 128-row kernel, then an ORDERED
+// list of refinements at the end - the first that applies decides, and that order is part of the rule.
+static int auto_tile(const aptai_gemm_desc& d, const GemmKnobs& k, int nbatch, int nsplit) {
+    const auto tiles = [&](int rows, int cols) { return ceil_div(d.M, rows) * ceil_div(d.N, cols); };
+    // wave-quantisation model fitted to tools/gemm_bench*.py on MI355X: the 256-tile kernel sustains ~1.25x the
+    // 128-tile kernel per busy CU (1 block/CU, 256 slots) but needs the grid to fill whole rounds of 256 tiles;
+    // the 128-tile kernel runs 2 blocks/CU (512 slots).
+    const long t256 = tiles(T2_BM, T2_BN) * nbatch * nsplit;
+    const long t128 = tiles(BM, BN) * nbatch * nsplit;
+    const double e256 = (double)t256 / (double)(ceil_div(t256, 256) * 256);
+    const double e128 = (double)t128 / (double)(ceil_div(t128, 512) * 512);
+    const int base = (d.M >= 256 && d.N >= 256 && k.f256 * e256 > e128) ? 256 : 128;
+    // 128x192 tiles (one block per CU): measured faster than the 128-tile kernel only where the whole K-contiguous GEMM
+    // is ONE round of full tiles (8192 x 768: 16.9 vs 19.7 us at K = 768, 43.6 vs 51.2 us at K = 3072)
+    const long t192 = tiles(T3_BM, T3_BN) * nbatch * nsplit;
+    // (round 3: also with a K-major B, the dgrads [8192] x 768 - since its LDS reads go through inline asm with counted waits the
+    //  192-tile kernel no longer drains its ring at every K-tile: 35.6 vs 38.6 us at K = 2304, 45.1 vs 49.0 us at K = 3072)
+    const bool full_tiles_192 = !d.a_kmajor && d.M % T3_BM == 0 && d.N % T3_BN == 0;
+    const bool fits_one_round_192 = base == 128 && full_tiles_192 && t192 > 192 && t192 <= 256;
+    // ... and where it is a whole number of rounds with a light epilogue (one block per CU leaves GELU / dropout arithmetic
+    // exposed: 8192 x 2304 x 768 with bias only 38.3 vs 40.7-42.8 us for the 64- / 128-row tiles, but 58.0 vs 52.5 us with
+    // bias + GELU + dropout + second output; tools/gemm_round.py)
+    const bool light_epi = !(d.flags & (APTAI_EPI_GELU | APTAI_EPI_DROPOUT | APTAI_EPI_DGELU)) && d.out_pre == nullptr;
+    const bool whole_rounds_192_light_epilogue = base == 128 && full_tiles_192 && !d.b_kmajor && t192 % 256 == 0 && t192 <= 768 &&
+                                                 d.K <= 1024 && light_epi && nbatch == 1 && nsplit == 1;
+    // 256 x 192 tiles (round 4, csrc/gemm_t4.hip; one block per CU, 8.9 staged bytes per kflop against 12.9 / 15.2): measured faster only
+    // where the whole K-contiguous GEMM is whole rounds of full tiles with a light epilogue - wav2vec2-large's q|k|v projection,
+    // [4096] x 3072 x 1024 = exactly 256 tiles: 26-28 us against 31-32 (128-row tiles) and 29-30 (vendor library), tools/gemm_t4_bench.py,
+    // profiles/r04_gemm_t4_bench.txt.  On the base model's [8192] x {2304, 3072} outputs it ties the 128-row kernels (43-44 us): every tile
+    // of this family sits on the same LDS / delivery balance, and its exposed epilogue loses with GELU / dropout.
+    const long t448 = tiles(tile_rows(448), tile_cols(448));
+    const bool whole_rounds_448 = !d.a_kmajor && !d.b_kmajor && !d.out_f32 && nbatch == 1 && nsplit == 1 && !d.accumulate && d.M % 256 == 0 &&
+                                  d.N % 192 == 0 && t448 % 256 == 0 && t448 <= 512 && light_epi && d.K >= 1024;
+    // GEMMs that fill the 512 slots of the 128-tile kernel badly run as 64 x 128 tiles on 768 slots (3 blocks per CU): base
+    // dgrads [8192] x 768 (384 tiles -> 768: 49.1 vs 54.9 us at K = 3072, 38.0 vs 42.9 us at K = 2304), base QKV (1152 tiles =
+    // 2.25 rounds -> 2304 = 3 rounds), large [4096] x 1024 outputs (256 tiles -> 512: 13.7 vs 17.5 us at K = 1024, 42.4 vs
+    // 47.5 us at K = 4096, dgrads 41-52 vs 52-65 us).  Whole step: -0.25 ms from the multi-round cases alone.
+    // APTAI_GEMM_M64=0 disables the rule, =2 restricts it to single-round shapes (A/B).
+    const long t64 = tiles(64, BN) * nbatch * nsplit;
+    const double e64 = (double)t64 / (double)(ceil_div(t64, 768) * 768);
+    const bool prefers_m64 = k.m64 && base == 128 && !d.a_kmajor && d.M % 64 == 0 && (t128 <= 512 || k.m64 != 2) && e64 >= 1.2 * e128;
+    if (fits_one_round_192) return 192;
+    if (whole_rounds_192_light_epilogue) return 192;
+    if (whole_rounds_448) return 448;
+    if (prefers_m64) return 64;
+    return base;
+}
+
+// Pure: no HIP call, no static, no environment; pointers are only compared with null.  Expects a descriptor validate_desc accepted.
+static GemmPlan plan_gemm(const aptai_gemm_desc& d, const GemmKnobs& k) {
+    // 2-D rasterisation (tile groups of 8 rows per XCD) for every kernel.  Rounds 2 and 3a kept the row-major walk for the 128- and 64-row
+    // kernels with a K-contiguous A, which then LOST 5-7 % to the raster (FFN1 forward 71.5 -> 76.7 us) while it cut their fabric-side
+    // re-reads (FFN1: 129 MB fetched for 17 MB of operands); with the per-flag-word epilogues the balance is the other way: per forced
+    // 128-row tile FFN1 forward 61.5-64.2 -> 59.3 us, FFN2 dgrad 50.4 -> 48.8 us, the layer's ten bf16-output GEMMs 388-392 -> 382-383 us
+    // (tools/step_gemm_tiles.py, APTAI_GEMM_RASTER = -1 / 4 / 8 / 16 in one call; 64-row tiles 425 -> 416 us).  APTAI_GEMM_RASTER=0 = row-major.
+    GemmPlan p = {};
+    launch_shape(d, p.nbatch, p.nsplit, p.ktiles_per_split);
+    p.raster_gm = raster_group(k, 8);
+    p.split_n = splitn_column(d, k);
+    p.tile = 256;
+    if (p.split_n) return p;
+    // tile selection: the 256x256 deep-pipelined kernel when the grid still fills the chip, else 128x128 (2 blocks/CU)
+    p.tile = d.tile ? d.tile : k.tile ? k.tile : auto_tile(d, k, p.nbatch, p.nsplit);
+    const bool sk_ok = d.sk_workspace != nullptr && d.sk_workspace_bytes >= sk_workspace_bytes() && p.nbatch == 1 && p.nsplit == 1 &&
+                       !d.accumulate && d.M >= T2_BM && d.N >= T2_BN;
+    if (p.tile == 257 && !sk_ok)
+        p.refusal = "aptai_gemm_bf16: tile 257 (stream-K) needs sk_workspace (aptai_gemm_sk_workspace_bytes), no batching / "
+                    "split-K / accumulate and M, N >= 256";
+    else if (p.tile == 64 && d.a_kmajor)
+        p.tile = 128;            // 64-row tiles need a K-contiguous A
+    else if (p.tile == 448 && !(!d.out_f32 && !d.a_kmajor && p.nbatch == 1 && p.nsplit == 1 && !d.accumulate))
+        p.refusal = "aptai_gemm_bf16: tile 448 (256 x 192) is built for bf16 output, K-contiguous A, no batching / split-K";
+    return p;
+}
+
+// The three run-time layout switches as compile-time constants: f(a_km, b_km, out_f32) receives std::bool_constants.  Only the
+// three operand layouts that are built are instantiated; the fourth is refused here, for every kernel.
+template <class F>
+static int with_layout(const char* who, bool a_km, bool b_km, bool out_f32, F&& f) {
+    APTAI_REQUIRE(!(a_km && !b_km), "%s: A K-major with B K-contiguous is not built", who);
+    const auto out = [&](auto a, auto b) { return out_f32 ? f(a, b, std::true_type{}) : f(a, b, std::false_type{}); };
+    return a_km ? out(std::true_type{}, std::true_type{}) : b_km ? out(std::false_type{}, std::true_type{}) : out(std::false_type{}, std::false_type{});
+}
+
+// validate, plan with the process's knobs, and turn what the planner or the layout table refuses into the error: host only
+extern "C" int aptai_gemm_plan(const aptai_gemm_desc* d, aptai_gemm_plan_info* out) {
+    APTAI_REQUIRE(out != nullptr, "aptai_gemm_plan: null output");
+    const int rc = validate_desc(d);
+    if (rc != APTAI_OK) return rc;
+    const GemmPlan p = plan_gemm(*d, gemm_knobs());
+    if (p.refusal) APTAI_FAIL(APTAI_ERR_INVALID, "%s", p.refusal);
+    *out = p;
+    return with_layout("aptai_gemm_bf16", d->a_kmajor != 0, d->b_kmajor != 0, d->out_f32 != 0, [](auto, auto, auto) { return (int)APTAI_OK; });
+}
+
+// descriptor + plan -> kernel arguments.  Split-K / accumulate launches write fp32 slabs into the workspace (reduced afterwards).
+static void fill_args(const aptai_gemm_desc* d, const aptai_gemm_plan_info& p, const void* stream, GemmArgs& g) {
     memset(&g, 0, sizeof(g));
     g.A = (const bf16_t*)d->A; g.lda = d->lda;
     g.B = (const bf16_t*)d->B; g.ldb = d->ldb;
@@ -1534,214 +1646,76 @@ static int build_args(const aptai_gemm_desc* d, GemmArgs& g, int& nbatch, int& n
     g.split_pieces = d->split_out_pieces;
     g.split_bcol = (d->flags & APTAI_EPI_SPLIT_OUT) ? d->split_out_bcol : 0;
     g.hash_ld = d->N; g.hash_n0 = 0;
-    g.tiles_m = (int)ceil_div(d->M, BM);
-    g.tiles_n = (int)ceil_div(d->N, BN);
-    {
-        // default (-1 here, resolved per kernel in raster_default below): groups of 8 tile rows for the kernels that gain from
-        // it, the plain row-major walk for the others; APTAI_GEMM_RASTER=<n> forces one value everywhere (A/B)
-        static int raster = -2;
-        if (raster == -2) {
-            const char* e = getenv("APTAI_GEMM_RASTER");
-            raster = e ? atoi(e) : -1;
-        }
-        g.raster_gm = raster;
-    }
-    const int total_kt = g.K / BK;
-    nsplit = d->split_k > 0 ? d->split_k : 1;
-    if (nsplit > total_kt) nsplit = total_kt;
-    g.ktiles_per_split = (int)ceil_div(total_kt, nsplit);
-    nsplit = (int)ceil_div(total_kt, g.ktiles_per_split);
-
-    nbatch = 1;
+    g.tiles_m = (int)ceil_div(d->M, tile_rows(p.tile));
+    g.tiles_n = (int)ceil_div(d->N, tile_cols(p.tile));
+    g.raster_gm = p.raster_gm;
+    g.ktiles_per_split = p.ktiles_per_split;
     g.nb_inner = 1;
-    if (d->batch_outer > 1 || d->batch_inner > 1) {
-        const int bo = d->batch_outer > 0 ? d->batch_outer : 1, bi = d->batch_inner > 0 ? d->batch_inner : 1;
-        nbatch = bo * bi;
-        g.nb_inner = bi;
+    if (p.nbatch > 1) {
+        g.nb_inner = d->batch_inner > 0 ? d->batch_inner : 1;
         for (int l = 0; l < 2; ++l) {
             g.sA[l] = d->batch_stride_a[l]; g.sB[l] = d->batch_stride_b[l]; g.sC[l] = d->batch_stride_c[l];
             g.sBias[l] = d->batch_stride_bias[l]; g.sR[l] = d->batch_stride_res[l]; g.sAux[l] = d->batch_stride_aux[l];
-            APTAI_REQUIRE(g.sA[l] % 8 == 0 && g.sB[l] % 8 == 0 && g.sC[l] % 8 == 0 && g.sBias[l] % 4 == 0 &&
-                              g.sR[l] % 8 == 0 && g.sAux[l] % 8 == 0,
-                          "aptai_gemm_bf16: batch strides must keep vector alignment");
         }
-        APTAI_REQUIRE(nbatch <= 65535, "aptai_gemm_bf16: too many batches");
     }
-    const bool f32 = d->out_f32 != 0;
-    if (nbatch > 1) APTAI_REQUIRE(!(f32 && (d->split_k > 1 || d->accumulate)), "aptai_gemm_bf16: batched GEMM cannot split-K/accumulate");
-    if (!f32) APTAI_REQUIRE(nsplit == 1, "aptai_gemm_bf16: split-K needs fp32 output");
-    if (f32 && (nsplit > 1 || d->accumulate)) {
-        APTAI_REQUIRE(d->workspace != nullptr, "aptai_gemm_bf16: split-K / accumulate needs a workspace");
-        APTAI_REQUIRE(d->ldc == d->N, "aptai_gemm_bf16: split-K output must be dense (ldc == N)");
-        APTAI_REQUIRE((size_t)d->workspace_bytes >= (size_t)nsplit * d->M * d->N * 4, "aptai_gemm_bf16: workspace too small");
+    if (d->out_f32 && (p.nsplit > 1 || d->accumulate)) {
         g.C = d->workspace;
         g.slab_stride = (long)d->M * d->N;
     }
-    return APTAI_OK;
 }
 
-static int gemm_bf16_one(const aptai_gemm_desc* d, void* stream_, long hash_ld, int hash_n0);
-
-extern "C" int aptai_gemm_bf16(const aptai_gemm_desc* d, void* stream_) {
-    // Outputs that make x.5 rounds of 256 x 256 tiles (base FFN1 forward / FFN2 dgrad: 8192 x 3072 = 384 tiles on 256 CUs) run as TWO
-    // launches over column ranges: whole rounds of 256-row tiles (0.63 of the MFMA rate in the loop), then the remainder as one round of
-    // 128-row tiles - instead of three rounds of 128-row tiles (0.34).  Measured both ways in one call: standalone the single launch is the
-    // faster one since the 128-row kernels walk the tiles in 2-D groups (FFN1 forward 56-58 vs 60.8 us), in the step the split is (8.82-8.85
-    // -> 8.78-8.79 ms, three interleaved pairs).  OFF by default (APTAI_GEMM_SPLITN=1 turns it on): 0.5 % is not worth a whole-CU 256-row launch
-    // in the backward pass, where anything that runs beside it - Force_APTAI's BiLSTM clusters did, a gradient all-reduce would - cannot get a CU.  Bit-identical outputs and dropout masks
-    // (tests/test_gpu_gemm.py: a tile's K walk does not depend on its size; the element index is the whole output's, hash_ld / hash_n0).
-    static const bool split_on = getenv("APTAI_GEMM_SPLITN") && atoi(getenv("APTAI_GEMM_SPLITN")) != 0;
-    if (split_on && d != nullptr && d->tile == 0 && !d->out_f32 && !d->a_kmajor && d->split_k <= 1 && !d->accumulate && d->batch_outer <= 1 &&
-        d->batch_inner <= 1 && d->colscale_n == 0 && d->sk_workspace == nullptr && d->M % 256 == 0 && d->N % 256 == 0 && d->K <= 1024 &&
-        getenv("APTAI_GEMM_TILE") == nullptr) {
-        const long tm = d->M / 256, tn = d->N / 256, T = tm * tn;
-        if (T > 256 && T % 256 == 128 && (T - 128) % tm == 0) {
-            const long n1 = (T - 128) / tm * 256, rem = d->N - n1;
-            if ((d->M / 128) * (rem / 128) <= 512) {
-                aptai_gemm_desc a = *d, b = *d;
-                a.N = n1; a.tile = 256;
-                b.N = rem; b.tile = 128;
-                b.B = (const char*)d->B + (d->b_kmajor ? n1 * 2 : n1 * d->ldb * 2);
-                b.C = (char*)d->C + n1 * 2;
-                if (d->out_pre) b.out_pre = (char*)d->out_pre + n1 * 2;
-                if (d->bias) b.bias = d->bias + n1;
-                if (d->residual) b.residual = (const char*)d->residual + n1 * 2;
-                if (d->aux) b.aux = (const char*)d->aux + n1 * 2;
-                const int rc = gemm_bf16_one(&a, stream_, d->N, 0);
-                if (rc != APTAI_OK) return rc;
-                return gemm_bf16_one(&b, stream_, d->N, (int)n1);
-            }
-        }
-    }
-    return gemm_bf16_one(d, stream_, d ? d->N : 0, 0);
-}
-
-static int gemm_bf16_one(const aptai_gemm_desc* d, void* stream_, long hash_ld, int hash_n0) {
+// one launch (plus the slab reduction of a split-K / accumulate problem) of a planned descriptor
+static int launch_plan(const aptai_gemm_desc* d, const aptai_gemm_plan_info& p, void* stream_, long hash_ld, int hash_n0) {
     hipStream_t stream = (hipStream_t)stream_;
     GemmArgs g;
-    int nbatch = 1, nsplit = 1;
-    const int brc = build_args(d, g, nbatch, nsplit, stream_);
-    if (brc != APTAI_OK) return brc;
+    fill_args(d, p, stream_, g);
     g.hash_ld = hash_ld; g.hash_n0 = hash_n0;
+    if (gemm_knobs().epi_runtime) g.flags |= EPX_RUNTIME;
     const bool f32 = d->out_f32 != 0;
-    float* final_out = (float*)d->C;
-    // tile selection: the 256x256 deep-pipelined kernel when the grid still fills the chip, else 128x128 (2 blocks/CU)
-    int tile = d->tile;
-    if (tile == 0) {
-        static int env_tile = -1;
-        if (env_tile < 0) {
-            const char* e = getenv("APTAI_GEMM_TILE");
-            env_tile = e ? atoi(e) : 0;
+    if (!f32) epi_trace(g, p.tile);
+    const dim3 grid(g.tiles_m * g.tiles_n, p.nbatch, p.nsplit);
+    const int rc = with_layout("aptai_gemm_bf16", d->a_kmajor != 0, d->b_kmajor != 0, f32, [&](auto a, auto b, auto f) {
+        constexpr bool A = a(), B = b(), F = f();
+        switch (p.tile) {
+        case 64: return launch_kernel<gemm_kernel_m64<B, F>>({NTHREADS, SMEM_M64_BYTES, "gemm_kernel_m64"}, grid, stream, g);   // K-contiguous A only (plan_gemm)
+        case 192: return launch_kernel<gemm192_kernel<A, B, F>>({T3_THREADS, T3_SMEM, "gemm192_kernel"}, grid, stream, g);
+        case 256: return launch_kernel<gemm256_kernel<A, B, F>>({T2_THREADS, T2_SMEM, "gemm256_kernel"}, grid, stream, g);
+        case 257: return launch_gemm256_sk<A, B, F>(g, d->sk_workspace, stream);
+        case 448: return launch_gemm_t4(g, B, stream);
+        default: return launch_gemm128<A, B, F>(g, grid, stream);
         }
-        tile = env_tile;
-    }
-    if (tile == 0) {
-        // wave-quantisation model fitted to tools/gemm_bench*.py on MI355X: the 256-tile kernel sustains ~1.25x the
-        // 128-tile kernel per busy CU (1 block/CU, 256 slots) but needs the grid to fill whole rounds of 256 tiles;
-        // the 128-tile kernel runs 2 blocks/CU (512 slots).
-        const long t256 = ceil_div(d->M, T2_BM) * ceil_div(d->N, T2_BN) * nbatch * nsplit;
-        const long t128 = ceil_div(d->M, BM) * ceil_div(d->N, BN) * nbatch * nsplit;
-        const double e256 = (double)t256 / (double)(ceil_div(t256, 256) * 256);
-        const double e128 = (double)t128 / (double)(ceil_div(t128, 512) * 512);
-        static double f256 = -1.0;
-        if (f256 < 0) {
-            const char* e = getenv("APTAI_GEMM_F256");      // A/B knob for the 256-tile advantage factor (default 1.25)
-            f256 = e ? atof(e) : 1.25;
-        }
-        tile = (d->M >= 256 && d->N >= 256 && f256 * e256 > e128) ? 256 : 128;
-        // 128x192 tiles (one block per CU): measured faster than the 128-tile kernel only where the whole K-contiguous GEMM
-        // is ONE round of full tiles (8192 x 768: 16.9 vs 19.7 us at K = 768, 43.6 vs 51.2 us at K = 3072)
-        const long t192 = ceil_div(d->M, T3_BM) * ceil_div(d->N, T3_BN) * nbatch * nsplit;
-        // (round 3: also with a K-major B, the dgrads [8192] x 768 - since its LDS reads go through inline asm with counted waits the
-        //  192-tile kernel no longer drains its ring at every K-tile: 35.6 vs 38.6 us at K = 2304, 45.1 vs 49.0 us at K = 3072)
-        if (tile == 128 && !d->a_kmajor && d->M % T3_BM == 0 && d->N % T3_BN == 0 && t192 > 192 && t192 <= 256)
-            tile = 192;
-        // ... and where it is a whole number of rounds with a light epilogue (one block per CU leaves GELU / dropout arithmetic
-        // exposed: 8192 x 2304 x 768 with bias only 38.3 vs 40.7-42.8 us for the 64- / 128-row tiles, but 58.0 vs 52.5 us with
-        // bias + GELU + dropout + second output; tools/gemm_round.py)
-        const bool light_epi = !(d->flags & (APTAI_EPI_GELU | APTAI_EPI_DROPOUT | APTAI_EPI_DGELU)) && d->out_pre == nullptr;
-        const bool t192_rounds = tile == 128 && !d->a_kmajor && !d->b_kmajor && d->M % T3_BM == 0 && d->N % T3_BN == 0 && t192 % 256 == 0 &&
-                                 t192 <= 768 && d->K <= 1024 && light_epi && nbatch == 1 && nsplit == 1;
-        if (t192_rounds) tile = 192;
-        // 256 x 192 tiles (round 4, csrc/gemm_t4.hip; one block per CU, 8.9 staged bytes per kflop against 12.9 / 15.2): measured faster only
-        // where the whole K-contiguous GEMM is whole rounds of full tiles with a light epilogue - wav2vec2-large's q|k|v projection,
-        // [4096] x 3072 x 1024 = exactly 256 tiles: 26-28 us against 31-32 (128-row tiles) and 29-30 (vendor library), tools/gemm_t4_bench.py,
-        // profiles/r04_gemm_t4_bench.txt.  On the base model's [8192] x {2304, 3072} outputs it ties the 128-row kernels (43-44 us): every tile
-        // of this family sits on the same LDS / delivery balance, and its exposed epilogue loses with GELU / dropout.
-        const long t448 = ceil_div(d->M, 256) * ceil_div(d->N, 192);
-        if (!d->a_kmajor && !d->b_kmajor && !f32 && nbatch == 1 && nsplit == 1 && !d->accumulate && d->M % 256 == 0 && d->N % 192 == 0 &&
-            t448 % 256 == 0 && t448 <= 512 && light_epi && d->K >= 1024 && (tile == 128 || tile == 64 || tile == 256))
-            tile = 448;
-        // GEMMs that fill the 512 slots of the 128-tile kernel badly run as 64 x 128 tiles on 768 slots (3 blocks per CU): base
-        // dgrads [8192] x 768 (384 tiles -> 768: 49.1 vs 54.9 us at K = 3072, 38.0 vs 42.9 us at K = 2304), base QKV (1152 tiles =
-        // 2.25 rounds -> 2304 = 3 rounds), large [4096] x 1024 outputs (256 tiles -> 512: 13.7 vs 17.5 us at K = 1024, 42.4 vs
-        // 47.5 us at K = 4096, dgrads 41-52 vs 52-65 us).  Whole step: -0.25 ms from the multi-round cases alone.
-        // APTAI_GEMM_M64=0 disables the rule, =2 restricts it to single-round shapes (A/B).
-        static int m64 = -1;
-        if (m64 < 0) {
-            const char* e = getenv("APTAI_GEMM_M64");
-            m64 = e ? atoi(e) : 1;
-        }
-        const long t64 = ceil_div(d->M, 64) * ceil_div(d->N, BN) * nbatch * nsplit;
-        const double e64 = (double)t64 / (double)(ceil_div(t64, 768) * 768);
-        if (m64 && tile == 128 && !t192_rounds && !d->a_kmajor && d->M % 64 == 0 && (t128 <= 512 || m64 != 2) && e64 >= 1.2 * e128) tile = 64;
-    }
-    const bool sk_ok = d->sk_workspace != nullptr && d->sk_workspace_bytes >= sk_workspace_bytes() && nbatch == 1 && nsplit == 1 &&
-                       !d->accumulate && d->M >= T2_BM && d->N >= T2_BN;
-    if (tile == 257) APTAI_REQUIRE(sk_ok, "aptai_gemm_bf16: tile 257 (stream-K) needs sk_workspace (aptai_gemm_sk_workspace_bytes), no batching / "
-                                          "split-K / accumulate and M, N >= 256");
-    if (tile == 64 && d->a_kmajor) tile = 128;            // 64-row tiles need a K-contiguous A
-    // 2-D rasterisation (tile groups of 8 rows per XCD) for every kernel.  Rounds 2 and 3a kept the row-major walk for the 128- and 64-row
-    // kernels with a K-contiguous A, which then LOST 5-7 % to the raster (FFN1 forward 71.5 -> 76.7 us) while it cut their fabric-side
-    // re-reads (FFN1: 129 MB fetched for 17 MB of operands); with the per-flag-word epilogues the balance is the other way: per forced
-    // 128-row tile FFN1 forward 61.5-64.2 -> 59.3 us, FFN2 dgrad 50.4 -> 48.8 us, the layer's ten bf16-output GEMMs 388-392 -> 382-383 us
-    // (tools/step_gemm_tiles.py, APTAI_GEMM_RASTER = -1 / 4 / 8 / 16 in one call; 64-row tiles 425 -> 416 us).  APTAI_GEMM_RASTER=0 = row-major.
-    if (g.raster_gm < 0) g.raster_gm = 8;
-    static const bool epi_runtime = getenv("APTAI_EPI_RUNTIME") && atoi(getenv("APTAI_EPI_RUNTIME")) != 0;
-    if (epi_runtime) g.flags |= EPX_RUNTIME;
-    if (!f32) epi_trace(g, tile);
-    int rc;
-    if (tile == 257) {
-        if (!d->a_kmajor && !d->b_kmajor) rc = f32 ? launch_gemm256_sk<false, false, true>(g, d->sk_workspace, stream) : launch_gemm256_sk<false, false, false>(g, d->sk_workspace, stream);
-        else if (!d->a_kmajor && d->b_kmajor) rc = f32 ? launch_gemm256_sk<false, true, true>(g, d->sk_workspace, stream) : launch_gemm256_sk<false, true, false>(g, d->sk_workspace, stream);
-        else if (d->a_kmajor && d->b_kmajor) rc = f32 ? launch_gemm256_sk<true, true, true>(g, d->sk_workspace, stream) : launch_gemm256_sk<true, true, false>(g, d->sk_workspace, stream);
-        else APTAI_FAIL(APTAI_ERR_INVALID, "aptai_gemm_bf16: A K-major with B K-contiguous is not built");
-    } else
-    if (tile == 64) {
-        if (!d->b_kmajor) rc = f32 ? launch_gemm_m64<false, true>(g, nbatch, nsplit, stream) : launch_gemm_m64<false, false>(g, nbatch, nsplit, stream);
-        else rc = f32 ? launch_gemm_m64<true, true>(g, nbatch, nsplit, stream) : launch_gemm_m64<true, false>(g, nbatch, nsplit, stream);
-    } else
-    if (tile == 448) {
-        APTAI_REQUIRE(!f32 && !d->a_kmajor && nbatch == 1 && nsplit == 1 && !d->accumulate,
-                      "aptai_gemm_bf16: tile 448 (256 x 192) is built for bf16 output, K-contiguous A, no batching / split-K");
-        rc = launch_gemm_t4(g, d->b_kmajor != 0, stream);
-    } else
-    if (tile == 192) {
-        if (!d->a_kmajor && !d->b_kmajor) rc = f32 ? launch_gemm192<false, false, true>(g, nbatch, nsplit, stream) : launch_gemm192<false, false, false>(g, nbatch, nsplit, stream);
-        else if (!d->a_kmajor && d->b_kmajor) rc = f32 ? launch_gemm192<false, true, true>(g, nbatch, nsplit, stream) : launch_gemm192<false, true, false>(g, nbatch, nsplit, stream);
-        else if (d->a_kmajor && d->b_kmajor) rc = f32 ? launch_gemm192<true, true, true>(g, nbatch, nsplit, stream) : launch_gemm192<true, true, false>(g, nbatch, nsplit, stream);
-        else APTAI_FAIL(APTAI_ERR_INVALID, "aptai_gemm_bf16: A K-major with B K-contiguous is not built");
-    } else
-    if (tile == 256) {
-        if (!d->a_kmajor && !d->b_kmajor) rc = f32 ? launch_gemm256<false, false, true>(g, nbatch, nsplit, stream) : launch_gemm256<false, false, false>(g, nbatch, nsplit, stream);
-        else if (!d->a_kmajor && d->b_kmajor) rc = f32 ? launch_gemm256<false, true, true>(g, nbatch, nsplit, stream) : launch_gemm256<false, true, false>(g, nbatch, nsplit, stream);
-        else if (d->a_kmajor && d->b_kmajor) rc = f32 ? launch_gemm256<true, true, true>(g, nbatch, nsplit, stream) : launch_gemm256<true, true, false>(g, nbatch, nsplit, stream);
-        else APTAI_FAIL(APTAI_ERR_INVALID, "aptai_gemm_bf16: A K-major with B K-contiguous is not built");
-    } else
-    if (!d->a_kmajor && !d->b_kmajor) rc = f32 ? launch_gemm<false, false, true>(g, nbatch, nsplit, stream) : launch_gemm<false, false, false>(g, nbatch, nsplit, stream);
-    else if (!d->a_kmajor && d->b_kmajor) rc = f32 ? launch_gemm<false, true, true>(g, nbatch, nsplit, stream) : launch_gemm<false, true, false>(g, nbatch, nsplit, stream);
-    else if (d->a_kmajor && d->b_kmajor) rc = f32 ? launch_gemm<true, true, true>(g, nbatch, nsplit, stream) : launch_gemm<true, true, false>(g, nbatch, nsplit, stream);
-    else APTAI_FAIL(APTAI_ERR_INVALID, "aptai_gemm_bf16: A K-major with B K-contiguous is not built");
+    });
     if (rc != APTAI_OK) return rc;
-    if (f32 && (nsplit > 1 || d->accumulate)) {
+    if (f32 && (p.nsplit > 1 || d->accumulate)) {
         const long n4 = (long)d->M * d->N / 4;
         int blocks = (int)(n4 / 256 < 2048 ? (n4 + 255) / 256 : 2048);
-        APTAI_LAUNCH(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, stream, (const float*)d->workspace, final_out,
-                           n4, g.slab_stride / 4, nsplit, d->accumulate ? 1 : 0);
+        APTAI_LAUNCH(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, stream, (const float*)d->workspace, (float*)d->C,
+                           n4, g.slab_stride / 4, p.nsplit, d->accumulate ? 1 : 0);
         APTAI_CHECK_LAUNCH("splitk_reduce_kernel");
     }
     return APTAI_OK;
 }
+
+// hash_ld / hash_n0: the two parts of a column split (splitn_column) draw the dropout masks of the whole output
+static int gemm_bf16_run(const aptai_gemm_desc* d, void* stream, long hash_ld, int hash_n0) {
+    aptai_gemm_plan_info p;
+    const int rc = aptai_gemm_plan(d, &p);
+    if (rc != APTAI_OK) return rc;
+    if (p.split_n == 0) return launch_plan(d, p, stream, hash_ld, hash_n0);
+    const long n1 = p.split_n;
+    aptai_gemm_desc a = *d, b = *d;
+    a.N = n1; a.tile = 256;
+    b.N = d->N - n1; b.tile = 128;
+    b.B = (const char*)d->B + (d->b_kmajor ? n1 * 2 : n1 * d->ldb * 2);
+    b.C = (char*)d->C + n1 * 2;
+    if (d->out_pre) b.out_pre = (char*)d->out_pre + n1 * 2;
+    if (d->bias) b.bias = d->bias + n1;
+    if (d->residual) b.residual = (const char*)d->residual + n1 * 2;
+    if (d->aux) b.aux = (const char*)d->aux + n1 * 2;
+    const int rca = gemm_bf16_run(&a, stream, hash_ld, hash_n0);
+    return rca != APTAI_OK ? rca : gemm_bf16_run(&b, stream, hash_ld, hash_n0 + (int)n1);
+}
+extern "C" int aptai_gemm_bf16(const aptai_gemm_desc* d, void* stream) { return gemm_bf16_run(d, stream, d ? d->N : 0, 0); }
 
 extern "C" int aptai_gemm_bf16_grouped(const aptai_gemm_desc* descs, int n, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
@@ -1751,11 +1725,15 @@ extern "C" int aptai_gemm_bf16_grouped(const aptai_gemm_desc* descs, int n, void
     int total = 0;
     for (int i = 0; i < n; ++i) {
         const aptai_gemm_desc* d = descs + i;
-        int nbatch = 1, nsplit = 1;
-        const int brc = build_args(d, ga.p[i], nbatch, nsplit, stream_);
+        const int brc = validate_desc(d);
         if (brc != APTAI_OK) return brc;
-        if (ga.p[i].raster_gm < 0) ga.p[i].raster_gm = (d->a_kmajor && d->b_kmajor) ? 8 : 0;     // see aptai_gemm_bf16
-        APTAI_REQUIRE(nbatch == 1 && nsplit == 1 && !d->accumulate, "aptai_gemm_bf16_grouped: problem %d: no batching, split-K or accumulate", i);
+        // 128-row tiles; rastered only where both operands are K-major (see plan_gemm)
+        aptai_gemm_plan_info p = {};
+        p.tile = 128;
+        launch_shape(*d, p.nbatch, p.nsplit, p.ktiles_per_split);
+        p.raster_gm = raster_group(gemm_knobs(), (d->a_kmajor && d->b_kmajor) ? 8 : 0);
+        fill_args(d, p, stream_, ga.p[i]);
+        APTAI_REQUIRE(p.nbatch == 1 && p.nsplit == 1 && !d->accumulate, "aptai_gemm_bf16_grouped: problem %d: no batching, split-K or accumulate", i);
         APTAI_REQUIRE(d->a_kmajor == descs[0].a_kmajor && d->b_kmajor == descs[0].b_kmajor && (d->out_f32 != 0) == (descs[0].out_f32 != 0),
                       "aptai_gemm_bf16_grouped: problem %d: all problems must share the operand layout and output type", i);
         total += ga.p[i].tiles_m * ga.p[i].tiles_n;
@@ -1763,25 +1741,9 @@ extern "C" int aptai_gemm_bf16_grouped(const aptai_gemm_desc* descs, int n, void
     }
     ga.n = n;
     ga.total = total;
-    const bool f32 = descs[0].out_f32 != 0, akm = descs[0].a_kmajor != 0, bkm = descs[0].b_kmajor != 0;
-    APTAI_REQUIRE(!(akm && !bkm), "aptai_gemm_bf16_grouped: A K-major with B K-contiguous is not built");
-#define APTAI_GROUPED(AK, BK_, F)                                                                                      \
-    do {                                                                                                              \
-        auto kern = gemm_grouped_kernel<AK, BK_, F>;                                                                  \
-        constexpr int smem = smem_for<AK, BK_>();                                                                     \
-        static bool attr_set = false;                                                                                 \
-        if (!attr_set) {                                                                                              \
-            (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem);                  \
-            attr_set = true;                                                                                          \
-        }                                                                                                             \
-        APTAI_LAUNCH(kern, dim3(total), dim3(NTHREADS), smem, stream, ga);                                            \
-    } while (0)
-    if (!akm && !bkm) { if (f32) APTAI_GROUPED(false, false, true); else APTAI_GROUPED(false, false, false); }
-    else if (!akm && bkm) { if (f32) APTAI_GROUPED(false, true, true); else APTAI_GROUPED(false, true, false); }
-    else { if (f32) APTAI_GROUPED(true, true, true); else APTAI_GROUPED(true, true, false); }
-#undef APTAI_GROUPED
-    APTAI_CHECK_LAUNCH("gemm_grouped_kernel");
-    return APTAI_OK;
+    return with_layout("aptai_gemm_bf16_grouped", descs[0].a_kmajor != 0, descs[0].b_kmajor != 0, descs[0].out_f32 != 0, [&](auto a, auto b, auto f) {
+        return launch_kernel<gemm_grouped_kernel<a(), b(), f()>>({NTHREADS, smem_for<a(), b()>(), "gemm_grouped_kernel"}, dim3(total), stream, ga);
+    });
 }
 
 extern "C" int64_t aptai_gemm_sk_workspace_bytes(void) { return sk_workspace_bytes(); }

@@ -1,5 +1,5 @@
 // Shared pieces of the bf16 MFMA GEMM family (gemm.hip, gemm_t4.hip): the kernel argument block, the per-flag-word epilogue, LDS-DMA
-// staging sources, fragment reads, tile-index remaps.  Device code only; everything is forceinline / constexpr / templates.
+// staging sources, fragment reads, tile-index remaps, and (at the end) the host launcher.  Everything is forceinline / constexpr / templates.
 #pragma once
 #include "common.h"
 
@@ -315,7 +315,26 @@ __device__ __forceinline__ void split_out_store(const GemmArgs& g, const int fla
     }
 }
 
-// 256 x 192 tile kernel (gemm_t4.hip): bf16 output, K-contiguous A, B K-contiguous or K-major; no batching / split-K
-int launch_gemm_t4(GemmArgs g, bool b_km, hipStream_t stream);
+// ---- host side: the one launcher of the family.  Kern is a kernel instantiation, so the dynamic-LDS attribute is set once per
+// instantiation; `args` are the kernel's own arguments (GemmArgs, plus SkArgs / GroupArgs where the kernel takes them).
+struct KernelLaunch {
+    int threads, smem;          // workgroup size, dynamic LDS bytes
+    const char* name;           // for the error text
+};
+template <auto Kern, class... Args>
+int launch_kernel(const KernelLaunch& k, dim3 grid, hipStream_t stream, const Args&... args) {
+    static bool attr_set = false;
+    if (!attr_set) {
+        (void)hipFuncSetAttribute((const void*)Kern, hipFuncAttributeMaxDynamicSharedMemorySize, k.smem);
+        attr_set = true;
+    }
+    APTAI_LAUNCH(Kern, grid, dim3(k.threads), k.smem, stream, args...);
+    APTAI_CHECK_LAUNCH(k.name);
+    return APTAI_OK;
+}
+
+// 256 x 192 tile kernel (gemm_t4.hip): bf16 output, K-contiguous A, B K-contiguous or K-major; no batching / split-K.
+// g.tiles_m / g.tiles_n count 256 x 192 tiles.
+int launch_gemm_t4(const GemmArgs& g, bool b_km, hipStream_t stream);
 
 }  // namespace aptai_gemm

@@ -363,29 +363,10 @@ __global__ __launch_bounds__(T4_THREADS, 2) void gemm_t4_kernel(GemmArgs g) {
 
 namespace aptai_gemm {
 
-int launch_gemm_t4(GemmArgs g, bool b_km, hipStream_t stream) {
-    g.tiles_m = (int)((g.M + T4_BM - 1) / T4_BM);
-    g.tiles_n = (int)((g.N + T4_BN - 1) / T4_BN);
-    dim3 grid(g.tiles_m * g.tiles_n, 1, 1);
-    if (!b_km) {
-        auto kern = gemm_t4_kernel<false>;
-        static bool attr_set = false;
-        if (!attr_set) {
-            (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, t4_smem<false>());
-            attr_set = true;
-        }
-        APTAI_LAUNCH(kern, grid, dim3(T4_THREADS), t4_smem<false>(), stream, g);
-    } else {
-        auto kern = gemm_t4_kernel<true>;
-        static bool attr_set = false;
-        if (!attr_set) {
-            (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, t4_smem<true>());
-            attr_set = true;
-        }
-        APTAI_LAUNCH(kern, grid, dim3(T4_THREADS), t4_smem<true>(), stream, g);
-    }
-    APTAI_CHECK_LAUNCH("gemm_t4_kernel");
-    return APTAI_OK;
+int launch_gemm_t4(const GemmArgs& g, bool b_km, hipStream_t stream) {
+    const dim3 grid(g.tiles_m * g.tiles_n, 1, 1);
+    return b_km ? launch_kernel<gemm_t4_kernel<true>>({T4_THREADS, t4_smem<true>(), "gemm_t4_kernel"}, grid, stream, g)
+                : launch_kernel<gemm_t4_kernel<false>>({T4_THREADS, t4_smem<false>(), "gemm_t4_kernel"}, grid, stream, g);
 }
 
 }  // namespace aptai_gemm

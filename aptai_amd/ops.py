@@ -31,6 +31,18 @@ class GemmDesc(ctypes.Structure):
                 ("sk_workspace", c_void_p), ("sk_workspace_bytes", c_i64), ("split_out_pieces", c_int), ("split_out_bcol", c_int)]
 
 
+class GemmPlanInfo(ctypes.Structure):
+    _fields_ = [("tile", c_int), ("nbatch", c_int), ("nsplit", c_int), ("ktiles_per_split", c_int), ("raster_gm", c_int), ("split_n", c_i64)]
+
+
+def gemm_plan(d: GemmDesc) -> GemmPlanInfo:
+    """What aptai_gemm_bf16 would launch for `d` in this process (aptai_gemm_plan: host only, no device needed); raises where
+    aptai_gemm_bf16 would refuse the descriptor, with the same text."""
+    info = GemmPlanInfo()
+    _lib.check(_lib.lib().aptai_gemm_plan(ctypes.byref(d), ctypes.byref(info)), "aptai_gemm_plan")
+    return info
+
+
 TILE_STREAMK = 257
 _SK_WS = {}
 

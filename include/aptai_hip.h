@@ -99,8 +99,8 @@ typedef struct {
                                        q|k|v projection (HF:495-498) hands the attention kernels Q already multiplied by
                                        head_dim^-0.5 * log2(e) (HF:522 applies the scaling to the projected query too), rounded once */
     void* sk_workspace;             /* optional, aptai_gemm_sk_workspace_bytes() bytes, ZEROED ONCE by the caller and then owned by ONE stream:
-                                       fp32 partial-tile slabs + ready flags (self-cleaning) + status word of the stream-K kernel.  With it the
-                                       auto rule may pick the stream-K form; without it tile 257 is refused and auto never picks it */
+                                       fp32 partial-tile slabs + ready flags (self-cleaning) + status word of the stream-K kernel.  Tile 257 is
+                                       opt-in only: without the workspace it is refused, and the auto rule never picks it */
     int64_t sk_workspace_bytes;
     int split_out_pieces;           /* with APTAI_EPI_SPLIT_OUT: 3 or 6 */
     int split_out_bcol;             /* with APTAI_EPI_SPLIT_OUT: output columns n >= split_out_bcol are written in the WEIGHT-side piece order
@@ -115,6 +115,17 @@ int aptai_gemm_bf16(const aptai_gemm_desc* desc, void* stream);
  * their full-K tiles fill the 256 CUs once, where each alone needs split-K slabs and a reduce pass.  A bias gradient is
  * the problem M = 8, A = ones[K][8] (K-major), row 0 of the [8][N] fp32 result. */
 int aptai_gemm_bf16_grouped(const aptai_gemm_desc* descs, int n, void* stream);
+/* What aptai_gemm_bf16 would launch for `desc` in this process (environment knobs included), without touching the device: the same
+ * validation and the same planner, so a refused descriptor returns the status and aptai_last_error() text of aptai_gemm_bf16. */
+typedef struct {
+    int tile;                       /* kernel, as in aptai_gemm_desc.tile (never 0) */
+    int nbatch, nsplit;             /* grid y (batches) and z (split-K slabs as launched) */
+    int ktiles_per_split;           /* 64-deep K-tiles per slab */
+    int raster_gm;                  /* tile rows per raster group, 0 = row-major walk */
+    int64_t split_n;                /* 0 = one launch; else two launches (APTAI_GEMM_SPLITN=1): columns [0, split_n) as `tile` (256),
+                                       columns [split_n, N) as 128-row tiles */
+} aptai_gemm_plan_info;
+int aptai_gemm_plan(const aptai_gemm_desc* desc, aptai_gemm_plan_info* out);
 int64_t aptai_gemm_workspace_bytes(int64_t M, int64_t N, int split_k);
 /* Stream-K workspace (independent of the problem: one 256 x 256 fp32 slab per CU + flags) and its status word: non-zero after a
  * launch in which a bounded wait for another workgroup's slab gave up (that launch's output is then incomplete; never a hang).
