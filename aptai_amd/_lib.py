@@ -104,6 +104,11 @@ ARGTYPES = {
     "aptai_attention_exact_fwd": [_P, _I64, _P, _P, _I64, _I64, _I64, _I64, _I64, _I, _F, _P],
     "aptai_conv0_fwd_f32": [_P, _I64, _I64, _P, _P, _P, _P, _I, _F, _P, _I64, _I64, _P, _P],
     "aptai_conv0_fwd_split": [_P, _I64, _I64, _P, _P, _P, _P, _I, _F, _P, _I, _I64, _I64, _P, _P],
+    "aptai_eval_tv_scores": [_P, _I64, _I64, _P, _I64, _I64, _P, _I64, _I64, _I64, _P, _P, _P],
+    "aptai_eval_frame_scores": [_P, _I64, _P, _I64, _P, _I64, _I64, _P, _P],
+    "aptai_eval_boundary_counts": [_P, _I64, _P, _P, _I64, _P, ctypes.c_double, _I64, _P, _P],
+    "aptai_eval_collapse_runs": [_P, _I64, _P, _I64, _P, _I64, _P, _P],
+    "aptai_eval_edit_distance": [_P, _I64, _P, _P, _I64, _P, _I64, _P, _P],
     "aptai_device_check": [ctypes.c_char_p, _I],
     "aptai_set_seed_salt": [_P, _P],
     "aptai_set_frame_bounds": [_P, _P],

@@ -395,12 +395,18 @@ class Force_APTAI(nn.Module):
         return given, fl, n, table
 
     def forward(self, epoch, audio_inputs, audio_lengths, phoneme_labels, phn_frames_49hz, LA, LP, JA, TTCL, TTCD, TMCL, TMCD,
-                TBCL, TBCD, _phn_pred_list=None, _ac_override=None, _prefetch_next=None):
+                TBCL, TBCD, _phn_pred_list=None, _ac_override=None, _prefetch_next=None, _device_outputs=False):
         """`_prefetch_next = (audio_inputs, audio_lengths)` of the batch the NEXT call will receive (the same tensor objects)
         starts its frozen-encoder pass on a side stream beside this call's heads (see prefetch)."""
         tv_targets = torch.stack([LA, LP, JA, TTCL, TTCD, TMCL, TMCD, TBCL, TBCD], dim=-1).float()
         res, g, dec = self._run(audio_inputs, audio_lengths, tv_targets, _phn_pred_list, _ac_override, _prefetch_next)
         loss, tv_loss, align_loss, tvs, frame_phns = res[:5]
+        if _device_outputs:
+            # private route of the device-resident evaluation (train_force_aptai._device_eval): the tensors `_run` already holds,
+            # no lists and no transfer; the caller folds the checks of `_lists` into its own single read
+            ids, nlen, frame_lens, _ = dec
+            return {'loss': loss, 'tv_loss': tv_loss, 'align_loss': align_loss, 'tvs_pred': tvs, 'frame_phns': frame_phns,
+                    'ctc_ids': ids, 'ctc_lens': nlen, 'frame_lens': frame_lens}
         phn_pred_list, frame_seq_lens, _, _ = self._lists(dec)
         fp = frame_phns.cpu().numpy()                                  # ONE transfer (reference: B*T .cpu() calls)
         pred_frame_phns = [fp[b, :frame_seq_lens[b]].tolist() for b in range(g.B)]

@@ -852,6 +852,83 @@ def ctc_viterbi(logits, ldl, rows_per_b, targets_i32, input_lens_i32, target_len
     return frame_token, spans, score, token_score
 
 
+# ----------------------------------------------------------------------------- evaluation metrics (csrc/eval.hip)
+EVAL_EDIT_MAX_LANE_SIDE = 2048          # APTAI_EVAL_EDIT_MAX_LANE_SIDE
+
+
+def _eval_lens(lens, B, name):
+    if lens.dtype != torch.int32 or lens.numel() != B or not lens.is_contiguous():
+        raise _lib.AptaiHipError(f"{name}: lengths must be a contiguous int32 device vector of {B} entries")
+
+
+def eval_tv_scores(gt, ldg, rows_g, pred, ldp, rows_p, lens_i32, B, max_len, C):
+    """(rmse, pcc) fp64 [B][C] of fp32 trajectories at (b*rows + t)*ld + c - see aptai_eval_tv_scores.  No synchronisation."""
+    _dev(gt, pred, lens_i32)
+    if gt.dtype != torch.float32 or pred.dtype != torch.float32:
+        raise _lib.AptaiHipError("eval_tv_scores: fp32 trajectories expected")
+    _eval_lens(lens_i32, B, "eval_tv_scores")
+    rmse = torch.empty((B, C), device=gt.device, dtype=torch.float64)
+    pcc = torch.empty((B, C), device=gt.device, dtype=torch.float64)
+    _lib.call("aptai_eval_tv_scores", gt.data_ptr(), ldg, rows_g, pred.data_ptr(), ldp, rows_p, lens_i32.data_ptr(), B, max_len, C,
+              rmse.data_ptr(), pcc.data_ptr(), _stream())
+    return rmse, pcc
+
+
+def eval_frame_scores(gt_i64, ldg, pred_i64, ldp, lens_i32, B, max_len):
+    """int32 [B][2] = {frames, frames with gt == pred} - see aptai_eval_frame_scores."""
+    _dev(gt_i64, pred_i64, lens_i32)
+    if gt_i64.dtype != torch.int64 or pred_i64.dtype != torch.int64:
+        raise _lib.AptaiHipError("eval_frame_scores: int64 frame labels expected")
+    _eval_lens(lens_i32, B, "eval_frame_scores")
+    out = torch.empty((B, 2), device=gt_i64.device, dtype=torch.int32)
+    _lib.call("aptai_eval_frame_scores", gt_i64.data_ptr(), ldg, pred_i64.data_ptr(), ldp, lens_i32.data_ptr(), B, max_len,
+              out.data_ptr(), _stream())
+    return out
+
+
+def eval_boundary_counts(y_f64, ldy, ny_i32, yhat_f64, ldh, nh_i32, B, tolerance):
+    """int32 [B][2] = {precision_counter, recall_counter} of get_stats - see aptai_eval_boundary_counts."""
+    _dev(y_f64, yhat_f64, ny_i32, nh_i32)
+    if y_f64.dtype != torch.float64 or yhat_f64.dtype != torch.float64:
+        raise _lib.AptaiHipError("eval_boundary_counts: fp64 boundary values expected")
+    _eval_lens(ny_i32, B, "eval_boundary_counts")
+    _eval_lens(nh_i32, B, "eval_boundary_counts")
+    out = torch.empty((B, 2), device=y_f64.device, dtype=torch.int32)
+    _lib.call("aptai_eval_boundary_counts", y_f64.data_ptr(), ldy, ny_i32.data_ptr(), yhat_f64.data_ptr(), ldh, nh_i32.data_ptr(),
+              float(tolerance), B, out.data_ptr(), _stream())
+    return out
+
+
+def eval_collapse_runs(x_i64, ld, lens_i32, B, ldo=None):
+    """(out int32 [B][ldo] zero-padded, n int32 [B]): runs of equal labels collapsed - see aptai_eval_collapse_runs."""
+    _dev(x_i64, lens_i32)
+    if x_i64.dtype != torch.int64:
+        raise _lib.AptaiHipError("eval_collapse_runs: int64 frame labels expected")
+    _eval_lens(lens_i32, B, "eval_collapse_runs")
+    ldo = int(ld if ldo is None else ldo)
+    out = torch.empty((B, ldo), device=x_i64.device, dtype=torch.int32)
+    n = torch.empty(B, device=x_i64.device, dtype=torch.int32)
+    _lib.call("aptai_eval_collapse_runs", x_i64.data_ptr(), ld, lens_i32.data_ptr(), B, out.data_ptr(), ldo, n.data_ptr(), _stream())
+    return out, n
+
+
+def eval_edit_distance(a_i32, lda, a_lens_i32, b_i32, ldb, b_lens_i32, B):
+    """Levenshtein distance int32 [B] of B pairs of int32 rows - see aptai_eval_edit_distance.  The kernel keeps `a` in registers
+    (at most EVAL_EDIT_MAX_LANE_SIDE symbols per row): the narrower side goes there, the distance is symmetric.  Two rows both
+    wider than that are refused by the library, with both widths in the message."""
+    _dev(a_i32, b_i32, a_lens_i32, b_lens_i32)
+    if a_i32.dtype != torch.int32 or b_i32.dtype != torch.int32:
+        raise _lib.AptaiHipError("eval_edit_distance: int32 symbols expected")
+    _eval_lens(a_lens_i32, B, "eval_edit_distance")
+    _eval_lens(b_lens_i32, B, "eval_edit_distance")
+    if ldb < lda:
+        a_i32, lda, a_lens_i32, b_i32, ldb, b_lens_i32 = b_i32, ldb, b_lens_i32, a_i32, lda, a_lens_i32
+    dist = torch.empty(B, device=a_i32.device, dtype=torch.int32)
+    _lib.call("aptai_eval_edit_distance", a_i32.data_ptr(), lda, a_lens_i32.data_ptr(), b_i32.data_ptr(), ldb, b_lens_i32.data_ptr(), B,
+              dist.data_ptr(), _stream())
+    return dist
+
+
 # ----------------------------------------------------------------------------- Force_APTAI heads (fp32)
 _SCRATCH32 = {}
 

@@ -97,7 +97,8 @@ def train(cfg, model, optimizer, lr_scheduler, train_dataloader, valid_dataloade
         if runner is not None:
             runner.suspend()             # the eager validation below rebuilds its weight copies; the captured buckets stay
         model.eval()
-        val_logs = validate(model, cfg.device, cfg.vocab, epoch, getattr(cfg, "exp_dir", None), test_spk, valid_dataloader)
+        val_logs = validate(model, cfg.device, cfg.vocab, epoch, getattr(cfg, "exp_dir", None), test_spk, valid_dataloader,
+                            device_metrics=getattr(cfg, "device_metrics", False))
         better = (eval_target is None
                   or (cfg.target_metric_bigger_better and eval_target <= val_logs[cfg.target_metric])
                   or (not cfg.target_metric_bigger_better and eval_target >= val_logs[cfg.target_metric]))
@@ -114,9 +115,31 @@ def train(cfg, model, optimizer, lr_scheduler, train_dataloader, valid_dataloade
     return history
 
 
-def validate(model, device, vocab, epoch, exp_dir, test_spk, val_dl, log_step=100) -> Dict[str, float]:
+def _device_eval(model, device, epoch, dl, acc):
+    """The evaluation pass of validate()/test() with `device_metrics=True`: the same forward, the metrics of every utterance of
+    the batch computed by the kernels of aptai_amd.device_metrics and left on the device (no blocking call per batch).  Any batch
+    size: frame counts come from `audio_lengths` through the encoder's length formula."""
+    from . import device_metrics as dm
+    for batch_x in dl:
+        with torch.no_grad():
+            batch_x = {k: v.to(device) for k, v in batch_x.items()}
+            tvs_gt = _stack_gt(batch_x)
+            outputs = model(epoch, **batch_x)
+        tvs_pred = outputs["tvs_pred"]
+        lens = dm.frame_lengths(model.wav2vec2, batch_x["audio_lengths"], tvs_pred.shape[1])
+        acc.add_loss(outputs["loss"])
+        acc.add_tv(tvs_gt, tvs_pred, lens)
+        acc.add_frames(batch_x["phn_frames_49hz"], outputs["phn_fc_pred"], lens)
+    return acc.result()
+
+
+def validate(model, device, vocab, epoch, exp_dir, test_spk, val_dl, log_step=100, device_metrics=False) -> Dict[str, float]:
     """train/train_aptai.py:533-652, batch size 1.  Reproduces the reference as written, including its two quirks: the ground
-    truth stack lists TTCD in the TMCD slot (:557-560) and `get_stats` receives frame label sequences, not boundary times."""
+    truth stack lists TTCD in the TMCD slot (:557-560) and `get_stats` receives frame label sequences, not boundary times.
+    `device_metrics=True` (opt-in) computes the same entries with aptai_amd.device_metrics: one device->host transfer per call."""
+    if device_metrics:
+        from .device_metrics import EvalAccumulator
+        return _device_eval(model, device, epoch, val_dl, EvalAccumulator("val", per="frames_rounded"))
     val_losses, val_rmses, val_pccs, val_overlaps = [], [], [], []
     val_ps, val_rs, val_f1s, val_rvals, edit_d, n_phn = [], [], [], [], [], []
     total_frames = corr_frames = 0
@@ -181,11 +204,15 @@ def _tv_test_summary(rate, rmse_tvs, pcc_tvs, with_std=False):
     return out
 
 
-def test(model, device, vocab, exp_dir, test_spk, test_dl, rate, log_step=100, num_epochs=0) -> Dict[str, float]:
+def test(model, device, vocab, exp_dir, test_spk, test_dl, rate, log_step=100, num_epochs=0, device_metrics=False) -> Dict[str, float]:
     """train/train_aptai.py:655-850, batch size 1: per-track RMSE / PCC means, FER, frame-grouped PER, overlap, boundary scores,
     keyed `test_{rate}_...` with rate in {'F', 'N'} (fast / normal speaking rate splits of the corpus).  `num_epochs` stands for
     the module-global `cfg.num_epochs` the reference passes as the epoch argument (:709)."""
     assert rate in ["F", "N"]
+    if device_metrics:
+        from .device_metrics import EvalAccumulator
+        model.eval()
+        return _device_eval(model, device, num_epochs, test_dl, EvalAccumulator("test", rate=rate, per="frames"))
     names = hostlogic.TV_NAMES
     rmse_tvs, pcc_tvs = {n: [] for n in names}, {n: [] for n in names}
     overlaps, ps, rs, f1s, rvals, edit_d, n_phn = [], [], [], [], [], [], []
@@ -224,7 +251,7 @@ def default_cfg(**kw):
     cfg = SimpleNamespace(device="cuda", num_epochs=2, batch_size=16, learning_rate=1e-5, adam_beta1=0.9, adam_beta2=0.999,
                           adam_epsilon=1e-8, adam_weight_decay=0.0, num_warmup_epochs=10, num_static_epochs=30, lr_decay=0.96,
                           target_metric="val_mean_rmse", target_metric_bigger_better=False, graphed=False, exp_dir=None,
-                          vocab={f"p{i}": i for i in range(VOCAB_SIZE)}, cache_dir=None)
+                          vocab={f"p{i}": i for i in range(VOCAB_SIZE)}, cache_dir=None, device_metrics=False)
     cfg.__dict__.update(kw)
     return cfg
 

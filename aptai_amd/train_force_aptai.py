@@ -89,7 +89,8 @@ def train(cfg, model, optimizer, lr_scheduler, train_dataloader, valid_dataloade
                 f"lr: {optimizer.param_groups[0]['lr']:.6f}")
         lr_scheduler.step()
         model.eval()
-        val_logs = validate(model, cfg.device, cfg.vocab, epoch, getattr(cfg, "exp_dir", None), test_spk, valid_dataloader)
+        val_logs = validate(model, cfg.device, cfg.vocab, epoch, getattr(cfg, "exp_dir", None), test_spk, valid_dataloader,
+                            device_metrics=getattr(cfg, "device_metrics", False))
         better = (eval_target is None
                   or (cfg.target_metric_bigger_better and eval_target <= val_logs[cfg.target_metric])
                   or (not cfg.target_metric_bigger_better and eval_target >= val_logs[cfg.target_metric]))
@@ -120,8 +121,34 @@ def _one_file(model, device, epoch, batch_x):
     return outputs, tvs_gt, tvs_pred, ed, n, _eval_frames(batch_x["phn_frames_49hz"], pred_frames)
 
 
-def validate(model, device, vocab, epoch, exp_dir, test_spk, val_dl, log_step=100) -> Dict[str, float]:
-    """train/train_force_aptai.py:533-652, batch size 1 (incl. the TTCD-twice ground-truth stack)."""
+def _device_eval(model, device, epoch, dl, acc):
+    """validate()/test() with `device_metrics=True`: Force_APTAI's device-output route (no Python lists), every metric through
+    aptai_amd.device_metrics.  The decoded-length check and the BiLSTM status words `_lists` reads per step are accumulated on
+    the device and checked once in `acc.result()`."""
+    from . import device_metrics as dm
+    acc.max_phonemes = model.max_phn_seq_len
+    for batch_x in dl:
+        with torch.no_grad():
+            batch_x = {k: v.to(device) for k, v in batch_x.items()}
+            tvs_gt = _stack_gt(batch_x)
+            outputs = model(epoch, **batch_x, _device_outputs=True)
+        lens = outputs["frame_lens"]
+        acc.add_loss(outputs["loss"])
+        acc.add_tv(tvs_gt, outputs["tvs_pred"], lens)
+        labels = batch_x["phoneme_labels"]
+        acc.add_edit(labels, dm.label_lengths(labels), outputs["ctc_ids"], outputs["ctc_lens"])
+        acc.add_frames(batch_x["phn_frames_49hz"], outputs["frame_phns"], lens)
+        acc.add_decoded_lengths(outputs["ctc_lens"])
+        acc.add_lstm_status(outputs["frame_phns"].device)
+    return acc.result()
+
+
+def validate(model, device, vocab, epoch, exp_dir, test_spk, val_dl, log_step=100, device_metrics=False) -> Dict[str, float]:
+    """train/train_force_aptai.py:533-652, batch size 1 (incl. the TTCD-twice ground-truth stack).  `device_metrics=True`
+    (opt-in): the same entries from aptai_amd.device_metrics, one device->host transfer per call."""
+    if device_metrics:
+        from .device_metrics import EvalAccumulator
+        return _device_eval(model, device, epoch, val_dl, EvalAccumulator("val", per="edit"))
     val_losses, val_rmses, val_pccs, val_overlaps = [], [], [], []
     val_ps, val_rs, val_f1s, val_rvals, edit_d, n_phn = [], [], [], [], [], []
     total_frames = corr_frames = 0
@@ -144,9 +171,13 @@ def validate(model, device, vocab, epoch, exp_dir, test_spk, val_dl, log_step=10
     }
 
 
-def test(model, device, vocab, exp_dir, test_spk, test_dl, rate, log_step=100, num_epochs=0) -> Dict[str, float]:
+def test(model, device, vocab, exp_dir, test_spk, test_dl, rate, log_step=100, num_epochs=0, device_metrics=False) -> Dict[str, float]:
     """train/train_force_aptai.py:655-838: as train_aptai.test plus the std entries and the CTC-based PER."""
     assert rate in ["F", "N"]
+    if device_metrics:
+        from .device_metrics import EvalAccumulator
+        model.eval()
+        return _device_eval(model, device, num_epochs, test_dl, EvalAccumulator("test", rate=rate, per="edit", with_std=True))
     names = hostlogic.TV_NAMES
     rmse_tvs, pcc_tvs = {n: [] for n in names}, {n: [] for n in names}
     overlaps, ps, rs, f1s, rvals, edit_d, n_phn, pers = [], [], [], [], [], [], [], []
@@ -179,7 +210,7 @@ def default_cfg(**kw):
     cfg = SimpleNamespace(device="cuda", num_epochs=2, batch_size=5, learning_rate=1e-5, adam_beta1=0.9, adam_beta2=0.999,
                           adam_epsilon=1e-8, adam_weight_decay=0.0, num_warmup_epochs=10, num_static_epochs=30, lr_decay=0.96,
                           target_metric="val_mean_rmse", target_metric_bigger_better=False, exp_dir=None, vocab=vocab,
-                          pr_model_path=None)
+                          pr_model_path=None, device_metrics=False)
     cfg.__dict__.update(kw)
     return cfg
 

@@ -118,7 +118,7 @@ def train(cfg, model, optimizer, lr_scheduler, vocab, train_dataloader, valid_da
         if runner is not None:
             runner.suspend()             # the eager validation below rebuilds its weight copies; the captured buckets stay
         model.eval()
-        val_logs = validate(model, cfg.device, vocab, epoch, valid_dataloader)
+        val_logs = validate(model, cfg.device, vocab, epoch, valid_dataloader, device_metrics=getattr(cfg, "device_metrics", False))
         better = (eval_target is None
                   or (cfg.target_metric_bigger_better and eval_target <= val_logs[cfg.target_metric])
                   or (not cfg.target_metric_bigger_better and eval_target >= val_logs[cfg.target_metric]))
@@ -154,8 +154,32 @@ def _decode(model, outputs) -> list:
     return [int(i) for i in ids[0, :int(n[0])].cpu().numpy()]
 
 
-def validate(model, device, vocab, epoch, validate_dataloader, log_step=100) -> Dict[str, float]:
-    """train/train_phoneme_recognizer.py:509-561, batch size 1."""
+def _device_eval(model, device, dl, acc, with_loss, laptop=False):
+    """validate()/test() with `device_metrics=True`: the best-path decode's ids and lengths go straight into the device
+    Levenshtein kernel; nothing is read back before `acc.result()`.  Any batch size (label counts from the -100 padding)."""
+    from . import device_metrics as dm, ops
+    for batch_idx, batch_x in enumerate(dl):
+        if laptop and batch_idx >= 1:
+            break
+        with torch.no_grad():
+            batch_x = {k: v.to(device) for k, v in batch_x.items()}
+            outputs = model(**batch_x)
+        if with_loss:
+            acc.add_loss(outputs["loss"])
+        lg = outputs["phoneme_logits"].float().contiguous()
+        B, T, V = lg.shape
+        ids, n = ops.ctc_greedy_decode(lg, V, T, B, T, V, model._blank(), T)
+        labels = batch_x["phoneme_labels"]
+        acc.add_edit(labels, dm.label_lengths(labels), ids, n)
+    return acc.result()
+
+
+def validate(model, device, vocab, epoch, validate_dataloader, log_step=100, device_metrics=False) -> Dict[str, float]:
+    """train/train_phoneme_recognizer.py:509-561, batch size 1.  `device_metrics=True` (opt-in): the edit distances stay on the
+    device (aptai_amd.device_metrics), one device->host transfer per call."""
+    if device_metrics:
+        from .device_metrics import EvalAccumulator
+        return _device_eval(model, device, validate_dataloader, EvalAccumulator("pr_val"), True)
     val_losses, edit_d, n_phn = [], [], []
     for batch_x in validate_dataloader:
         with torch.no_grad():
@@ -168,10 +192,13 @@ def validate(model, device, vocab, epoch, validate_dataloader, log_step=100) -> 
     return {"mean_val_per": float(np.sum(edit_d) / np.sum(n_phn)), "mean_val_loss": float(np.mean(val_losses))}
 
 
-def test(model, device, vocab, test_dl, dataset_name, log_step=100, laptop=False) -> Dict[str, float]:
+def test(model, device, vocab, test_dl, dataset_name, log_step=100, laptop=False, device_metrics=False) -> Dict[str, float]:
     """train/train_phoneme_recognizer.py:566-617."""
     edit_d, n_phn = [], []
     model.eval()
+    if device_metrics:
+        from .device_metrics import EvalAccumulator
+        return _device_eval(model, device, test_dl, EvalAccumulator("pr_test"), False, laptop=laptop)
     for batch_idx, batch_x in enumerate(test_dl):
         if laptop and batch_idx >= 1:
             break
@@ -189,7 +216,8 @@ def default_cfg(**kw):
     cfg = SimpleNamespace(device="cuda", num_epochs=2, batch_size=2, samples_per_epoch=8, learning_rate=5e-6, adam_beta1=0.9,
                           adam_beta2=0.999, adam_epsilon=1e-8, adam_weight_decay=0.0, num_warmup_epochs=10, num_static_epochs=30,
                           lr_decay=0.96, target_metric="mean_val_per", target_metric_bigger_better=False, final_dropout=0.1,
-                          num_hidden_layers=None, freeze_feature_extractor=False, save_all_epochs=False, cache_dir=None)
+                          num_hidden_layers=None, freeze_feature_extractor=False, save_all_epochs=False, cache_dir=None,
+                          device_metrics=False)
     cfg.__dict__.update(kw)
     return cfg
 

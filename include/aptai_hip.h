@@ -487,6 +487,40 @@ int aptai_dropout_f32(const float* x, float* y, int64_t n, float dropout_p, uint
 int aptai_colsum_f32(const float* x, int64_t ld, float* out, float* workspace, int64_t rows, int64_t N, void* stream);
 int64_t aptai_colsum_f32_workspace_bytes(int64_t N);
 
+/* ------------------------------------------------------------------------------------------------ evaluation metrics
+ * What validate()/test() of the reference's train_*.py compute on the host per utterance, on the device: raw pointers and
+ * pitches, int32 length vectors on the device, caller-owned outputs, the passed stream, no synchronisation, no atomics (fixed
+ * reduction order: lane-strided partials, a shuffle tree, then the waves in order; same inputs -> same bits).  Elements at or
+ * beyond a length are never read into a result.  All of these are latency-bound: one block or one wave per utterance. */
+/* tvs_metric_rmse / tvs_metric_ppc (utility.py:393-444).  gt, pred fp32: element (b, t, c) at (b*rows + t)*ld + c, each with its
+ * own rows and pitch; lens int32 [B], clamped to [0, max_len]; C tracks.  rmse, pcc fp64 [B][C], all arithmetic fp64 on the
+ * widened inputs.  rmse = sqrt(sum (x-y)^2 / T).  Pearson as scipy: means first, then centred sums, r = sxy / sqrt(sxx * syy)
+ * clipped to [-1, 1]; NaN where a track is constant over its T frames (T == 1 included); T == 0 gives NaN in both. */
+int aptai_eval_tv_scores(const float* gt, int64_t ldg, int64_t rows_g, const float* pred, int64_t ldp, int64_t rows_p,
+                         const int32_t* lens, int64_t B, int64_t max_len, int64_t C, double* rmse, double* pcc, void* stream);
+/* torch.eq(gt, pred).sum() of the loops and evaluate_overlap (utility.py:615-622): gt, pred int64 [B][ld]; counts int32 [B][2] =
+ * {frames = lens[b] clamped to [0, max_len], frames with gt == pred}. */
+int aptai_eval_frame_scores(const int64_t* gt, int64_t ldg, const int64_t* pred, int64_t ldp, const int32_t* lens, int64_t B,
+                            int64_t max_len, int32_t* counts, void* stream);
+/* get_stats (utility.py:588-612): y fp64 [B][ldy] with ny int32 [B], yhat fp64 [B][ldh] with nh; counts int32 [B][2] =
+ * {precision_counter = #{j : min_i |y_i - yhat_j| <= tolerance}, recall_counter = #{i : min_j |y_i - yhat_j| <= tolerance}} with
+ * numpy's fp64 subtraction, abs and compare, so the counts are exact.  ny == 0 or nh == 0 gives {0, 0}.  One block per
+ * utterance, the other side staged through LDS in chunks. */
+int aptai_eval_boundary_counts(const double* y, int64_t ldy, const int32_t* ny, const double* yhat, int64_t ldh, const int32_t* nh,
+                               double tolerance, int64_t B, int32_t* counts, void* stream);
+/* phn_frame_id2phn (utility.py:561-566): runs of equal labels collapsed.  x int64 [B][ld], lens int32 [B]; out int32 [B][ldo]
+ * zero-padded, n_out int32 [B] = collapsed length (may exceed ldo: the caller checks; never when ldo >= ld). */
+int aptai_eval_collapse_runs(const int64_t* x, int64_t ld, const int32_t* lens, int64_t B, int32_t* out, int64_t ldo, int32_t* n_out,
+                             void* stream);
+/* editdistance.eval (train/train_force_aptai.py:582, train/train_phoneme_recognizer.py:540): Levenshtein distance of B pairs.
+ * a int32 [B][lda] with a_lens, b int32 [B][ldb] with b_lens (lengths clamped to the row length); dist int32 [B].  One wave per
+ * pair; `a` lives in registers, 64 lanes x {1, 4, 8, 16, 32} rows picked from lda, so lda <= APTAI_EVAL_EDIT_MAX_LANE_SIDE (a
+ * status names both row lengths otherwise; the distance is symmetric, so the caller puts the side that fits in `a`); b is
+ * unbounded: b_len + 63 steps.  An empty side gives the other side's length. */
+#define APTAI_EVAL_EDIT_MAX_LANE_SIDE 2048
+int aptai_eval_edit_distance(const int32_t* a, int64_t lda, const int32_t* a_lens, const int32_t* b, int64_t ldb,
+                             const int32_t* b_lens, int64_t B, int32_t* dist, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
