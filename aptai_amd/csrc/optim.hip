@@ -23,13 +23,19 @@ __device__ __forceinline__ float adam_one(float p, float g, float& m, float& v, 
     return p - (a.lr / a.bc1) * (m / denom);
 }
 
-__global__ __launch_bounds__(256) void adam_multi_kernel(AdamArgs a) {
+// SCALED = false is the plain step.  SCALED = true multiplies every gradient by *scale first (the global-norm clip coefficient
+// grad_norm_final_kernel left on the device: one scalar load per block, one rounded fp32 multiply per element), then runs the
+// same adam_one - so weight decay is added to the SCALED gradient, as torch.nn.utils.clip_grad_norm_ + torch.optim.Adam do.
+template <bool SCALED>
+__global__ __launch_bounds__(256) void adam_multi_kernel(AdamArgs a, const float* __restrict__ scale) {
     const int64_t* job = a.table + (long)blockIdx.y * 6;
     const int64_t* dyn = a.dyn + (long)blockIdx.y * 2;
     const long n = job[4];
     const long base = (long)blockIdx.x * ADAM_CHUNK;
     const float* g = (const float*)dyn[0];
     if (base >= n || g == nullptr) return;
+    float coef = 1.0f;
+    if (SCALED) coef = *scale;
     // bias corrections of this parameter's own step count (parameters skipped by LayerDrop lag behind), in double like
     // the Python reference; every thread computes the same two values
     // (one lane per block evaluates the two double-precision powers - 256 threads each did, ~200 instructions beside 16 elements of work)
@@ -66,7 +72,7 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(AdamArgs a) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 float mr = mm[r], vr = vv[r];
-                pp[r] = adam_one(pp[r], gg[r], mr, vr, a);
+                pp[r] = adam_one(pp[r], SCALED ? __fmul_rn(gg[r], coef) : gg[r], mr, vr, a);
                 mm[r] = mr;
                 vv[r] = vr;
             }
@@ -83,7 +89,7 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(AdamArgs a) {
         end = end < n ? end : n;
         for (long i = base + threadIdx.x; i < end; i += 256) {
             float mr = m[i], vr = v[i];
-            const float pn = adam_one(p[i], g[i], mr, vr, a);
+            const float pn = adam_one(p[i], SCALED ? __fmul_rn(g[i], coef) : g[i], mr, vr, a);
             p[i] = pn;
             m[i] = mr;
             v[i] = vr;
@@ -95,18 +101,176 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(AdamArgs a) {
     }
 }
 
+// ---------------------------------------------------------------------------------- global gradient norm (clipping)
+// Stage 1: block (x, y) sums the squares of chunk x of job y's gradient - the ADAM_CHUNK chunking and thread mapping of
+// adam_multi_kernel - in fp32 and in a fixed order: <= 16 products per thread, the 6-step shuffle tree of wave_sum, the four wave
+// sums in index order.  One partial per chunk, written with a plain store to partials[chunks of jobs 0 .. y-1 + x]; a job without a
+// gradient this step owns no chunks (it contributes exact zeros, and the partials are those of the table without it).  Which block
+// writes which word is a function of the two job tables only: no atomics, no dispatch order.
+__device__ __forceinline__ long norm_chunks(long n, int64_t grad) { return grad ? (n + ADAM_CHUNK - 1) / ADAM_CHUNK : 0; }
+
+__global__ __launch_bounds__(256) void grad_sqnorm_kernel(const int64_t* __restrict__ table, const int64_t* __restrict__ dynt,
+                                                          float* __restrict__ partials) {
+    const int64_t* job = table + (long)blockIdx.y * 6;
+    const long n = job[4];
+    const long base = (long)blockIdx.x * ADAM_CHUNK;
+    const float* g = (const float*)dynt[(long)blockIdx.y * 2];
+    if (base >= n || g == nullptr) return;
+    float acc = 0.f;
+    {
+        const bool vec = (n % 4 == 0) && ((int64_t)g % 16 == 0);
+        if (vec) {
+            f32x4 gq[4];
+#pragma unroll
+            for (int it = 0; it < 4; ++it) {
+                const long i = base + (long)(it * 256 + threadIdx.x) * 4;
+                gq[it] = i < n ? *(const f32x4*)(g + i) : (f32x4){0.f, 0.f, 0.f, 0.f};
+            }
+#pragma unroll
+            for (int it = 0; it < 4; ++it)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) acc = fmaf(gq[it][r], gq[it][r], acc);
+        } else {
+            long end = base + ADAM_CHUNK;
+            end = end < n ? end : n;
+            for (long i = base + threadIdx.x; i < end; i += 256) acc = fmaf(g[i], g[i], acc);
+        }
+    }
+    // this chunk's slot: the chunks of every job before this one (one strided pass over the table; it overlaps the gradient loads)
+    long before = 0;
+    for (long j = threadIdx.x; j < (long)blockIdx.y; j += 256) before += norm_chunks(table[j * 6 + 4], dynt[j * 2]);
+    __shared__ float ws[4];
+    __shared__ long wo[4];
+    acc = wave_sum(acc);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) before += __shfl_xor(before, o, 64);
+    if ((threadIdx.x & 63) == 0) { ws[threadIdx.x >> 6] = acc; wo[threadIdx.x >> 6] = before; }
+    __syncthreads();
+    if (threadIdx.x == 0) partials[wo[0] + wo[1] + wo[2] + wo[3] + blockIdx.x] = ((ws[0] + ws[1]) + ws[2]) + ws[3];
+}
+
+// Stage 2, ONE block: thread t adds partials t, t + 256, ... in index order in double, a fixed LDS tree adds the 256 sums, thread 0
+// takes the root and evaluates coef = min(1, max_norm / (total + 1e-6)) in double (NaN propagates through the comparison; total = inf
+// gives 0; max_norm = inf gives 1) and rounds once.  result = {total norm, coef, number of gradient elements} as fp32.
+__global__ __launch_bounds__(256) void grad_norm_final_kernel(const int64_t* __restrict__ table, const int64_t* __restrict__ dynt,
+                                                              long njobs, const float* __restrict__ partials,
+                                                              float* __restrict__ result, double max_norm) {
+    __shared__ double sd[256];
+    __shared__ long sc[256];
+    __shared__ double se[256];
+    long count = 0;
+    double elems = 0.0;
+    for (long j = threadIdx.x; j < njobs; j += 256) {
+        const long n = table[j * 6 + 4];
+        count += norm_chunks(n, dynt[j * 2]);
+        if (dynt[j * 2] != 0) elems += (double)n;
+    }
+    sc[threadIdx.x] = count;
+    se[threadIdx.x] = elems;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) { sc[threadIdx.x] += sc[threadIdx.x + o]; se[threadIdx.x] += se[threadIdx.x + o]; }
+        __syncthreads();
+    }
+    count = sc[0];
+    double acc = 0.0;
+    for (long i = threadIdx.x; i < count; i += 256) acc += (double)partials[i];
+    sd[threadIdx.x] = acc;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) sd[threadIdx.x] += sd[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const double total = sqrt(sd[0]);
+        const double c = max_norm / (total + 1e-6);
+        result[0] = (float)total;
+        result[1] = (float)(c > 1.0 ? 1.0 : c);
+        result[2] = (float)se[0];
+    }
+}
+
+// g *= *scale in place (one rounded fp32 multiply, the multiply of adam_multi_kernel<true>), same chunking, both paths.
+__global__ __launch_bounds__(256) void scale_multi_kernel(const int64_t* __restrict__ table, const int64_t* __restrict__ dynt,
+                                                          const float* __restrict__ scale) {
+    const long n = table[(long)blockIdx.y * 6 + 4];
+    const long base = (long)blockIdx.x * ADAM_CHUNK;
+    float* g = (float*)dynt[(long)blockIdx.y * 2];
+    if (base >= n || g == nullptr) return;
+    const float coef = *scale;
+    if ((n % 4 == 0) && ((int64_t)g % 16 == 0)) {
+        f32x4 gq[4];
+#pragma unroll
+        for (int it = 0; it < 4; ++it) {
+            const long i = base + (long)(it * 256 + threadIdx.x) * 4;
+            if (i < n) gq[it] = *(const f32x4*)(g + i);
+        }
+#pragma unroll
+        for (int it = 0; it < 4; ++it) {
+            const long i = base + (long)(it * 256 + threadIdx.x) * 4;
+            if (i >= n) break;
+            f32x4 gg = gq[it];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) gg[r] = __fmul_rn(gg[r], coef);
+            *(f32x4*)(g + i) = gg;
+        }
+    } else {
+        long end = base + ADAM_CHUNK;
+        end = end < n ? end : n;
+        for (long i = base + threadIdx.x; i < end; i += 256) g[i] = __fmul_rn(g[i], coef);
+    }
+}
+
 }  // namespace
 
-extern "C" int aptai_adam_multi(const int64_t* table_dev, const int64_t* dyn_dev, int64_t njobs, int64_t max_n, float lr, float beta1,
-                                float beta2, float eps, float weight_decay, void* stream) {
-    APTAI_REQUIRE(table_dev && dyn_dev && njobs > 0 && njobs <= 65535 && max_n > 0, "aptai_adam_multi: bad arguments");
-    APTAI_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f, "aptai_adam_multi: betas must lie in [0, 1)");
+static int adam_launch(const char* who, const int64_t* table_dev, const int64_t* dyn_dev, int64_t njobs, int64_t max_n, float lr,
+                       float beta1, float beta2, float eps, float weight_decay, const float* grad_scale_dev, bool scaled, void* stream) {
+    APTAI_REQUIRE(table_dev && dyn_dev && njobs > 0 && njobs <= 65535 && max_n > 0, "%s: bad arguments", who);
+    APTAI_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f, "%s: betas must lie in [0, 1)", who);
+    APTAI_REQUIRE(!scaled || grad_scale_dev, "%s: grad_scale_dev is null", who);
     AdamArgs a;
     a.table = table_dev;
     a.dyn = dyn_dev;
     a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.weight_decay = weight_decay;
     a.bc1 = a.bc2_sqrt = 1.f;
-    APTAI_LAUNCH(adam_multi_kernel, dim3((unsigned)ceil_div(max_n, ADAM_CHUNK), (unsigned)njobs), dim3(256), 0, (hipStream_t)stream, a);
+    const dim3 grid((unsigned)ceil_div(max_n, ADAM_CHUNK), (unsigned)njobs);
+    if (scaled) APTAI_LAUNCH(adam_multi_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, a, grad_scale_dev);
+    else APTAI_LAUNCH(adam_multi_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, a, (const float*)nullptr);
     APTAI_CHECK_LAUNCH("adam_multi_kernel");
+    return APTAI_OK;
+}
+
+extern "C" int aptai_adam_multi(const int64_t* table_dev, const int64_t* dyn_dev, int64_t njobs, int64_t max_n, float lr, float beta1,
+                                float beta2, float eps, float weight_decay, void* stream) {
+    return adam_launch("aptai_adam_multi", table_dev, dyn_dev, njobs, max_n, lr, beta1, beta2, eps, weight_decay, nullptr, false, stream);
+}
+
+extern "C" int aptai_adam_multi_scaled(const int64_t* table_dev, const int64_t* dyn_dev, int64_t njobs, int64_t max_n, float lr,
+                                       float beta1, float beta2, float eps, float weight_decay, const float* grad_scale_dev,
+                                       void* stream) {
+    return adam_launch("aptai_adam_multi_scaled", table_dev, dyn_dev, njobs, max_n, lr, beta1, beta2, eps, weight_decay,
+                       grad_scale_dev, true, stream);
+}
+
+extern "C" int aptai_grad_sqnorm_multi(const int64_t* table_dev, const int64_t* dyn_dev, int64_t njobs, int64_t max_n,
+                                       float* partials_dev, float* result_dev, double max_norm, void* stream) {
+    APTAI_REQUIRE(table_dev && dyn_dev && partials_dev && result_dev && njobs > 0 && njobs <= 65535 && max_n > 0,
+                  "aptai_grad_sqnorm_multi: bad arguments");
+    APTAI_REQUIRE(max_norm >= 0.0, "aptai_grad_sqnorm_multi: max_norm must be >= 0 (inf measures without clipping)");
+    APTAI_LAUNCH(grad_sqnorm_kernel, dim3((unsigned)ceil_div(max_n, ADAM_CHUNK), (unsigned)njobs), dim3(256), 0, (hipStream_t)stream,
+                 table_dev, dyn_dev, partials_dev);
+    APTAI_CHECK_LAUNCH("grad_sqnorm_kernel");
+    APTAI_LAUNCH(grad_norm_final_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, table_dev, dyn_dev, (long)njobs,
+                 (const float*)partials_dev, result_dev, max_norm);
+    APTAI_CHECK_LAUNCH("grad_norm_final_kernel");
+    return APTAI_OK;
+}
+
+extern "C" int aptai_scale_multi(const int64_t* table_dev, const int64_t* dyn_dev, int64_t njobs, int64_t max_n, const float* scale_dev,
+                                 void* stream) {
+    APTAI_REQUIRE(table_dev && dyn_dev && scale_dev && njobs > 0 && njobs <= 65535 && max_n > 0, "aptai_scale_multi: bad arguments");
+    APTAI_LAUNCH(scale_multi_kernel, dim3((unsigned)ceil_div(max_n, ADAM_CHUNK), (unsigned)njobs), dim3(256), 0, (hipStream_t)stream,
+                 table_dev, dyn_dev, scale_dev);
+    APTAI_CHECK_LAUNCH("scale_multi_kernel");
     return APTAI_OK;
 }

@@ -590,6 +590,36 @@ class CastPlan:
         _lib.call("aptai_cast_multi", self.table.data_ptr(), len(self.jobs), self.max_n, _stream())
 
 
+GRAD_NORM_CHUNK = 4096      # elements per partial sum of grad_sqnorm_multi (ADAM_CHUNK of csrc/optim.hip)
+
+
+def grad_norm_chunks(numels) -> int:
+    """fp32 words of the partial-sum workspace grad_sqnorm_multi needs for jobs of these sizes."""
+    return sum((int(n) + GRAD_NORM_CHUNK - 1) // GRAD_NORM_CHUNK for n in numels)
+
+
+def grad_sqnorm_multi(table_ptr: int, dyn_ptr: int, njobs: int, max_n: int, partials, result, max_norm: float, stream=None) -> None:
+    """result fp32 [3] = {global 2-norm, clip coefficient, gradient elements} of the jobs' gradients (aptai_grad_sqnorm_multi: Adam
+    job tables by address, so a row range of a larger table works); order-fixed, no synchronisation."""
+    _dev(partials, result)
+    _lib.call("aptai_grad_sqnorm_multi", table_ptr, dyn_ptr, njobs, max_n, partials.data_ptr(), result.data_ptr(), float(max_norm),
+              _stream() if stream is None else stream)
+
+
+def adam_multi_scaled(table_ptr: int, dyn_ptr: int, njobs: int, max_n: int, lr, beta1, beta2, eps, weight_decay, scale,
+                      stream=None) -> None:
+    """aptai_adam_multi on gradients multiplied by the device scalar `scale` (aptai_adam_multi_scaled); `.grad` is not written."""
+    _dev(scale)
+    _lib.call("aptai_adam_multi_scaled", table_ptr, dyn_ptr, njobs, max_n, float(lr), float(beta1), float(beta2), float(eps),
+              float(weight_decay), scale.data_ptr(), _stream() if stream is None else stream)
+
+
+def scale_multi(table_ptr: int, dyn_ptr: int, njobs: int, max_n: int, scale, stream=None) -> None:
+    """Gradients of the jobs *= the device scalar `scale`, in place (aptai_scale_multi)."""
+    _dev(scale)
+    _lib.call("aptai_scale_multi", table_ptr, dyn_ptr, njobs, max_n, scale.data_ptr(), _stream() if stream is None else stream)
+
+
 def conv_weight_bf16(w: torch.Tensor) -> torch.Tensor:
     """[N][C][Kw] fp32 -> [N][Kw*C] bf16."""
     _dev(w)

@@ -5,6 +5,12 @@ same constructor arguments, ``param_groups`` (LambdaLR works unchanged) and ``st
 
 It can also refresh the model's compute copies in the same pass (``publish_to(model)``): the updated fp32 parameter is written
 back AND converted into the persistent bf16 buffer the GEMMs read, which removes the separate per-step cast launch.
+
+Global-norm gradient clipping (``torch.nn.utils.clip_grad_norm_(params, max_norm)`` before ``optimizer.step()``, the HF Trainer's
+``max_grad_norm``) is fused into the step: ``Adam(..., max_grad_norm=1.0)`` measures the 2-norm of every gradient of every parameter
+group with an order-fixed two-stage reduction, leaves the coefficient on the device and the Adam kernel multiplies each gradient by
+it as it reads it.  ``.grad`` is NOT modified in this form: it still holds the unclipped gradient after ``step()``.
+``clip_grad_norm_`` below is the in-place drop-in for a loop that wants torch's two calls.
 """
 from __future__ import annotations
 
@@ -13,17 +19,52 @@ from typing import Dict, Optional
 
 import torch
 
-from . import _lib
+from . import _lib, ops
+
+
+def _check_max_norm(max_norm) -> float:
+    max_norm = float(max_norm)
+    if not max_norm >= 0:                           # negative or NaN
+        raise ValueError(f"max_grad_norm must be >= 0 (float('inf') measures the norm without clipping), got {max_norm}")
+    return max_norm
 
 
 class Adam(torch.optim.Optimizer):
-    def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0):
+    def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
+                 max_grad_norm: Optional[float] = None):
         if lr < 0 or eps < 0 or not (0 <= betas[0] < 1) or not (0 <= betas[1] < 1) or weight_decay < 0:
             raise ValueError("invalid Adam hyper-parameters")
+        # an attribute, not a param_groups key (one norm spans all groups; state_dict() stays interchangeable with torch's)
+        self.max_grad_norm = max_grad_norm
         super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay))
         self._copies: Dict[int, tuple] = {}         # id(param) -> (destination tensor, kind)
         self._tables: Dict[int, tuple] = {}         # group index -> (key, table tensor, max_n)
         self._plans = []
+        self._span = None                           # clipping: one job table over every group (_span_tables)
+        self._clip_result = None                    # clipping: device fp32 {total norm, coefficient, gradient elements}
+        self._pending_clip = None
+
+    # ------------------------------------------------------------------ global-norm clipping
+    @property
+    def max_grad_norm(self) -> Optional[float]:
+        """None: the plain step.  A value: clip the gradients of ALL parameter groups at this global 2-norm inside step() (`.grad`
+        keeps the unclipped gradient); float('inf') measures the norm and clips nothing.  May be reassigned between steps."""
+        return self._max_grad_norm
+
+    @max_grad_norm.setter
+    def max_grad_norm(self, value) -> None:
+        self._max_grad_norm = None if value is None else _check_max_norm(value)
+
+    @property
+    def last_grad_norm(self) -> Optional[torch.Tensor]:
+        """0-dim device view of the last clipped step's global gradient norm (before clipping).  Valid after step(), overwritten by
+        the next one, NOT synchronised: reading it on the host waits for the step."""
+        return None if self._clip_result is None else self._clip_result[0]
+
+    @property
+    def last_clip_coef(self) -> Optional[torch.Tensor]:
+        """0-dim device view of min(1, max_grad_norm / (norm + 1e-6)) of the last clipped step (see last_grad_norm)."""
+        return None if self._clip_result is None else self._clip_result[1]
 
     # ------------------------------------------------------------------ compute copies
     def publish_to(self, model) -> "Adam":
@@ -37,6 +78,7 @@ class Adam(torch.optim.Optimizer):
                 self._copies[id(p)] = (dst, 0 if dst.dtype == torch.bfloat16 else 1)
         self._plans.append(plan)
         self._tables.clear()
+        self._span = None
         return self
 
     # ------------------------------------------------------------------ step
@@ -69,6 +111,31 @@ class Adam(torch.optim.Optimizer):
         self._tables[gi] = cached
         return cached
 
+    def _span_tables(self, ts):
+        """Clipping: ONE job table over the rows of every group (`ts`: the groups' tables in group order), so that one norm spans
+        them and its summation order depends on the tables alone; per-step rows, pinned ring, partial-sum workspace and the result
+        words are allocated here, never inside a step.  The groups' Adam launches read row ranges of this table."""
+        span = self._span
+        if span is not None and len(span["tables"]) == len(ts) and all(a is t["table"] for a, t in zip(span["tables"], ts)):
+            return span
+        devs = {t["table"].device for t in ts}
+        if len(devs) != 1:
+            raise _lib.AptaiHipError("aptai_amd.optim.Adam(max_grad_norm=...): one global norm needs every parameter group on one device")
+        dev = devs.pop()
+        offs, n = {}, 0
+        for t in ts:
+            offs[id(t)] = n
+            n += len(t["params"])
+        numels = [m for t in ts for m in t["numels"]]
+        if self._clip_result is None or self._clip_result.device != dev:
+            self._clip_result = torch.zeros(3, dtype=torch.float32, device=dev)
+        span = dict(tables=[t["table"] for t in ts], table=torch.cat([t["table"] for t in ts]).contiguous(), offs=offs, n=n,
+                    max_n=max(numels), dyn_dev=torch.zeros((n, 2), dtype=torch.int64, device=dev),
+                    partials=torch.zeros(ops.grad_norm_chunks(numels), dtype=torch.float32, device=dev),
+                    ring=[torch.zeros((n, 2), dtype=torch.int64).pin_memory() for _ in range(4)], events=[None] * 4, turn=0)
+        self._span = span
+        return span
+
     @torch.no_grad()
     def step(self, closure=None):
         loss = None
@@ -89,6 +156,11 @@ class Adam(torch.optim.Optimizer):
         stream = torch.cuda.current_stream()
         early_ids = {id(p) for p in early}
         self._pending = []
+        self._pending_clip = None
+        if self._max_grad_norm is not None:
+            # the global norm does not exist before the last gradient does: every row goes to finish(), `early` is ignored
+            # (launch_early() then finds nothing to do and the step is the one-launch step, bit for bit)
+            return self._prepare_clipped(stream)
         for gi, group in enumerate(self.param_groups):
             if not any(p.is_cuda for p in group["params"]):
                 if any(p.grad is not None for p in group["params"]):
@@ -125,6 +197,49 @@ class Adam(torch.optim.Optimizer):
             t["events"][slot] = ev
             self._pending.append((t, group, any_late))
 
+    def _prepare_clipped(self, stream) -> None:
+        """prepare() with clipping on: the same checks and step counts, the per-step rows of ALL groups in one table, one copy."""
+        ts = []
+        for gi, group in enumerate(self.param_groups):
+            if not any(p.is_cuda for p in group["params"]):
+                if any(p.grad is not None for p in group["params"]):
+                    raise _lib.AptaiHipError("aptai_amd.optim.Adam needs parameters on the MI355X (no CPU fallback)")
+                continue
+            t = self._group_tables(gi, group)
+            if any(p.grad is not None for p in t["others"]):
+                raise _lib.AptaiHipError("aptai_amd.optim.Adam updates contiguous fp32 parameters on the MI355X only")
+            ts.append((t, group))
+        if not ts:
+            return
+        span = self._span_tables([t for t, _ in ts])
+        slot = span["turn"]
+        span["turn"] = (slot + 1) % len(span["ring"])
+        if span["events"][slot] is not None:
+            span["events"][slot].synchronize()         # the copy that last used this pinned buffer has been consumed
+        host = span["ring"][slot].numpy()              # [rows of all groups][2]
+        host[:, 0] = 0
+        for t, group in ts:
+            off, any_grad = span["offs"][id(t)], False
+            for j, (p, st) in enumerate(zip(t["params"], t["states"])):
+                g = p.grad
+                if g is None:
+                    continue
+                if g.dtype != torch.float32 or not g.is_contiguous():
+                    raise _lib.AptaiHipError("aptai_amd.optim.Adam needs contiguous fp32 gradients")
+                st["step"] += 1
+                host[off + j, 0] = g.data_ptr()
+                host[off + j, 1] = st["step"]
+                any_grad = True
+            if any_grad:
+                self._pending.append((t, group, True))
+        if not self._pending:
+            return
+        span["dyn_dev"].copy_(span["ring"][slot], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(stream)
+        span["events"][slot] = ev
+        self._pending_clip = (span, self._max_grad_norm)
+
     def _launch(self, t, group, plane: int, r0: int, r1: int, stream) -> None:
         b1, b2 = group["betas"]
         _lib.call("aptai_adam_multi", t["table"][r0].data_ptr(), t["dyn_dev"][plane, r0].data_ptr(), r1 - r0, max(t["numels"][r0:r1]),
@@ -135,6 +250,8 @@ class Adam(torch.optim.Optimizer):
         """Update `params` (named in prepare(early=...)) now, on `stream`: one launch per parameter group over the row range that
         spans them (rows in between that were not named `early` carry no gradient pointer in this plane and are skipped)."""
         stream = stream or torch.cuda.current_stream()
+        if self._pending_clip is not None:
+            return
         ids = {id(p) for p in params}
         for t, group, _ in self._pending:
             rows = [j for j, p in enumerate(t["params"]) if id(p) in ids]
@@ -145,9 +262,23 @@ class Adam(torch.optim.Optimizer):
     def finish(self, stream=None) -> None:
         """Update every parameter that has a gradient and was not named `early`."""
         stream = stream or torch.cuda.current_stream()
-        for t, group, any_late in self._pending:
-            if any_late:
-                self._launch(t, group, 0, 0, len(t["params"]), stream)
+        if self._pending_clip is not None:
+            # here, not in prepare(): every gradient is final now (and, under data parallelism, already averaged: the norm is that
+            # of the averaged gradient and the same on every rank).  Two norm launches, then the groups' Adam launches read the
+            # coefficient from the device on the same stream
+            span, max_norm = self._pending_clip
+            tab, dyn, coef = span["table"].data_ptr(), span["dyn_dev"].data_ptr(), self._clip_result[1:2]
+            ops.grad_sqnorm_multi(tab, dyn, span["n"], span["max_n"], span["partials"], self._clip_result, max_norm, stream.cuda_stream)
+            for t, group, _ in self._pending:
+                off = span["offs"][id(t)]
+                b1, b2 = group["betas"]
+                ops.adam_multi_scaled(tab + off * 48, dyn + off * 16, len(t["params"]), t["max_n"], group["lr"], b1, b2, group["eps"],
+                                      group["weight_decay"], coef, stream.cuda_stream)
+            self._pending_clip = None
+        else:
+            for t, group, any_late in self._pending:
+                if any_late:
+                    self._launch(t, group, 0, 0, len(t["params"]), stream)
         self._pending = []
         for plan in self._plans:                    # the copies of every parameter that had a gradient are fresh now;
             plan.optimizer_synced = True            # parameters without one did not move
@@ -170,3 +301,70 @@ class Adam(torch.optim.Optimizer):
             if torch.is_tensor(st.get("step")):
                 st["step"] = int(st["step"].item())
         self._tables.clear()                        # the moment buffers were replaced: rebuild the job tables
+        self._span = None
+
+
+def clip_grad_norm_(parameters, max_norm: float, norm_type: float = 2.0, error_if_nonfinite: bool = False, foreach=None) -> torch.Tensor:
+    """Drop-in for ``torch.nn.utils.clip_grad_norm_`` in a loop of the user's own: the order-fixed norm kernel of
+    ``Adam(max_grad_norm=...)``, then the gradients are multiplied IN PLACE by min(1, max_norm / (norm + 1e-6)) read from the device.
+    Returns the total norm as a 0-dim device tensor, not synchronised.  2-norm only; contiguous fp32 gradients on one MI355X only (no
+    fallback).  ``error_if_nonfinite=True`` reads the norm back - a host synchronisation - and raises before anything is scaled.
+    ``foreach`` is accepted and ignored.  The pointer table is built per call from pageable memory: a convenience, not the hot path
+    (that is ``Adam(max_grad_norm=...)``, which reads each gradient once more instead of rewriting it)."""
+    if float(norm_type) != 2.0:
+        raise ValueError(f"aptai_amd.optim.clip_grad_norm_ computes the 2-norm only (norm_type={norm_type})")
+    max_norm = _check_max_norm(max_norm)
+    if isinstance(parameters, torch.Tensor):
+        parameters = [parameters]
+    grads = [p.grad for p in parameters if p.grad is not None]
+    for g in grads:
+        if not g.is_cuda or g.dtype != torch.float32 or not g.is_contiguous():
+            raise _lib.AptaiHipError("aptai_amd.optim.clip_grad_norm_ needs contiguous fp32 gradients on the MI355X (no CPU fallback)")
+    if len({g.device for g in grads}) > 1:
+        raise _lib.AptaiHipError("aptai_amd.optim.clip_grad_norm_: gradients on more than one device")
+    grads = [g for g in grads if g.numel() > 0]
+    if not grads:
+        return torch.zeros(())
+    dev = grads[0].device
+    numels = [g.numel() for g in grads]
+    table = torch.tensor([[0, 0, 0, 0, n, 0] for n in numels], dtype=torch.int64).to(dev)
+    dyn = torch.tensor([[g.data_ptr(), 0] for g in grads], dtype=torch.int64).to(dev)
+    partials = torch.empty(ops.grad_norm_chunks(numels), dtype=torch.float32, device=dev)
+    result = torch.empty(3, dtype=torch.float32, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    ops.grad_sqnorm_multi(table.data_ptr(), dyn.data_ptr(), len(grads), max(numels), partials, result, max_norm, stream)
+    if error_if_nonfinite and not math.isfinite(result[0].item()):
+        raise RuntimeError("The total norm for gradients from `parameters` is non-finite, so it cannot be clipped. To disable this "
+                           "error and scale the gradients by the non-finite norm anyway, set `error_if_nonfinite=False`")
+    ops.scale_multi(table.data_ptr(), dyn.data_ptr(), len(grads), max(numels), result[1:2], stream)
+    return result[0]
+
+
+class ClipMonitor:
+    """What the training loops log about clipping: adds the optimiser's device-side norm and `coef < 1` into two device scalars after
+    each step and reads them back ONCE per epoch (epoch_log())."""
+
+    def __init__(self, optimizer):
+        if getattr(optimizer, "max_grad_norm", None) is None:
+            raise _lib.AptaiHipError("cfg.max_grad_norm needs an aptai_amd.optim.Adam built with max_grad_norm=... (no clipping fallback)")
+        self.opt = optimizer
+        self.acc = None
+        self.steps = 0
+
+    def update(self) -> None:
+        norm, coef = self.opt.last_grad_norm, self.opt.last_clip_coef
+        if norm is None:                            # no step with clipping yet (nothing had a gradient)
+            return
+        if self.acc is None:
+            self.acc = torch.zeros(2, dtype=torch.float32, device=norm.device)
+        self.acc[0] += norm
+        self.acc[1] += coef < 1
+        self.steps += 1
+
+    def epoch_log(self) -> dict:
+        sums = [0.0, 0.0] if self.acc is None else self.acc.tolist()
+        out = dict(mean_grad_norm=sums[0] / max(self.steps, 1), clipped_steps=int(sums[1]))
+        if self.acc is not None:
+            self.acc.zero_()
+        self.steps = 0
+        return out

@@ -49,7 +49,8 @@ def load_model_optimizer(args_cfg):
     model = Force_APTAI(args_cfg.pr_model_path, args_cfg.device, args_cfg.vocab).to(args_cfg.device)
     from .optim import Adam
     optimizer = Adam([p for p in model.parameters() if p.requires_grad], lr=args_cfg.learning_rate,
-                     betas=(args_cfg.adam_beta1, args_cfg.adam_beta2), eps=args_cfg.adam_epsilon, weight_decay=args_cfg.adam_weight_decay)
+                     betas=(args_cfg.adam_beta1, args_cfg.adam_beta2), eps=args_cfg.adam_epsilon, weight_decay=args_cfg.adam_weight_decay,
+                     max_grad_norm=getattr(args_cfg, "max_grad_norm", None))
     lr_scheduler = torch.optim.lr_scheduler.LambdaLR(
         optimizer=optimizer, lr_lambda=hostlogic.get_lr_schedule(args_cfg.num_warmup_epochs, args_cfg.num_static_epochs, args_cfg.lr_decay))
     return model, optimizer, lr_scheduler
@@ -59,6 +60,12 @@ def train(cfg, model, optimizer, lr_scheduler, train_dataloader, valid_dataloade
     """train/train_force_aptai.py:392-531.  Returns the per-epoch log dicts."""
     eval_target = None
     history = []
+    # cfg.max_grad_norm: the optimiser clips at this global norm inside step(); the loop only adds the device-side norm and the
+    # "was clipped" flag into two device scalars per step and reads them once per epoch (optim.ClipMonitor)
+    clip = None
+    if getattr(cfg, "max_grad_norm", None) is not None:
+        from .optim import ClipMonitor
+        clip = ClipMonitor(optimizer)
     best_ckpt_path = Path(best_ckpt_path)
     best_ckpt_path.mkdir(parents=True, exist_ok=True)
     for epoch in range(cfg.num_epochs):
@@ -82,6 +89,8 @@ def train(cfg, model, optimizer, lr_scheduler, train_dataloader, valid_dataloade
             outputs = model(epoch, **batch_x, _prefetch_next=ahead)
             outputs["loss"].backward()
             optimizer.step()
+            if clip is not None:
+                clip.update()
             sum_train_loss += float(outputs["loss"].detach())
             steps += 1
             log(f"\tepoch {epoch + 1} ~ batch {batch_idx + 1}/{len(train_dataloader)}, train_loss: {float(outputs['loss'].detach()):.4f}, "
@@ -100,6 +109,8 @@ def train(cfg, model, optimizer, lr_scheduler, train_dataloader, valid_dataloade
             pickle.dump(model.get_config(), open(best_ckpt_path / "model_cfg.pkl", "wb"))
         epoch_log = dict(val_logs, epoch=epoch, mean_train_loss=sum_train_loss / max(steps, 1), lr=optimizer.param_groups[0]["lr"],
                          saved=bool(better))
+        if clip is not None:
+            epoch_log.update(clip.epoch_log())
         history.append(epoch_log)
         log(f"Epoch {epoch + 1}/{cfg.num_epochs} -> " + " | ".join(f"{k}: {v:.4f}" for k, v in epoch_log.items() if isinstance(v, float)))
     return history
@@ -224,9 +235,12 @@ def main(argv=None):
     ap.add_argument("--batch_size", type=int, default=5)
     ap.add_argument("--seconds", type=float, default=10.0)
     ap.add_argument("--learning_rate", type=float, default=1e-5)
+    ap.add_argument("--max_grad_norm", type=float, default=None,
+                    help="clip the gradients at this global 2-norm inside the optimiser step (off by default)")
     ap.add_argument("--out", default="force_aptai_ckpt")
     a = ap.parse_args(argv)
-    cfg = default_cfg(num_epochs=a.num_epochs, batch_size=a.batch_size, learning_rate=a.learning_rate, pr_model_path=a.pr_model_path)
+    cfg = default_cfg(num_epochs=a.num_epochs, batch_size=a.batch_size, learning_rate=a.learning_rate, pr_model_path=a.pr_model_path,
+                      max_grad_norm=a.max_grad_norm)
     model, optimizer, lr_scheduler = load_model_optimizer(cfg)
     w2v = model.w2v2_pr.wav2vec2.config
     train_ds = SyntheticHPRCWithLabels(a.steps_per_epoch * a.batch_size, a.seconds, seed=1, cfg=w2v, vocab_size=len(cfg.vocab))

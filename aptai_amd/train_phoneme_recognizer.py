@@ -71,7 +71,8 @@ def load_model_optimizer(args_cfg, vocab):
         model.freeze_feature_encoder()
     from .optim import Adam
     optimizer = Adam(model.parameters(), lr=args_cfg.learning_rate, betas=(args_cfg.adam_beta1, args_cfg.adam_beta2),
-                     eps=args_cfg.adam_epsilon, weight_decay=args_cfg.adam_weight_decay).publish_to(model)
+                     eps=args_cfg.adam_epsilon, weight_decay=args_cfg.adam_weight_decay,
+                     max_grad_norm=getattr(args_cfg, "max_grad_norm", None)).publish_to(model)
     lr_scheduler = torch.optim.lr_scheduler.LambdaLR(
         optimizer=optimizer, lr_lambda=hostlogic.get_lr_schedule(args_cfg.num_warmup_epochs, args_cfg.num_static_epochs, args_cfg.lr_decay))
     return model, optimizer, lr_scheduler
@@ -83,6 +84,12 @@ def train(cfg, model, optimizer, lr_scheduler, vocab, train_dataloader, valid_da
     eval_target = None
     history = []
     runner = None
+    # cfg.max_grad_norm: the optimiser clips at this global norm inside step(); the loop only adds the device-side norm and the
+    # "was clipped" flag into two device scalars per step and reads them once per epoch (optim.ClipMonitor)
+    clip = None
+    if getattr(cfg, "max_grad_norm", None) is not None:
+        from .optim import ClipMonitor
+        clip = ClipMonitor(optimizer)
     best_ckpt_path, last_ckpt_path, all_ckpt_path = Path(best_ckpt_path), Path(last_ckpt_path), Path(all_ckpt_path)
     best_ckpt_path.mkdir(parents=True, exist_ok=True)
     last_ckpt_path.mkdir(parents=True, exist_ok=True)
@@ -111,6 +118,8 @@ def train(cfg, model, optimizer, lr_scheduler, vocab, train_dataloader, valid_da
                 outputs = model(**batch_x)
                 outputs["loss"].backward()
                 optimizer.step()
+            if clip is not None:
+                clip.update()
             sum_train_loss += float(outputs["loss"].detach())
             log(f"\tepoch {epoch + 1} ~ batch {subset_random_idx + 1}/{epoch_train_steps}, train_loss: {float(outputs['loss'].detach()):.4f}")
             subset_random_idx += 1
@@ -136,6 +145,8 @@ def train(cfg, model, optimizer, lr_scheduler, vocab, train_dataloader, valid_da
         pickle.dump(model.get_config(), open(last_ckpt_path / "model_cfg.pkl", "wb"))
         epoch_log = dict(val_logs, epoch=epoch, mean_train_loss=sum_train_loss / max(epoch_train_steps, 1),
                          lr=optimizer.param_groups[0]["lr"], saved=bool(better), trained_batches=subset_random_idx)
+        if clip is not None:
+            epoch_log.update(clip.epoch_log())
         history.append(epoch_log)
         log(f"Epoch {epoch + 1}/{cfg.num_epochs} -> lr: {epoch_log['lr']}| mean_train_loss: {epoch_log['mean_train_loss']}| "
             f"mean_val_loss: {val_logs['mean_val_loss']}| val_per: {val_logs['mean_val_per']}")
@@ -233,6 +244,8 @@ def main(argv=None):
     ap.add_argument("--batch_size", type=int, default=16)
     ap.add_argument("--seconds", type=float, default=10.0)
     ap.add_argument("--learning_rate", type=float, default=5e-6)
+    ap.add_argument("--max_grad_norm", type=float, default=None,
+                    help="clip the gradients at this global 2-norm inside the optimiser step (off by default)")
     ap.add_argument("--save_all_epochs", action="store_true")
     ap.add_argument("--out", default="pr_exp")
     a = ap.parse_args(argv)
@@ -246,7 +259,7 @@ def main(argv=None):
             model_dir = tmp
         cfg = default_cfg(num_epochs=a.num_epochs, batch_size=a.batch_size, samples_per_epoch=a.samples_per_epoch,
                           learning_rate=a.learning_rate, save_all_epochs=a.save_all_epochs, huggingface_model_id=model_dir,
-                          pretrain_cfg=w2v)
+                          pretrain_cfg=w2v, max_grad_norm=a.max_grad_norm)
         model, optimizer, lr_scheduler = load_model_optimizer(cfg, vocab)
     tr = torch.utils.data.DataLoader(SyntheticCommonPhone(a.train_items, a.seconds, len(vocab), seed=1), batch_size=a.batch_size,
                                      shuffle=True, drop_last=True, collate_fn=hostlogic.collate_pr)

@@ -252,6 +252,29 @@ int aptai_cast_multi(const int64_t* table_dev, int64_t njobs, int64_t max_n, voi
  * forward reads).  Bias corrections 1 - beta^step are evaluated per job in double, as torch does on the host. */
 int aptai_adam_multi(const int64_t* table_dev, const int64_t* dyn_dev, int64_t njobs, int64_t max_n, float lr, float beta1,
                      float beta2, float eps, float weight_decay, void* stream);
+/* Global-norm gradient clipping.  The three entries below replace `torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm)`
+ * before the `optimizer.step()` of train/train_*.py (the HF Trainer's max_grad_norm); they read the Adam job tables above: numel is
+ * column 4 of the static rows, the gradient pointer column 0 of the per-step rows, a job with a null gradient contributes exact zeros
+ * (it owns no partial: the sums are those of the table without that row).
+ *
+ * aptai_grad_sqnorm_multi, two launches on the stream: (1) one block per 4096-element chunk (the chunking of aptai_adam_multi) sums
+ * the squares in fp32 in a fixed order and stores one partial at partials_dev[chunks of the jobs before it + chunk index];
+ * partials_dev: room for fp32 [sum over jobs of ceil(n / 4096)].  (2) ONE block adds the partials in double - thread t takes t, t + 256, ...
+ * in index order, then a fixed tree - takes the root in double and writes result_dev: fp32 [3] = {total_norm,
+ * coef = min(1, max_norm / (total_norm + 1e-6)) evaluated in double and rounded once, number of gradient elements}.  NaN propagates;
+ * total_norm = inf gives coef 0; max_norm = inf gives coef 1 (measure only).  No atomics: the summation order is a function of the
+ * two tables, the same gradients give the same bits.  One table may span several parameter groups (one norm over all of them). */
+int aptai_grad_sqnorm_multi(const int64_t* table_dev, const int64_t* dyn_dev, int64_t njobs, int64_t max_n, float* partials_dev,
+                            float* result_dev, double max_norm, void* stream);
+/* aptai_adam_multi on the gradient g * (*grad_scale_dev) (one rounded fp32 multiply, then the same update: weight decay is added to the
+ * scaled gradient, as torch does after clip_grad_norm_).  The coefficient is read from device memory - result_dev + 1 of the call
+ * above - so nothing is read back; the gradients themselves are NOT modified. */
+int aptai_adam_multi_scaled(const int64_t* table_dev, const int64_t* dyn_dev, int64_t njobs, int64_t max_n, float lr, float beta1,
+                            float beta2, float eps, float weight_decay, const float* grad_scale_dev, void* stream);
+/* g *= *scale_dev in place for every job with a gradient (the in-place half of clip_grad_norm_, for a user's own loop): the same
+ * single rounded multiply as aptai_adam_multi_scaled, so scale-then-step equals the fused step bit for bit. */
+int aptai_scale_multi(const int64_t* table_dev, const int64_t* dyn_dev, int64_t njobs, int64_t max_n, const float* scale_dev,
+                      void* stream);
 /* nn.Conv1d weight [N][C][Kw] (HF:260-266) -> [N][Kw*C] bf16, K index = kw*C + c (channels-last frames) */
 int aptai_conv_weight_to_bf16(const float* src, void* dst, int64_t N, int64_t C, int64_t Kw, void* stream);
 /* positional conv (HF:329-356): weight_norm(dim=2) w = g*v/||v||_(0,1) ; v [H][H/groups][Kw], gain [Kw];
