@@ -112,6 +112,9 @@ ARGTYPES = {
     "aptai_eval_boundary_counts": [_P, _I64, _P, _P, _I64, _P, ctypes.c_double, _I64, _P, _P],
     "aptai_eval_collapse_runs": [_P, _I64, _P, _I64, _P, _I64, _P, _P],
     "aptai_eval_edit_distance": [_P, _I64, _P, _P, _I64, _P, _I64, _P, _P],
+    "aptai_resample_batch": [_P, _I, _P, _I64, _P, _P, _I64, _I64, _I64, _I64, _P, _P, _I64, _I64, _P],
+    "aptai_wave_normalize": [_P, _I64, _P, _I64, _I64, _P, _P],
+    "aptai_wave_normalize_workspace_bytes": [_I64, _I64],
     "aptai_device_check": [ctypes.c_char_p, _I],
     "aptai_set_seed_salt": [_P, _P],
     "aptai_set_frame_bounds": [_P, _P],

@@ -478,6 +478,100 @@ def resample(waveform, orig_freq: int, new_freq: int = 16000, lowpass_filter_wid
     return y[0] if squeeze else y
 
 
+def resample_out_length(n: int, orig: int, new: int) -> int:
+    """``ceil(new * n / orig)`` in integer arithmetic: the number of samples `resample` returns for `n` input samples."""
+    return (int(new) * int(n) + int(orig) - 1) // int(orig)
+
+
+def resample_taps(orig_freq: int, new_freq: int, lowpass_filter_width: int = 6, rolloff: float = 0.99) -> dict:
+    """The windowed-sinc filter bank `resample` builds, in fp64, without its clamped entries: what aptai_resample_batch reads.
+
+    The full bank is [new][2 width + orig] (orig, new = the rates over their gcd); row p is the filter of the output samples
+    n = q new + p.  Wherever |t base| >= lowpass_filter_width the clamp puts the Hann window at cos^2(pi/2): such an entry is below
+    2e-49 and at most 2 width + 1 entries per row are not of that kind.  Returns dict(taps fp64 [new][Kc], first int64 [new],
+    orig, new, width) with full[p][first[p] + j] == taps[p][j] and only clamped entries outside, so that
+
+        y[q new + p] = sum_j taps[p][j] x[q orig + first[p] + j - width],   x = 0 outside [0, len).
+
+    Kc is the largest unclamped count made odd (rows of an odd pitch start on different LDS banks); a row is shifted left where
+    it would otherwise run past the bank's end.  Equal rates give the identity table (one tap of 1.0, width 0)."""
+    import math
+    orig_freq, new_freq = int(orig_freq), int(new_freq)
+    if orig_freq <= 0 or new_freq <= 0:
+        raise ValueError(f"sampling rates must be positive, got {orig_freq} -> {new_freq}")
+    g = math.gcd(orig_freq, new_freq)
+    orig, new = orig_freq // g, new_freq // g
+    if orig == new:
+        return {"taps": np.ones((1, 1)), "first": np.zeros(1, dtype=np.int64), "orig": 1, "new": 1, "width": 0}
+    base = min(orig, new) * rolloff
+    width = math.ceil(lowpass_filter_width * orig / base)
+    full_w = 2 * width + orig
+    # per row the unclamped entries form one run around k = width + p orig / new; rows are built one at a time so that a ratio
+    # such as 16001 -> 16000 (a full bank of 16000 x 16015 entries) never exists in memory
+    half = lowpass_filter_width * orig / base                      # |k - centre| < half  <=>  unclamped (up to rounding: checked below)
+    span = 2 * int(math.ceil(half)) + 3
+    p = np.arange(new, dtype=np.int64)
+    k0 = np.clip(np.floor(width + p * orig / new - half).astype(np.int64) - 1, 0, max(full_w - span, 0))
+    k = k0[:, None] + np.arange(min(span, full_w), dtype=np.int64)[None, :]          # candidate columns, [new][span]
+
+    def t_of(cols):                                                # `resample`'s own expression, operation for operation
+        return (-(p.reshape((-1,) + (1,) * (cols.ndim - 1)).astype(np.float64)) / new + (cols - width).astype(np.float64) / orig) * base
+
+    t_raw = t_of(k)
+    t = np.clip(t_raw, -lowpass_filter_width, lowpass_filter_width)
+    live = np.abs(t_raw) < lowpass_filter_width
+    window = np.cos(t * math.pi / lowpass_filter_width / 2) ** 2
+    tp = t * math.pi
+    vals = np.where(tp == 0, 1.0, np.sin(tp) / np.where(tp == 0, 1.0, tp)) * window * (base / orig)
+    # t grows with k, so the unclamped entries of a row are one run: the window holds all of them if its two neighbours are clamped
+    left, right = k[:, 0] - 1, k[:, -1] + 1
+    assert (((left < 0) | (np.abs(t_of(left)) >= lowpass_filter_width))
+            & ((right >= full_w) | (np.abs(t_of(right)) >= lowpass_filter_width))).all(), "unclamped entry outside the candidate window"
+    count = live.sum(axis=1)
+    Kc = int(count.max())
+    Kc += 1 - Kc % 2
+    assert Kc <= 2 * width + 1 <= full_w
+    first_live = np.argmax(live, axis=1)
+    j0 = np.minimum(first_live, k.shape[1] - Kc)                   # row start inside the candidate window
+    j0 = np.minimum(j0, (full_w - Kc) - k0)                        # ... and inside the bank
+    assert (j0 >= 0).all() and (j0 <= first_live).all()
+    cols = j0[:, None] + np.arange(Kc)[None, :]
+    taps = np.take_along_axis(vals, cols, axis=1)
+    assert (np.take_along_axis(live, cols, axis=1).sum(axis=1) == count).all()
+    return {"taps": np.ascontiguousarray(taps), "first": (k0 + j0).astype(np.int64), "orig": orig, "new": new, "width": int(width)}
+
+
+def _pack_audio(batch: List[dict]):
+    """The items' audio back to back in one 1-D tensor (their own dtype: float32, or int16 PCM) and int64 offsets [B + 1]."""
+    waves = [torch.as_tensor(x["audio"]).reshape(-1) for x in batch]
+    lens = [int(x["audio_len"]) for x in batch]
+    offsets = torch.zeros(len(batch) + 1, dtype=torch.long)
+    offsets[1:] = torch.cumsum(torch.LongTensor(lens), 0)
+    return (torch.cat(waves) if waves else torch.zeros(0)), offsets
+
+
+def collate_pr_raw(batch: List[dict]) -> Dict[str, torch.Tensor]:
+    """`collate_pr` for audio at its native rate: no padding on the host - `audio_packed` holds the utterances back to back,
+    `audio_offsets` int64 [B + 1] their running lengths; aptai_amd.frontend turns the pair into `input_values` / `input_lengths`
+    on the device.  The labels are `collate_pr`'s."""
+    packed, offsets = _pack_audio(batch)
+    return {"audio_packed": packed, "audio_offsets": offsets,
+            "phoneme_labels": _pad([torch.IntTensor(x["phoneme_label"]) for x in batch], -100)}
+
+
+def collate_aptai_raw(batch: List[dict], with_phoneme_labels: bool = False) -> Dict[str, torch.Tensor]:
+    """`collate_aptai` for audio at its native rate (see collate_pr_raw): `audio_packed` + `audio_offsets` instead of
+    `audio_inputs` + `audio_lengths`; frame labels, phoneme labels and TV targets exactly as `collate_aptai` pads them."""
+    packed, offsets = _pack_audio(batch)
+    out = {"audio_packed": packed, "audio_offsets": offsets}
+    if with_phoneme_labels:
+        out["phoneme_labels"] = _pad([torch.IntTensor(x["phoneme_label"]) for x in batch], -100)
+    out["phn_frames_49hz"] = _pad([torch.LongTensor(x["phn_frames_49hz"]) for x in batch], 0)
+    for name in TV_NAMES:
+        out[name] = _pad([torch.from_numpy(np.asarray(x["tvs_norm_49hz"][name])) for x in batch], -100.0)
+    return out
+
+
 def convert_ts_float(input_string: str):
     """'[(0.0, 0.1), (0.1, 0.25)]' -> [(0.0, 0.1), (0.1, 0.25)] (utility.py:298-309)."""
     s = input_string.replace('[', '').replace(']', '').replace(' ', '')

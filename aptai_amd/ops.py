@@ -959,6 +959,49 @@ def eval_edit_distance(a_i32, lda, a_lens_i32, b_i32, ldb, b_lens_i32, B):
     return dist
 
 
+# ----------------------------------------------------------------------------- audio front end (csrc/frontend.hip)
+RESAMPLE_MAX_TABLE = 1 << 22            # APTAI_RESAMPLE_MAX_TABLE
+
+
+def _i64_vec(t, n, name, what):
+    if t.dtype != torch.int64 or t.numel() != n or not t.is_contiguous():
+        raise _lib.AptaiHipError(f"{name}: {what} must be a contiguous int64 device vector of {n} entries")
+
+
+def resample_batch(packed, offsets_i64, B, taps_f32, first_i32, orig, new, Kc, width, out, ncols, out_start_i64=None):
+    """Resamples the B utterances packed back to back in `packed` (1-D float32 or int16) into the first `ncols` columns of
+    `out` fp32 [B][ld] - see aptai_resample_batch.  `taps_f32` [new][Kc] / `first_i32` [new] from hostlogic.resample_taps (both may
+    be None when orig == new).  No synchronisation."""
+    _dev(packed, offsets_i64, taps_f32, first_i32, out, out_start_i64)
+    if packed.dtype not in (torch.float32, torch.int16) or packed.dim() != 1 or not packed.is_contiguous():
+        raise _lib.AptaiHipError("resample_batch: the packed source must be a contiguous 1-D float32 or int16 tensor")
+    if out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != B or out.stride(1) != 1 or ncols > out.shape[1]:
+        raise _lib.AptaiHipError(f"resample_batch: the output must be fp32 [{B}][>= {ncols}] with unit column stride")
+    _i64_vec(offsets_i64, B + 1, "resample_batch", "offsets")
+    if out_start_i64 is not None:
+        _i64_vec(out_start_i64, B, "resample_batch", "out_start")
+    if orig != new:
+        if (taps_f32 is None or first_i32 is None or taps_f32.dtype != torch.float32 or first_i32.dtype != torch.int32
+                or taps_f32.numel() != new * Kc or first_i32.numel() != new or not taps_f32.is_contiguous() or not first_i32.is_contiguous()):
+            raise _lib.AptaiHipError(f"resample_batch: taps fp32 [{new}][{Kc}] and first int32 [{new}] expected")
+    _lib.call("aptai_resample_batch", packed.data_ptr(), int(packed.dtype == torch.int16), offsets_i64.data_ptr(), B, _ptr(taps_f32),
+              _ptr(first_i32), orig, new, Kc, width, _ptr(out_start_i64), out.data_ptr(), out.stride(0), ncols, _stream())
+    return out
+
+
+def wave_normalize(x, lens_i64, ncols=None):
+    """zero_mean_unit_var_norm in place over the first lens[b] samples of every row of x fp32 [B][ld] - see aptai_wave_normalize."""
+    _dev(x, lens_i64)
+    if x.dtype != torch.float32 or x.dim() != 2 or x.stride(1) != 1:
+        raise _lib.AptaiHipError("wave_normalize: fp32 [B][ld] with unit column stride expected")
+    B = x.shape[0]
+    ncols = x.shape[1] if ncols is None else int(ncols)
+    _i64_vec(lens_i64, B, "wave_normalize", "lengths")
+    ws = _ws(max(_lib.lib().aptai_wave_normalize_workspace_bytes(B, ncols), 8), x.device)
+    _lib.call("aptai_wave_normalize", x.data_ptr(), x.stride(0), lens_i64.data_ptr(), B, ncols, ws.data_ptr(), _stream())
+    return x
+
+
 # ----------------------------------------------------------------------------- Force_APTAI heads (fp32)
 _SCRATCH32 = {}
 

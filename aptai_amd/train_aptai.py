@@ -31,8 +31,12 @@ class SyntheticHPRC(torch.utils.data.Dataset):
     """Items shaped like data/dataset_hprc.py's (audio, audio_len, phn_frames_49hz, tvs_norm_49hz[9 tracks]) with the
     synthetic content SURVEY.md §8d prescribes: N(0,1) audio, uniform frame labels, N(0,1) trajectories."""
 
-    def __init__(self, n_items: int, seconds: float = 10.0, vary_length: bool = True, seed: int = 0, cfg: Optional[W2V2Config] = None):
-        self.n, self.S, self.vary, self.seed = n_items, int(16000 * seconds), vary_length, seed
+    def __init__(self, n_items: int, seconds: float = 10.0, vary_length: bool = True, seed: int = 0, cfg: Optional[W2V2Config] = None,
+                 source_rate: Optional[int] = None):
+        # source_rate: the audio is emitted at that rate (`audio_len` = the raw length); frame labels and TV targets are sized
+        # from the 16 kHz length ceil(16000 n / source_rate) the device front end produces
+        self.rate = int(source_rate or 16000)
+        self.n, self.S, self.vary, self.seed = n_items, int(self.rate * seconds), vary_length, seed
         self.cfg = cfg or W2V2Config.base()
 
     def __len__(self):
@@ -41,10 +45,20 @@ class SyntheticHPRC(torch.utils.data.Dataset):
     def __getitem__(self, i):
         g = np.random.RandomState(self.seed * 100003 + i)
         n = self.S if (not self.vary or i % 2 == 0) else int(g.randint(int(0.8 * self.S), self.S + 1))
-        T = int(hostlogic.feat_extract_output_lengths(n, self.cfg.conv_kernel, self.cfg.conv_stride))
+        T = int(hostlogic.feat_extract_output_lengths(hostlogic.resample_out_length(n, self.rate, 16000), self.cfg.conv_kernel,
+                                                      self.cfg.conv_stride))
         labels = np.repeat(g.randint(1, VOCAB_SIZE, size=T // 4 + 1), 4)[:T]        # phone-like runs of 4 frames
         return {"audio": g.randn(n).astype(np.float32), "audio_len": n, "phn_frames_49hz": labels.astype(np.int64),
                 "tvs_norm_49hz": {k: g.randn(T) for k in hostlogic.TV_NAMES}}
+
+
+def _to_device(batch_x, device, frontend=None, host_lengths=False):
+    """The collate's batch on the device.  With a front end (cfg.source_rate / cfg.normalize_audio) the batch is a `collate_*_raw`
+    one: its packed audio is uploaded as it is and resampled / normalised there into `audio_inputs` / `audio_lengths`."""
+    if frontend is None:
+        return {k: v.to(device) for k, v in batch_x.items()}
+    from .frontend import raw_batch_to_device
+    return raw_batch_to_device(batch_x, frontend, device, "audio_inputs", "audio_lengths", host_lengths=host_lengths)
 
 
 def load_model_optimizer(args_cfg):
@@ -68,6 +82,8 @@ def train(cfg, model, optimizer, lr_scheduler, train_dataloader, valid_dataloade
     eval_target = None
     history = []
     runner = None
+    from .frontend import make_frontend
+    frontend = make_frontend(cfg)            # None unless cfg.source_rate / cfg.normalize_audio: then the loaders use collate_aptai_raw
     # cfg.max_grad_norm: the optimiser clips at this global norm inside step(); the loop only adds the device-side norm and the
     # "was clipped" flag into two device scalars per step and reads them once per epoch (optim.ClipMonitor)
     clip = None
@@ -88,9 +104,10 @@ def train(cfg, model, optimizer, lr_scheduler, train_dataloader, valid_dataloade
                 if runner is None:
                     from .graphed import BucketedGraphedStep
                     runner = BucketedGraphedStep(model, optimizer)
-                outputs = runner.step(batch_x)
+                # (with a front end it runs eagerly first: its output is the device batch the runners take as well)
+                outputs = runner.step(batch_x if frontend is None else _to_device(batch_x, cfg.device, frontend, host_lengths=True))
             else:
-                batch_x = {k: v.to(cfg.device) for k, v in batch_x.items()}
+                batch_x = _to_device(batch_x, cfg.device, frontend)
                 optimizer.zero_grad()
                 outputs = model(epoch, **batch_x)
                 outputs["loss"].backward()
@@ -107,7 +124,7 @@ def train(cfg, model, optimizer, lr_scheduler, train_dataloader, valid_dataloade
             runner.suspend()             # the eager validation below rebuilds its weight copies; the captured buckets stay
         model.eval()
         val_logs = validate(model, cfg.device, cfg.vocab, epoch, getattr(cfg, "exp_dir", None), test_spk, valid_dataloader,
-                            device_metrics=getattr(cfg, "device_metrics", False))
+                            device_metrics=getattr(cfg, "device_metrics", False), frontend=frontend)
         better = (eval_target is None
                   or (cfg.target_metric_bigger_better and eval_target <= val_logs[cfg.target_metric])
                   or (not cfg.target_metric_bigger_better and eval_target >= val_logs[cfg.target_metric]))
@@ -126,14 +143,14 @@ def train(cfg, model, optimizer, lr_scheduler, train_dataloader, valid_dataloade
     return history
 
 
-def _device_eval(model, device, epoch, dl, acc):
+def _device_eval(model, device, epoch, dl, acc, frontend=None):
     """The evaluation pass of validate()/test() with `device_metrics=True`: the same forward, the metrics of every utterance of
     the batch computed by the kernels of aptai_amd.device_metrics and left on the device (no blocking call per batch).  Any batch
     size: frame counts come from `audio_lengths` through the encoder's length formula."""
     from . import device_metrics as dm
     for batch_x in dl:
         with torch.no_grad():
-            batch_x = {k: v.to(device) for k, v in batch_x.items()}
+            batch_x = _to_device(batch_x, device, frontend)
             tvs_gt = _stack_gt(batch_x)
             outputs = model(epoch, **batch_x)
         tvs_pred = outputs["tvs_pred"]
@@ -144,13 +161,13 @@ def _device_eval(model, device, epoch, dl, acc):
     return acc.result()
 
 
-def validate(model, device, vocab, epoch, exp_dir, test_spk, val_dl, log_step=100, device_metrics=False) -> Dict[str, float]:
+def validate(model, device, vocab, epoch, exp_dir, test_spk, val_dl, log_step=100, device_metrics=False, frontend=None) -> Dict[str, float]:
     """train/train_aptai.py:533-652, batch size 1.  Reproduces the reference as written, including its two quirks: the ground
     truth stack lists TTCD in the TMCD slot (:557-560) and `get_stats` receives frame label sequences, not boundary times.
     `device_metrics=True` (opt-in) computes the same entries with aptai_amd.device_metrics: one device->host transfer per call."""
     if device_metrics:
         from .device_metrics import EvalAccumulator
-        return _device_eval(model, device, epoch, val_dl, EvalAccumulator("val", per="frames_rounded"))
+        return _device_eval(model, device, epoch, val_dl, EvalAccumulator("val", per="frames_rounded"), frontend=frontend)
     val_losses, val_rmses, val_pccs, val_overlaps = [], [], [], []
     val_ps, val_rs, val_f1s, val_rvals, edit_d, n_phn = [], [], [], [], [], []
     total_frames = corr_frames = 0
@@ -158,7 +175,7 @@ def validate(model, device, vocab, epoch, exp_dir, test_spk, val_dl, log_step=10
         with torch.no_grad():
             tvs_gt = torch.stack([batch_x["LA"], batch_x["LP"], batch_x["JA"], batch_x["TTCL"], batch_x["TTCD"], batch_x["TMCL"],
                                   batch_x["TTCD"], batch_x["TBCL"], batch_x["TBCD"]], dim=-1).float()
-            batch_x = {k: v.to(device) for k, v in batch_x.items()}
+            batch_x = _to_device(batch_x, device, frontend)
             outputs = model(epoch, **batch_x)
         val_losses.append(outputs["loss"].item())
         tvs_gt = torch.squeeze(tvs_gt, dim=0).cpu().numpy()
@@ -215,7 +232,8 @@ def _tv_test_summary(rate, rmse_tvs, pcc_tvs, with_std=False):
     return out
 
 
-def test(model, device, vocab, exp_dir, test_spk, test_dl, rate, log_step=100, num_epochs=0, device_metrics=False) -> Dict[str, float]:
+def test(model, device, vocab, exp_dir, test_spk, test_dl, rate, log_step=100, num_epochs=0, device_metrics=False,
+         frontend=None) -> Dict[str, float]:
     """train/train_aptai.py:655-850, batch size 1: per-track RMSE / PCC means, FER, frame-grouped PER, overlap, boundary scores,
     keyed `test_{rate}_...` with rate in {'F', 'N'} (fast / normal speaking rate splits of the corpus).  `num_epochs` stands for
     the module-global `cfg.num_epochs` the reference passes as the epoch argument (:709)."""
@@ -223,7 +241,7 @@ def test(model, device, vocab, exp_dir, test_spk, test_dl, rate, log_step=100, n
     if device_metrics:
         from .device_metrics import EvalAccumulator
         model.eval()
-        return _device_eval(model, device, num_epochs, test_dl, EvalAccumulator("test", rate=rate, per="frames"))
+        return _device_eval(model, device, num_epochs, test_dl, EvalAccumulator("test", rate=rate, per="frames"), frontend=frontend)
     names = hostlogic.TV_NAMES
     rmse_tvs, pcc_tvs = {n: [] for n in names}, {n: [] for n in names}
     overlaps, ps, rs, f1s, rvals, edit_d, n_phn = [], [], [], [], [], [], []
@@ -232,7 +250,7 @@ def test(model, device, vocab, exp_dir, test_spk, test_dl, rate, log_step=100, n
     for batch_x in test_dl:
         with torch.no_grad():
             tvs_gt = _stack_gt(batch_x)
-            batch_x = {k: v.to(device) for k, v in batch_x.items()}
+            batch_x = _to_device(batch_x, device, frontend)
             outputs = model(num_epochs, **batch_x)
         tvs_gt = torch.squeeze(tvs_gt, dim=0).cpu().numpy()
         tvs_pred = torch.squeeze(outputs["tvs_pred"], dim=0).float().cpu().numpy()
@@ -262,7 +280,8 @@ def default_cfg(**kw):
     cfg = SimpleNamespace(device="cuda", num_epochs=2, batch_size=16, learning_rate=1e-5, adam_beta1=0.9, adam_beta2=0.999,
                           adam_epsilon=1e-8, adam_weight_decay=0.0, num_warmup_epochs=10, num_static_epochs=30, lr_decay=0.96,
                           target_metric="val_mean_rmse", target_metric_bigger_better=False, graphed=False, exp_dir=None,
-                          vocab={f"p{i}": i for i in range(VOCAB_SIZE)}, cache_dir=None, device_metrics=False)
+                          vocab={f"p{i}": i for i in range(VOCAB_SIZE)}, cache_dir=None, device_metrics=False,
+                          source_rate=None, normalize_audio=False)
     cfg.__dict__.update(kw)
     return cfg
 
@@ -279,6 +298,9 @@ def main(argv=None):
     ap.add_argument("--learning_rate", type=float, default=1e-5)
     ap.add_argument("--max_grad_norm", type=float, default=None,
                     help="clip the gradients at this global 2-norm inside the optimiser step (off by default)")
+    ap.add_argument("--source_rate", type=int, default=None,
+                    help="the corpus' sampling rate: the audio is uploaded at that rate and resampled to 16 kHz on the device")
+    ap.add_argument("--normalize_audio", action="store_true", help="zero-mean / unit-variance normalisation on the device")
     ap.add_argument("--graphed", action="store_true")
     ap.add_argument("--out", default="aptai_ckpt")
     a = ap.parse_args(argv)
@@ -290,12 +312,14 @@ def main(argv=None):
             Wav2Vec2Model(w2v).save_pretrained(tmp)
             model_dir = tmp
         cfg = default_cfg(num_epochs=a.num_epochs, batch_size=a.batch_size, learning_rate=a.learning_rate, graphed=a.graphed,
-                          huggingface_model_id=model_dir, pretrain_cfg=w2v, max_grad_norm=a.max_grad_norm)
+                          huggingface_model_id=model_dir, pretrain_cfg=w2v, max_grad_norm=a.max_grad_norm, source_rate=a.source_rate,
+                          normalize_audio=a.normalize_audio)
         model, optimizer, lr_scheduler = load_model_optimizer(cfg)
-    train_ds = SyntheticHPRC(a.steps_per_epoch * a.batch_size, a.seconds, vary_length=True, seed=1, cfg=w2v)
-    val_ds = SyntheticHPRC(a.val_items, a.seconds, vary_length=True, seed=2, cfg=w2v)
-    train_dl = torch.utils.data.DataLoader(train_ds, batch_size=a.batch_size, shuffle=True, drop_last=True, collate_fn=hostlogic.collate_aptai)
-    val_dl = torch.utils.data.DataLoader(val_ds, batch_size=1, shuffle=False, collate_fn=hostlogic.collate_aptai)
+    train_ds = SyntheticHPRC(a.steps_per_epoch * a.batch_size, a.seconds, vary_length=True, seed=1, cfg=w2v, source_rate=a.source_rate)
+    val_ds = SyntheticHPRC(a.val_items, a.seconds, vary_length=True, seed=2, cfg=w2v, source_rate=a.source_rate)
+    collate = hostlogic.collate_aptai_raw if (a.source_rate or a.normalize_audio) else hostlogic.collate_aptai
+    train_dl = torch.utils.data.DataLoader(train_ds, batch_size=a.batch_size, shuffle=True, drop_last=True, collate_fn=collate)
+    val_dl = torch.utils.data.DataLoader(val_ds, batch_size=1, shuffle=False, collate_fn=collate)
     return train(cfg, model, optimizer, lr_scheduler, train_dl, val_dl, "synthetic", a.out)
 
 

@@ -21,7 +21,7 @@ import torch
 
 from . import hostlogic, metrics
 from .force_aptai import Force_APTAI
-from .train_aptai import SyntheticHPRC, _eval_frames, _stack_gt, _tv_test_summary
+from .train_aptai import SyntheticHPRC, _eval_frames, _stack_gt, _to_device, _tv_test_summary
 
 
 class SyntheticHPRCWithLabels(SyntheticHPRC):
@@ -43,6 +43,11 @@ def collate(batch):
     return hostlogic.collate_aptai(batch, with_phoneme_labels=True)
 
 
+def collate_raw(batch):
+    """`collate` for a corpus at its native rate (cfg.source_rate / cfg.normalize_audio): packed audio + offsets."""
+    return hostlogic.collate_aptai_raw(batch, with_phoneme_labels=True)
+
+
 def load_model_optimizer(args_cfg):
     """train/train_force_aptai.py:328-368: Force_APTAI over a trained recogniser checkpoint, Adam over the parameters that
     require gradients (the heads), LambdaLR with the 10x warm-up schedule."""
@@ -60,6 +65,8 @@ def train(cfg, model, optimizer, lr_scheduler, train_dataloader, valid_dataloade
     """train/train_force_aptai.py:392-531.  Returns the per-epoch log dicts."""
     eval_target = None
     history = []
+    from .frontend import make_frontend
+    frontend = make_frontend(cfg)            # None unless cfg.source_rate / cfg.normalize_audio: then the loaders use collate_raw
     # cfg.max_grad_norm: the optimiser clips at this global norm inside step(); the loop only adds the device-side norm and the
     # "was clipped" flag into two device scalars per step and reads them once per epoch (optim.ClipMonitor)
     clip = None
@@ -77,13 +84,13 @@ def train(cfg, model, optimizer, lr_scheduler, train_dataloader, valid_dataloade
         it = iter(train_dataloader)
         nxt = next(it, None)
         if nxt is not None:
-            nxt = {k: v.to(cfg.device) for k, v in nxt.items()}
+            nxt = _to_device(nxt, cfg.device, frontend)
         batch_idx = -1
         while nxt is not None:
             batch_idx += 1
             batch_x, nxt = nxt, next(it, None)
             if nxt is not None:
-                nxt = {k: v.to(cfg.device) for k, v in nxt.items()}
+                nxt = _to_device(nxt, cfg.device, frontend)
             optimizer.zero_grad()
             ahead = (nxt["audio_inputs"], nxt["audio_lengths"]) if (pipelined and nxt is not None) else None
             outputs = model(epoch, **batch_x, _prefetch_next=ahead)
@@ -99,7 +106,7 @@ def train(cfg, model, optimizer, lr_scheduler, train_dataloader, valid_dataloade
         lr_scheduler.step()
         model.eval()
         val_logs = validate(model, cfg.device, cfg.vocab, epoch, getattr(cfg, "exp_dir", None), test_spk, valid_dataloader,
-                            device_metrics=getattr(cfg, "device_metrics", False))
+                            device_metrics=getattr(cfg, "device_metrics", False), frontend=frontend)
         better = (eval_target is None
                   or (cfg.target_metric_bigger_better and eval_target <= val_logs[cfg.target_metric])
                   or (not cfg.target_metric_bigger_better and eval_target >= val_logs[cfg.target_metric]))
@@ -116,12 +123,12 @@ def train(cfg, model, optimizer, lr_scheduler, train_dataloader, valid_dataloade
     return history
 
 
-def _one_file(model, device, epoch, batch_x):
+def _one_file(model, device, epoch, batch_x, frontend=None):
     """One batch-1 evaluation pass shared by validate() and test(): TV arrays, CTC-based edit distance (:578-586), frame scores
     with `pred_frame_phns` as the prediction (:588-600)."""
     with torch.no_grad():
         tvs_gt = _stack_gt(batch_x)
-        batch_x = {k: v.to(device) for k, v in batch_x.items()}
+        batch_x = _to_device(batch_x, device, frontend)
         outputs = model(epoch, **batch_x)
     tvs_gt = torch.squeeze(tvs_gt, dim=0).cpu().numpy()
     tvs_pred = torch.squeeze(outputs["tvs_pred"], dim=0).float().cpu().numpy()
@@ -132,7 +139,7 @@ def _one_file(model, device, epoch, batch_x):
     return outputs, tvs_gt, tvs_pred, ed, n, _eval_frames(batch_x["phn_frames_49hz"], pred_frames)
 
 
-def _device_eval(model, device, epoch, dl, acc):
+def _device_eval(model, device, epoch, dl, acc, frontend=None):
     """validate()/test() with `device_metrics=True`: Force_APTAI's device-output route (no Python lists), every metric through
     aptai_amd.device_metrics.  The decoded-length check and the BiLSTM status words `_lists` reads per step are accumulated on
     the device and checked once in `acc.result()`."""
@@ -140,7 +147,7 @@ def _device_eval(model, device, epoch, dl, acc):
     acc.max_phonemes = model.max_phn_seq_len
     for batch_x in dl:
         with torch.no_grad():
-            batch_x = {k: v.to(device) for k, v in batch_x.items()}
+            batch_x = _to_device(batch_x, device, frontend)
             tvs_gt = _stack_gt(batch_x)
             outputs = model(epoch, **batch_x, _device_outputs=True)
         lens = outputs["frame_lens"]
@@ -154,17 +161,17 @@ def _device_eval(model, device, epoch, dl, acc):
     return acc.result()
 
 
-def validate(model, device, vocab, epoch, exp_dir, test_spk, val_dl, log_step=100, device_metrics=False) -> Dict[str, float]:
+def validate(model, device, vocab, epoch, exp_dir, test_spk, val_dl, log_step=100, device_metrics=False, frontend=None) -> Dict[str, float]:
     """train/train_force_aptai.py:533-652, batch size 1 (incl. the TTCD-twice ground-truth stack).  `device_metrics=True`
     (opt-in): the same entries from aptai_amd.device_metrics, one device->host transfer per call."""
     if device_metrics:
         from .device_metrics import EvalAccumulator
-        return _device_eval(model, device, epoch, val_dl, EvalAccumulator("val", per="edit"))
+        return _device_eval(model, device, epoch, val_dl, EvalAccumulator("val", per="edit"), frontend=frontend)
     val_losses, val_rmses, val_pccs, val_overlaps = [], [], [], []
     val_ps, val_rs, val_f1s, val_rvals, edit_d, n_phn = [], [], [], [], [], []
     total_frames = corr_frames = 0
     for batch_x in val_dl:
-        outputs, tvs_gt, tvs_pred, ed, n, (frames, corr, overlap, (p, r, f1, rval), _, _) = _one_file(model, device, epoch, batch_x)
+        outputs, tvs_gt, tvs_pred, ed, n, (frames, corr, overlap, (p, r, f1, rval), _, _) = _one_file(model, device, epoch, batch_x, frontend)
         val_losses.append(outputs["loss"].item())
         val_rmses.append(np.mean(list(metrics.tvs_metric_rmse(tvs_gt, tvs_pred).values())))
         val_pccs.append(np.mean([v[0] for v in metrics.tvs_metric_ppc(tvs_gt, tvs_pred).values()]))
@@ -182,20 +189,22 @@ def validate(model, device, vocab, epoch, exp_dir, test_spk, val_dl, log_step=10
     }
 
 
-def test(model, device, vocab, exp_dir, test_spk, test_dl, rate, log_step=100, num_epochs=0, device_metrics=False) -> Dict[str, float]:
+def test(model, device, vocab, exp_dir, test_spk, test_dl, rate, log_step=100, num_epochs=0, device_metrics=False,
+         frontend=None) -> Dict[str, float]:
     """train/train_force_aptai.py:655-838: as train_aptai.test plus the std entries and the CTC-based PER."""
     assert rate in ["F", "N"]
     if device_metrics:
         from .device_metrics import EvalAccumulator
         model.eval()
-        return _device_eval(model, device, num_epochs, test_dl, EvalAccumulator("test", rate=rate, per="edit", with_std=True))
+        return _device_eval(model, device, num_epochs, test_dl, EvalAccumulator("test", rate=rate, per="edit", with_std=True),
+                            frontend=frontend)
     names = hostlogic.TV_NAMES
     rmse_tvs, pcc_tvs = {n: [] for n in names}, {n: [] for n in names}
     overlaps, ps, rs, f1s, rvals, edit_d, n_phn, pers = [], [], [], [], [], [], [], []
     total_frames = corr_frames = 0
     model.eval()
     for batch_x in test_dl:
-        _, tvs_gt, tvs_pred, ed, n, (frames, corr, overlap, (p, r, f1, rval), _, _) = _one_file(model, device, num_epochs, batch_x)
+        _, tvs_gt, tvs_pred, ed, n, (frames, corr, overlap, (p, r, f1, rval), _, _) = _one_file(model, device, num_epochs, batch_x, frontend)
         edit_d.append(ed); n_phn.append(n); pers.append(ed / n)
         total_frames += frames
         corr_frames += corr
@@ -221,7 +230,7 @@ def default_cfg(**kw):
     cfg = SimpleNamespace(device="cuda", num_epochs=2, batch_size=5, learning_rate=1e-5, adam_beta1=0.9, adam_beta2=0.999,
                           adam_epsilon=1e-8, adam_weight_decay=0.0, num_warmup_epochs=10, num_static_epochs=30, lr_decay=0.96,
                           target_metric="val_mean_rmse", target_metric_bigger_better=False, exp_dir=None, vocab=vocab,
-                          pr_model_path=None, device_metrics=False)
+                          pr_model_path=None, device_metrics=False, source_rate=None, normalize_audio=False)
     cfg.__dict__.update(kw)
     return cfg
 
@@ -237,16 +246,21 @@ def main(argv=None):
     ap.add_argument("--learning_rate", type=float, default=1e-5)
     ap.add_argument("--max_grad_norm", type=float, default=None,
                     help="clip the gradients at this global 2-norm inside the optimiser step (off by default)")
+    ap.add_argument("--source_rate", type=int, default=None,
+                    help="the corpus' sampling rate: the audio is uploaded at that rate and resampled to 16 kHz on the device")
+    ap.add_argument("--normalize_audio", action="store_true", help="zero-mean / unit-variance normalisation on the device")
     ap.add_argument("--out", default="force_aptai_ckpt")
     a = ap.parse_args(argv)
     cfg = default_cfg(num_epochs=a.num_epochs, batch_size=a.batch_size, learning_rate=a.learning_rate, pr_model_path=a.pr_model_path,
-                      max_grad_norm=a.max_grad_norm)
+                      max_grad_norm=a.max_grad_norm, source_rate=a.source_rate, normalize_audio=a.normalize_audio)
     model, optimizer, lr_scheduler = load_model_optimizer(cfg)
     w2v = model.w2v2_pr.wav2vec2.config
-    train_ds = SyntheticHPRCWithLabels(a.steps_per_epoch * a.batch_size, a.seconds, seed=1, cfg=w2v, vocab_size=len(cfg.vocab))
-    val_ds = SyntheticHPRCWithLabels(a.val_items, a.seconds, seed=2, cfg=w2v, vocab_size=len(cfg.vocab))
-    train_dl = torch.utils.data.DataLoader(train_ds, batch_size=a.batch_size, shuffle=True, drop_last=True, collate_fn=collate)
-    val_dl = torch.utils.data.DataLoader(val_ds, batch_size=1, shuffle=False, collate_fn=collate)
+    train_ds = SyntheticHPRCWithLabels(a.steps_per_epoch * a.batch_size, a.seconds, seed=1, cfg=w2v, vocab_size=len(cfg.vocab),
+                                       source_rate=a.source_rate)
+    val_ds = SyntheticHPRCWithLabels(a.val_items, a.seconds, seed=2, cfg=w2v, vocab_size=len(cfg.vocab), source_rate=a.source_rate)
+    coll = collate_raw if (a.source_rate or a.normalize_audio) else collate
+    train_dl = torch.utils.data.DataLoader(train_ds, batch_size=a.batch_size, shuffle=True, drop_last=True, collate_fn=coll)
+    val_dl = torch.utils.data.DataLoader(val_ds, batch_size=1, shuffle=False, collate_fn=coll)
     return train(cfg, model, optimizer, lr_scheduler, train_dl, val_dl, "synthetic", a.out)
 
 

@@ -39,8 +39,12 @@ class SyntheticCommonPhone(torch.utils.data.Dataset):
     """Items shaped like data/dataset_commonphone.py's (audio, audio_len, phoneme_label): N(0,1) 16 kHz audio (optionally the
     reference's 1-second crop), 20..55 label ids in [1, V-1] (scaled down for clips that hold fewer frames)."""
 
-    def __init__(self, n_items: int, seconds: float = 10.0, vocab_size: int = 40, vary_length: bool = True, seed: int = 0):
-        self.n, self.S, self.V, self.vary, self.seed = n_items, int(16000 * seconds), vocab_size, vary_length, seed
+    def __init__(self, n_items: int, seconds: float = 10.0, vocab_size: int = 40, vary_length: bool = True, seed: int = 0,
+                 source_rate: Optional[int] = None):
+        # source_rate: the audio is emitted at that rate (`audio_len` = the raw length) and the label count is sized from the
+        # 16 kHz length ceil(16000 n / source_rate) the device front end produces
+        self.rate = int(source_rate or 16000)
+        self.n, self.S, self.V, self.vary, self.seed = n_items, int(self.rate * seconds), vocab_size, vary_length, seed
 
     def __len__(self):
         return self.n
@@ -48,11 +52,20 @@ class SyntheticCommonPhone(torch.utils.data.Dataset):
     def __getitem__(self, i):
         g = np.random.RandomState(self.seed * 100003 + i)
         n = self.S if (not self.vary or i % 2 == 0) else int(g.randint(int(0.8 * self.S), self.S + 1))
-        frames = max(n // 320 - 1, 2)
+        frames = max(hostlogic.resample_out_length(n, self.rate, 16000) // 320 - 1, 2)
         hi = max(2, min(55, frames // 3))
         lo = max(1, min(20, hi - 1))
         return {"audio": g.randn(n).astype(np.float32), "audio_len": n,
                 "phoneme_label": g.randint(1, self.V, size=int(g.randint(lo, hi + 1))).astype(np.int32)}
+
+
+def _to_device(batch_x, device, frontend=None, host_lengths=False):
+    """The collate's batch on the device.  With a front end (cfg.source_rate / cfg.normalize_audio) the batch is a `collate_*_raw`
+    one: its packed audio is uploaded as it is and resampled / normalised there into `input_values` / `input_lengths`."""
+    if frontend is None:
+        return {k: v.to(device) for k, v in batch_x.items()}
+    from .frontend import raw_batch_to_device
+    return raw_batch_to_device(batch_x, frontend, device, "input_values", "input_lengths", host_lengths=host_lengths)
 
 
 def load_model_optimizer(args_cfg, vocab):
@@ -84,6 +97,8 @@ def train(cfg, model, optimizer, lr_scheduler, vocab, train_dataloader, valid_da
     eval_target = None
     history = []
     runner = None
+    from .frontend import make_frontend
+    frontend = make_frontend(cfg)            # None unless cfg.source_rate / cfg.normalize_audio: then the loaders use collate_pr_raw
     # cfg.max_grad_norm: the optimiser clips at this global norm inside step(); the loop only adds the device-side norm and the
     # "was clipped" flag into two device scalars per step and reads them once per epoch (optim.ClipMonitor)
     clip = None
@@ -111,9 +126,9 @@ def train(cfg, model, optimizer, lr_scheduler, vocab, train_dataloader, valid_da
                 if runner is None:
                     from .graphed import BucketedGraphedStep
                     runner = BucketedGraphedStep(model, optimizer)
-                outputs = runner.step({k: v.to(cfg.device) for k, v in batch_x.items()})
+                outputs = runner.step(_to_device(batch_x, cfg.device, frontend, host_lengths=True))
             else:
-                batch_x = {k: v.to(cfg.device) for k, v in batch_x.items()}
+                batch_x = _to_device(batch_x, cfg.device, frontend)
                 optimizer.zero_grad()
                 outputs = model(**batch_x)
                 outputs["loss"].backward()
@@ -127,7 +142,8 @@ def train(cfg, model, optimizer, lr_scheduler, vocab, train_dataloader, valid_da
         if runner is not None:
             runner.suspend()             # the eager validation below rebuilds its weight copies; the captured buckets stay
         model.eval()
-        val_logs = validate(model, cfg.device, vocab, epoch, valid_dataloader, device_metrics=getattr(cfg, "device_metrics", False))
+        val_logs = validate(model, cfg.device, vocab, epoch, valid_dataloader, device_metrics=getattr(cfg, "device_metrics", False),
+                            frontend=frontend)
         better = (eval_target is None
                   or (cfg.target_metric_bigger_better and eval_target <= val_logs[cfg.target_metric])
                   or (not cfg.target_metric_bigger_better and eval_target >= val_logs[cfg.target_metric]))
@@ -165,7 +181,7 @@ def _decode(model, outputs) -> list:
     return [int(i) for i in ids[0, :int(n[0])].cpu().numpy()]
 
 
-def _device_eval(model, device, dl, acc, with_loss, laptop=False):
+def _device_eval(model, device, dl, acc, with_loss, laptop=False, frontend=None):
     """validate()/test() with `device_metrics=True`: the best-path decode's ids and lengths go straight into the device
     Levenshtein kernel; nothing is read back before `acc.result()`.  Any batch size (label counts from the -100 padding)."""
     from . import device_metrics as dm, ops
@@ -173,7 +189,7 @@ def _device_eval(model, device, dl, acc, with_loss, laptop=False):
         if laptop and batch_idx >= 1:
             break
         with torch.no_grad():
-            batch_x = {k: v.to(device) for k, v in batch_x.items()}
+            batch_x = _to_device(batch_x, device, frontend)
             outputs = model(**batch_x)
         if with_loss:
             acc.add_loss(outputs["loss"])
@@ -185,17 +201,17 @@ def _device_eval(model, device, dl, acc, with_loss, laptop=False):
     return acc.result()
 
 
-def validate(model, device, vocab, epoch, validate_dataloader, log_step=100, device_metrics=False) -> Dict[str, float]:
+def validate(model, device, vocab, epoch, validate_dataloader, log_step=100, device_metrics=False, frontend=None) -> Dict[str, float]:
     """train/train_phoneme_recognizer.py:509-561, batch size 1.  `device_metrics=True` (opt-in): the edit distances stay on the
     device (aptai_amd.device_metrics), one device->host transfer per call."""
     if device_metrics:
         from .device_metrics import EvalAccumulator
-        return _device_eval(model, device, validate_dataloader, EvalAccumulator("pr_val"), True)
+        return _device_eval(model, device, validate_dataloader, EvalAccumulator("pr_val"), True, frontend=frontend)
     val_losses, edit_d, n_phn = [], [], []
     for batch_x in validate_dataloader:
         with torch.no_grad():
             phoneme_label = batch_x["phoneme_labels"].numpy()[0]
-            batch_x = {k: v.to(device) for k, v in batch_x.items()}
+            batch_x = _to_device(batch_x, device, frontend)
             outputs = model(**batch_x)
         val_losses.append(outputs["loss"].item())
         edit_d.append(metrics.edit_distance(phoneme_label, _decode(model, outputs)))
@@ -203,19 +219,19 @@ def validate(model, device, vocab, epoch, validate_dataloader, log_step=100, dev
     return {"mean_val_per": float(np.sum(edit_d) / np.sum(n_phn)), "mean_val_loss": float(np.mean(val_losses))}
 
 
-def test(model, device, vocab, test_dl, dataset_name, log_step=100, laptop=False, device_metrics=False) -> Dict[str, float]:
+def test(model, device, vocab, test_dl, dataset_name, log_step=100, laptop=False, device_metrics=False, frontend=None) -> Dict[str, float]:
     """train/train_phoneme_recognizer.py:566-617."""
     edit_d, n_phn = [], []
     model.eval()
     if device_metrics:
         from .device_metrics import EvalAccumulator
-        return _device_eval(model, device, test_dl, EvalAccumulator("pr_test"), False, laptop=laptop)
+        return _device_eval(model, device, test_dl, EvalAccumulator("pr_test"), False, laptop=laptop, frontend=frontend)
     for batch_idx, batch_x in enumerate(test_dl):
         if laptop and batch_idx >= 1:
             break
         with torch.no_grad():
             phoneme_label = batch_x["phoneme_labels"].numpy()[0]
-            batch_x = {k: v.to(device) for k, v in batch_x.items()}
+            batch_x = _to_device(batch_x, device, frontend)
             outputs = model(**batch_x)
         edit_d.append(metrics.edit_distance(phoneme_label, _decode(model, outputs)))
         n_phn.append(len(phoneme_label))
@@ -228,7 +244,7 @@ def default_cfg(**kw):
                           adam_beta2=0.999, adam_epsilon=1e-8, adam_weight_decay=0.0, num_warmup_epochs=10, num_static_epochs=30,
                           lr_decay=0.96, target_metric="mean_val_per", target_metric_bigger_better=False, final_dropout=0.1,
                           num_hidden_layers=None, freeze_feature_extractor=False, save_all_epochs=False, cache_dir=None,
-                          device_metrics=False)
+                          device_metrics=False, source_rate=None, normalize_audio=False)
     cfg.__dict__.update(kw)
     return cfg
 
@@ -246,6 +262,9 @@ def main(argv=None):
     ap.add_argument("--learning_rate", type=float, default=5e-6)
     ap.add_argument("--max_grad_norm", type=float, default=None,
                     help="clip the gradients at this global 2-norm inside the optimiser step (off by default)")
+    ap.add_argument("--source_rate", type=int, default=None,
+                    help="the corpus' sampling rate: the audio is uploaded at that rate and resampled to 16 kHz on the device")
+    ap.add_argument("--normalize_audio", action="store_true", help="zero-mean / unit-variance normalisation on the device")
     ap.add_argument("--save_all_epochs", action="store_true")
     ap.add_argument("--out", default="pr_exp")
     a = ap.parse_args(argv)
@@ -259,12 +278,13 @@ def main(argv=None):
             model_dir = tmp
         cfg = default_cfg(num_epochs=a.num_epochs, batch_size=a.batch_size, samples_per_epoch=a.samples_per_epoch,
                           learning_rate=a.learning_rate, save_all_epochs=a.save_all_epochs, huggingface_model_id=model_dir,
-                          pretrain_cfg=w2v, max_grad_norm=a.max_grad_norm)
+                          pretrain_cfg=w2v, max_grad_norm=a.max_grad_norm, source_rate=a.source_rate, normalize_audio=a.normalize_audio)
         model, optimizer, lr_scheduler = load_model_optimizer(cfg, vocab)
-    tr = torch.utils.data.DataLoader(SyntheticCommonPhone(a.train_items, a.seconds, len(vocab), seed=1), batch_size=a.batch_size,
-                                     shuffle=True, drop_last=True, collate_fn=hostlogic.collate_pr)
-    va = torch.utils.data.DataLoader(SyntheticCommonPhone(a.val_items, a.seconds, len(vocab), seed=2), batch_size=1,
-                                     collate_fn=hostlogic.collate_pr)
+    collate = hostlogic.collate_pr_raw if (a.source_rate or a.normalize_audio) else hostlogic.collate_pr
+    tr = torch.utils.data.DataLoader(SyntheticCommonPhone(a.train_items, a.seconds, len(vocab), seed=1, source_rate=a.source_rate),
+                                     batch_size=a.batch_size, shuffle=True, drop_last=True, collate_fn=collate)
+    va = torch.utils.data.DataLoader(SyntheticCommonPhone(a.val_items, a.seconds, len(vocab), seed=2, source_rate=a.source_rate),
+                                     batch_size=1, collate_fn=collate)
     out = Path(a.out)
     return train(cfg, model, optimizer, lr_scheduler, vocab, tr, va, out / "best-model-ckpt", out / "last-model-ckpt", out / "model-ckpts")
 

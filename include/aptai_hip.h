@@ -544,6 +544,32 @@ int aptai_eval_collapse_runs(const int64_t* x, int64_t ld, const int32_t* lens, 
 int aptai_eval_edit_distance(const int32_t* a, int64_t lda, const int32_t* a_lens, const int32_t* b, int64_t ldb,
                              const int32_t* b_lens, int64_t B, int32_t* dist, void* stream);
 
+/* ------------------------------------------------------------------------------------------------ audio front end
+ * The step in front of the models that the reference runs on the host inside __getitem__ (data/dataset_commonphone.py:28-33,
+ * data/dataset_hprc.py:68-70): resampling to 16 kHz, and the feature extractor's normalisation.  Caller-owned buffers, device
+ * int64 offsets / lengths, the passed stream, no synchronisation, no atomics: equal inputs give equal bits. */
+/* torchaudio.functional.resample (sinc_interp_hann) of B utterances in one launch.  src: all utterances back to back, float32
+ * (src_is_int16 = 0) or int16 PCM (1; a sample counts as i / 32768 exactly), 16-byte aligned; offsets int64 [B + 1]: utterance b is
+ * src[offsets[b] .. offsets[b+1]), nothing outside that range is read for it (it counts as 0.0).  taps fp32 [new][Kc] and first
+ * int32 [new]: the compact filter bank of hostlogic.resample_taps for the reduced ratio orig -> new, `width` its half width:
+ *     y[q new + p] = sum_{j < Kc} taps[p][j] x[q orig + first[p] + j - width]      (fp32 fused multiply-adds, j ascending, from 0)
+ * a sequence that depends on nothing but the sample itself.  out fp32 [B][ld]: column c < ncols of row b is output sample
+ * out_start[b] + c (out_start int64 [B] on the device, or null for 0), and exactly 0.0 at or beyond the utterance's
+ * ceil(new len / orig) samples; columns ncols .. ld-1 are left alone.  orig == new copies (taps, first may be null).  A table of
+ * more than APTAI_RESAMPLE_MAX_TABLE entries (new * Kc) is refused; one that fits LDS is staged there, a larger one is read
+ * through L2. */
+#define APTAI_RESAMPLE_MAX_TABLE (1 << 22)
+int aptai_resample_batch(const void* src, int src_is_int16, const int64_t* offsets, int64_t B, const float* taps, const int32_t* first,
+                         int64_t orig, int64_t new_, int64_t Kc, int64_t width, const int64_t* out_start, float* out, int64_t ld,
+                         int64_t ncols, void* stream);
+/* Wav2Vec2FeatureExtractor.zero_mean_unit_var_norm in place on x fp32 [B][ld]: y = (x - mean) / sqrt(var + 1e-7) over the first
+ * lens[b] samples of row b (lens int64 [B] on the device, clamped to [0, ncols]), population variance; the rest of the row is
+ * not touched.  Statistics and the affine step in fp64 (sums of x - x[b][0], so a large offset does not cancel), summed in a
+ * fixed order through `workspace` (aptai_wave_normalize_workspace_bytes), one rounding to fp32.  A row of length 0 is left as it
+ * is; a constant row becomes zeros. */
+int aptai_wave_normalize(float* x, int64_t ld, const int64_t* lens, int64_t B, int64_t ncols, void* workspace, void* stream);
+int64_t aptai_wave_normalize_workspace_bytes(int64_t B, int64_t ncols);
+
 #ifdef __cplusplus
 }
 #endif
