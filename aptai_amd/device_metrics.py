@@ -135,7 +135,7 @@ class EvalAccumulator:
 
     `add_*` launch kernels and append device tensors; nothing in them waits for the device.  `result()` concatenates everything
     into one fp64 vector (int32 counts and fp32 losses are exact in fp64), copies it to the host once, and forms the loops'
-    dictionaries with the host formulas, in the host loops' order of operations:
+    dictionaries with the host formulas (metrics.eval_summary, where the host loops end as well):
 
         kind       "val" (val_mean_* keys), "test" (test_{rate}_* keys), "pr_val" (mean_val_per, mean_val_loss), "pr_test"
         per        which distance feeds the PER of the TV loops: "frames_rounded" = collapsed frame labels through compute_PER's
@@ -225,43 +225,17 @@ class EvalAccumulator:
         if "decoded_n" in h and self.max_phonemes is not None:
             assert all(int(v) < self.max_phonemes for v in h["decoded_n"]), 'Need longer max phoneme sequence length.'
         if self.kind in ("pr_val", "pr_test"):
-            per = self._per(h, "edit")
-            if self.kind == "pr_test":
-                return {"mean_test_per": per}
-            return {"mean_val_per": per, "mean_val_loss": float(np.mean(h["loss"].tolist()))}
+            d, n = self._dist(h, "edit")
+            return metrics.eval_summary(self.kind, d, n, losses=h["loss"].tolist() if self.kind == "pr_val" else ())
         C = len(self.names)
-        rmse, pcc = h["rmse"].reshape(-1, C), h["pcc"].reshape(-1, C)
         frames, correct = [int(v) for v in h["frames"]], [int(v) for v in h["correct"]]
-        overlaps = [c / f for c, f in zip(correct, frames)]
-        ps, rs, f1s, rvals = [], [], [], []
-        for pc, rc, f in zip(h["prec"], h["rec"], frames):               # get_stats: len(yhat) == len(y) == frames
-            p, r, f1, rval = metrics.get_metrics(int(pc), int(rc), f, f)
-            ps.append(p); rs.append(r); f1s.append(f1); rvals.append(rval)
-        fer = 1 - (sum(correct) / sum(frames))
-        per = self._per(h, self.per)
-        if self.kind == "val":
-            return {
-                "val_mean_loss": float(np.mean(h["loss"].tolist())),
-                "val_mean_rmse": float(np.mean([np.mean(row.tolist()) for row in rmse])),
-                "val_mean_pcc": float(np.mean([np.mean(row.tolist()) for row in pcc])), "val_mean_FER": fer,
-                "val_mean_PER": per, "val_mean_F1": float(np.mean(f1s)),
-                "val_mean_p": float(np.mean(ps)), "val_mean_r": float(np.mean(rs)), "val_mean_Rval": float(np.mean(rvals)),
-                "val_mean_overlap": float(np.mean(overlaps)),
-            }
-        from .train_aptai import _tv_test_summary
-        rate = self.rate
-        out = _tv_test_summary(rate, {n: rmse[:, i].tolist() for i, n in enumerate(self.names)},
-                               {n: pcc[:, i].tolist() for i, n in enumerate(self.names)}, with_std=self.with_std)
-        out.update({f"test_{rate}_mean_FER": fer, f"test_{rate}_mean_PER": per})
-        if self.with_std:
-            d, n = self._dist(h, self.per)
-            out[f"test_{rate}_std_PER"] = float(np.std([a / b for a, b in zip(d, n)]))
-        out[f"test_{rate}_mean_overlap"] = float(np.mean(overlaps))
-        if self.with_std:
-            out[f"test_{rate}_std_overlap"] = float(np.std(overlaps))
-        out.update({f"test_{rate}_mean_F1": float(np.mean(f1s)), f"test_{rate}_mean_p": float(np.mean(ps)),
-                    f"test_{rate}_mean_r": float(np.mean(rs)), f"test_{rate}_mean_Rval": float(np.mean(rvals))})
-        return out
+        # get_stats: len(yhat) == len(y) == frames
+        stats = [metrics.get_metrics(int(pc), int(rc), f, f) for pc, rc, f in zip(h["prec"], h["rec"], frames)]
+        d, n = self._dist(h, self.per)
+        return metrics.eval_summary(self.kind, d, n, losses=h["loss"].tolist() if self.kind == "val" else (),
+                                    rmse=h["rmse"].reshape(-1, C).tolist(), pcc=h["pcc"].reshape(-1, C).tolist(), frames=frames,
+                                    correct=correct, overlaps=[c / f for c, f in zip(correct, frames)], stats=stats, rate=self.rate,
+                                    with_std=self.with_std, names=self.names)
 
     @staticmethod
     def _dist(h, per):
@@ -271,11 +245,6 @@ class EvalAccumulator:
         if per == "frames_rounded":                                      # metrics.compute_PER(...) / 100.0 * len(y_grp), as the loop writes it
             d = [round(a / b * 100, 2) / 100.0 * b for a, b in zip(d, n)]
         return d, n
-
-    @classmethod
-    def _per(cls, h, per) -> float:
-        d, n = cls._dist(h, per)
-        return float(np.sum(d) / np.sum(n))
 
 
 def frame_lengths(w2v2, audio_lengths, max_frames: int):

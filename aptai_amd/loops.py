@@ -1,0 +1,159 @@
+"""What the three training loops (train_aptai, train_force_aptai, train_phoneme_recognizer) share, once: the batch upload
+through the optional device front end, Adam + LambdaLR, the common hyper-parameters and command-line flags, and `EpochDriver`,
+the epoch skeleton of the reference's train() functions (train/train_aptai.py:392-531 and its two siblings): train step, clip
+monitor, graphed runner, schedule step, validation, best checkpoint, epoch log.  Which batches an epoch trains on, how the model
+is called and what gets printed stay in each loop's own module.
+"""
+from __future__ import annotations
+
+import pickle
+from pathlib import Path
+from types import SimpleNamespace
+
+import torch
+
+from . import hostlogic
+from .frontend import make_frontend, raw_batch_to_device
+
+
+def to_device(batch, device, frontend, audio_key, length_key, host_lengths=False):
+    """The collate's batch on the device.  With a front end (cfg.source_rate / cfg.normalize_audio) the batch is a `collate_*_raw`
+    one: its packed audio is uploaded as it is and resampled / normalised there into `audio_key` / `length_key`."""
+    if frontend is None:
+        return {k: v.to(device) for k, v in batch.items()}
+    return raw_batch_to_device(batch, frontend, device, audio_key, length_key, host_lengths=host_lengths)
+
+
+def adam_and_schedule(params, args_cfg, publish_to=None):
+    """Adam and LambdaLR with the 10x warm-up schedule, as the reference's load_model_optimizer functions build them.  The
+    optimiser is torch.optim.Adam's update rule as one multi-tensor HIP kernel (aptai_amd.optim.Adam; same constructor,
+    param_groups and state keys): `torch.optim.Adam(params, ...)` works unchanged on the same parameters.  `publish_to`: the model
+    whose bf16 weight copies the step refreshes in the same pass."""
+    from .optim import Adam
+    optimizer = Adam(params, lr=args_cfg.learning_rate, betas=(args_cfg.adam_beta1, args_cfg.adam_beta2), eps=args_cfg.adam_epsilon,
+                     weight_decay=args_cfg.adam_weight_decay, max_grad_norm=getattr(args_cfg, "max_grad_norm", None))
+    if publish_to is not None:
+        optimizer.publish_to(publish_to)
+    lr_scheduler = torch.optim.lr_scheduler.LambdaLR(
+        optimizer=optimizer, lr_lambda=hostlogic.get_lr_schedule(args_cfg.num_warmup_epochs, args_cfg.num_static_epochs, args_cfg.lr_decay))
+    return optimizer, lr_scheduler
+
+
+def default_cfg(overrides, **own):
+    """The hyper-parameters all three loops take at the reference's argparse defaults, the loop's `own` ones, then `overrides`."""
+    cfg = SimpleNamespace(device="cuda", num_epochs=2, adam_beta1=0.9, adam_beta2=0.999, adam_epsilon=1e-8, adam_weight_decay=0.0,
+                          num_warmup_epochs=10, num_static_epochs=30, lr_decay=0.96, target_metric_bigger_better=False,
+                          device_metrics=False, source_rate=None, normalize_audio=False, **own)
+    cfg.__dict__.update(overrides)
+    return cfg
+
+
+def add_shared_arguments(ap):
+    ap.add_argument("--max_grad_norm", type=float, default=None,
+                    help="clip the gradients at this global 2-norm inside the optimiser step (off by default)")
+    ap.add_argument("--source_rate", type=int, default=None,
+                    help="the corpus' sampling rate: the audio is uploaded at that rate and resampled to 16 kHz on the device")
+    ap.add_argument("--normalize_audio", action="store_true", help="zero-mean / unit-variance normalisation on the device")
+
+
+def shared_arguments(a) -> dict:
+    """The parsed flags of add_shared_arguments as default_cfg entries."""
+    return dict(max_grad_norm=a.max_grad_norm, source_rate=a.source_rate, normalize_audio=a.normalize_audio)
+
+
+def save_checkpoint(model, path):
+    """The two files a checkpoint directory holds."""
+    torch.save(model.state_dict(), path / "pytorch_model.bin")
+    pickle.dump(model.get_config(), open(path / "model_cfg.pkl", "wb"))
+
+
+def epoch_line(cfg, epoch_log) -> str:
+    """The epoch line of the two TV loops: the float-valued entries, in the log's order."""
+    return (f"Epoch {epoch_log['epoch'] + 1}/{cfg.num_epochs} -> "
+            + " | ".join(f"{k}: {v:.4f}" for k, v in epoch_log.items() if isinstance(v, float)))
+
+
+class EpochDriver:
+    """The state a train() carries from step to step and from epoch to epoch.  Per trained batch the loop calls `eager_step` or
+    `graphed_step`, per epoch `end_epoch`, at the end `close`.
+
+        frontend   None unless cfg.source_rate / cfg.normalize_audio: then the loaders use the `collate_*_raw` functions
+        steps      batches trained on in this epoch so far
+    """
+
+    def __init__(self, cfg, model, optimizer, lr_scheduler, best_ckpt_path):
+        self.cfg, self.model, self.optimizer, self.lr_scheduler = cfg, model, optimizer, lr_scheduler
+        self.frontend = make_frontend(cfg)
+        # cfg.max_grad_norm: the optimiser clips at this global norm inside step(); the loop only adds the device-side norm and the
+        # "was clipped" flag into two device scalars per step and reads them once per epoch (optim.ClipMonitor)
+        self.clip = None
+        if getattr(cfg, "max_grad_norm", None) is not None:
+            from . import optim
+            self.clip = optim.ClipMonitor(optimizer)
+        self.best_ckpt_path = Path(best_ckpt_path)
+        self.best_ckpt_path.mkdir(parents=True, exist_ok=True)
+        self.runner = None
+        self.eval_target = None
+        self.history = []
+        self.sum_train_loss, self.steps = 0.0, 0
+
+    def eager_step(self, forward):
+        """zero_grad -> `forward()` (the loop's model call on its uploaded batch) -> backward -> optimizer.step.  Returns the outputs."""
+        self.optimizer.zero_grad()
+        outputs = forward()
+        outputs["loss"].backward()
+        self.optimizer.step()
+        return self._trained(outputs)
+
+    def graphed_step(self, batch):
+        """The same step replayed as hipGraph segments.  The collates pad every batch to its own longest utterance (and label
+        list), so shapes vary: BucketedGraphedStep keeps one captured runner per (batch size, bucket length, label width) and
+        feeds each batch to the next larger bucket (results equal the eager step on the batch's own shape).  `batch`: the
+        collate's HOST batch (pinned staging ring + asynchronous copies), or a device batch whose lengths are host tensors."""
+        if self.runner is None:
+            from . import graphed
+            self.runner = graphed.BucketedGraphedStep(self.model, self.optimizer)
+        return self._trained(self.runner.step(batch))
+
+    def _trained(self, outputs):
+        if self.clip is not None:
+            self.clip.update()
+        self.sum_train_loss += float(outputs["loss"].detach())
+        self.steps += 1
+        return outputs
+
+    def end_epoch(self, epoch, validate, planned_steps=None, extra_checkpoints=None):
+        """Schedule step, validation (`validate()` -> its dictionary), best checkpoint, the epoch's log dictionary (also appended
+        to `history`).  A tie on cfg.target_metric counts as better and writes the checkpoint again.  `planned_steps`: the
+        recogniser's fixed number of steps per epoch; the mean train loss divides by it and the log gains `trained_batches`.
+        `extra_checkpoints()`: further files, written after the best checkpoint."""
+        cfg, model = self.cfg, self.model
+        self.lr_scheduler.step()
+        if self.runner is not None:
+            self.runner.suspend()        # the eager validation below rebuilds its weight copies; the captured buckets stay
+        model.eval()
+        val_logs = validate()
+        better = (self.eval_target is None
+                  or (cfg.target_metric_bigger_better and self.eval_target <= val_logs[cfg.target_metric])
+                  or (not cfg.target_metric_bigger_better and self.eval_target >= val_logs[cfg.target_metric]))
+        if better:
+            self.eval_target = val_logs[cfg.target_metric]
+            save_checkpoint(model, self.best_ckpt_path)
+        if extra_checkpoints is not None:
+            extra_checkpoints()
+        divisor = self.steps if planned_steps is None else planned_steps
+        epoch_log = dict(val_logs, epoch=epoch, mean_train_loss=self.sum_train_loss / max(divisor, 1),
+                         lr=self.optimizer.param_groups[0]["lr"], saved=bool(better))
+        if planned_steps is not None:
+            epoch_log["trained_batches"] = self.steps
+        if self.clip is not None:
+            epoch_log.update(self.clip.epoch_log())
+        self.history.append(epoch_log)
+        self.sum_train_loss, self.steps = 0.0, 0
+        return epoch_log
+
+    def close(self):
+        """After the last epoch: releases the graphed runner.  Returns the per-epoch log dictionaries."""
+        if self.runner is not None:
+            self.runner.close()
+        return self.history

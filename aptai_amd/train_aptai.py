@@ -10,16 +10,13 @@
 from __future__ import annotations
 
 import argparse
-import pickle
 import tempfile
-from pathlib import Path
-from types import SimpleNamespace
 from typing import Dict, Optional
 
 import numpy as np
 import torch
 
-from . import hostlogic, metrics
+from . import hostlogic, loops, metrics
 from .aptai import APTAI
 from .config import W2V2Config
 from .wav2vec2 import Wav2Vec2Model
@@ -53,12 +50,7 @@ class SyntheticHPRC(torch.utils.data.Dataset):
 
 
 def _to_device(batch_x, device, frontend=None, host_lengths=False):
-    """The collate's batch on the device.  With a front end (cfg.source_rate / cfg.normalize_audio) the batch is a `collate_*_raw`
-    one: its packed audio is uploaded as it is and resampled / normalised there into `audio_inputs` / `audio_lengths`."""
-    if frontend is None:
-        return {k: v.to(device) for k, v in batch_x.items()}
-    from .frontend import raw_batch_to_device
-    return raw_batch_to_device(batch_x, frontend, device, "audio_inputs", "audio_lengths", host_lengths=host_lengths)
+    return loops.to_device(batch_x, device, frontend, "audio_inputs", "audio_lengths", host_lengths)
 
 
 def load_model_optimizer(args_cfg):
@@ -66,81 +58,32 @@ def load_model_optimizer(args_cfg):
     pretrain_cfg = args_cfg.pretrain_cfg
     model = APTAI(device=args_cfg.device, vocab=args_cfg.vocab, huggingface_model_id=args_cfg.huggingface_model_id,
                   pretrain_cfg=pretrain_cfg, cache_dir=getattr(args_cfg, "cache_dir", None)).to(args_cfg.device)
-    # torch.optim.Adam's update rule as one multi-tensor HIP kernel (aptai_amd.optim.Adam; same constructor, param_groups and
-    # state keys).  `torch.optim.Adam(model.parameters(), ...)` works unchanged on the same parameters.
-    from .optim import Adam
-    optimizer = Adam(model.parameters(), lr=args_cfg.learning_rate, betas=(args_cfg.adam_beta1, args_cfg.adam_beta2),
-                     eps=args_cfg.adam_epsilon, weight_decay=args_cfg.adam_weight_decay,
-                     max_grad_norm=getattr(args_cfg, "max_grad_norm", None)).publish_to(model)
-    lr_scheduler = torch.optim.lr_scheduler.LambdaLR(
-        optimizer=optimizer, lr_lambda=hostlogic.get_lr_schedule(args_cfg.num_warmup_epochs, args_cfg.num_static_epochs, args_cfg.lr_decay))
+    optimizer, lr_scheduler = loops.adam_and_schedule(model.parameters(), args_cfg, publish_to=model)
     return model, optimizer, lr_scheduler
 
 
 def train(cfg, model, optimizer, lr_scheduler, train_dataloader, valid_dataloader, test_spk, best_ckpt_path, log=print):
     """train/train_aptai.py:392-531.  Returns the per-epoch log dicts (the reference only prints them)."""
-    eval_target = None
-    history = []
-    runner = None
-    from .frontend import make_frontend
-    frontend = make_frontend(cfg)            # None unless cfg.source_rate / cfg.normalize_audio: then the loaders use collate_aptai_raw
-    # cfg.max_grad_norm: the optimiser clips at this global norm inside step(); the loop only adds the device-side norm and the
-    # "was clipped" flag into two device scalars per step and reads them once per epoch (optim.ClipMonitor)
-    clip = None
-    if getattr(cfg, "max_grad_norm", None) is not None:
-        from .optim import ClipMonitor
-        clip = ClipMonitor(optimizer)
-    best_ckpt_path = Path(best_ckpt_path)
-    best_ckpt_path.mkdir(parents=True, exist_ok=True)
+    run = loops.EpochDriver(cfg, model, optimizer, lr_scheduler, best_ckpt_path)
+    frontend = run.frontend                  # not None: the loaders use collate_aptai_raw
     for epoch in range(cfg.num_epochs):
-        sum_train_loss, steps = 0.0, 0
         model.train()
         for batch_idx, batch_x in enumerate(train_dataloader):
             if getattr(cfg, "graphed", False):
-                # same step as below, replayed as hipGraph segments.  The collate pads every batch to its own longest utterance
-                # (train/train_aptai.py:268-285), so shapes vary: BucketedGraphedStep keeps one captured runner per (batch size,
-                # bucket length) and feeds each batch to the next larger bucket (results equal the eager step on the batch's own
-                # shape).  The runners take the collate_fn's HOST batch: pinned staging ring + asynchronous copies (set_batch)
-                if runner is None:
-                    from .graphed import BucketedGraphedStep
-                    runner = BucketedGraphedStep(model, optimizer)
-                # (with a front end it runs eagerly first: its output is the device batch the runners take as well)
-                outputs = runner.step(batch_x if frontend is None else _to_device(batch_x, cfg.device, frontend, host_lengths=True))
+                # the runners take the collate_fn's HOST batch; with a front end that runs eagerly first, and its output is the
+                # device batch the runners take as well
+                outputs = run.graphed_step(batch_x if frontend is None else _to_device(batch_x, cfg.device, frontend, host_lengths=True))
             else:
                 batch_x = _to_device(batch_x, cfg.device, frontend)
-                optimizer.zero_grad()
-                outputs = model(epoch, **batch_x)
-                outputs["loss"].backward()
-                optimizer.step()
-            if clip is not None:
-                clip.update()
-            sum_train_loss += float(outputs["loss"].detach())
-            steps += 1
+                outputs = run.eager_step(lambda: model(epoch, **batch_x))
             log(f"\tepoch {epoch + 1} ~ batch {batch_idx + 1}/{len(train_dataloader)}, train_loss: {float(outputs['loss'].detach()):.4f}, "
                 f"train_mse_loss: {float(outputs['mse_loss'].detach()):.4f}, train_ce_loss: {float(outputs['ce_loss'].detach()):.4f}, "
                 f"lr: {optimizer.param_groups[0]['lr']:.6f}")
-        lr_scheduler.step()
-        if runner is not None:
-            runner.suspend()             # the eager validation below rebuilds its weight copies; the captured buckets stay
-        model.eval()
-        val_logs = validate(model, cfg.device, cfg.vocab, epoch, getattr(cfg, "exp_dir", None), test_spk, valid_dataloader,
-                            device_metrics=getattr(cfg, "device_metrics", False), frontend=frontend)
-        better = (eval_target is None
-                  or (cfg.target_metric_bigger_better and eval_target <= val_logs[cfg.target_metric])
-                  or (not cfg.target_metric_bigger_better and eval_target >= val_logs[cfg.target_metric]))
-        if better:
-            eval_target = val_logs[cfg.target_metric]
-            torch.save(model.state_dict(), best_ckpt_path / "pytorch_model.bin")
-            pickle.dump(model.get_config(), open(best_ckpt_path / "model_cfg.pkl", "wb"))
-        epoch_log = dict(val_logs, epoch=epoch, mean_train_loss=sum_train_loss / max(steps, 1), lr=optimizer.param_groups[0]["lr"],
-                         saved=bool(better))
-        if clip is not None:
-            epoch_log.update(clip.epoch_log())
-        history.append(epoch_log)
-        log(f"Epoch {epoch + 1}/{cfg.num_epochs} -> " + " | ".join(f"{k}: {v:.4f}" for k, v in epoch_log.items() if isinstance(v, float)))
-    if runner is not None:
-        runner.close()
-    return history
+        epoch_log = run.end_epoch(epoch, lambda: validate(model, cfg.device, cfg.vocab, epoch, getattr(cfg, "exp_dir", None), test_spk,
+                                                          valid_dataloader, device_metrics=getattr(cfg, "device_metrics", False),
+                                                          frontend=frontend))
+        log(loops.epoch_line(cfg, epoch_log))
+    return run.close()
 
 
 def _device_eval(model, device, epoch, dl, acc, frontend=None):
@@ -168,38 +111,14 @@ def validate(model, device, vocab, epoch, exp_dir, test_spk, val_dl, log_step=10
     if device_metrics:
         from .device_metrics import EvalAccumulator
         return _device_eval(model, device, epoch, val_dl, EvalAccumulator("val", per="frames_rounded"), frontend=frontend)
-    val_losses, val_rmses, val_pccs, val_overlaps = [], [], [], []
-    val_ps, val_rs, val_f1s, val_rvals, edit_d, n_phn = [], [], [], [], [], []
-    total_frames = corr_frames = 0
+    s = _scores()
     for batch_x in val_dl:
-        with torch.no_grad():
-            tvs_gt = torch.stack([batch_x["LA"], batch_x["LP"], batch_x["JA"], batch_x["TTCL"], batch_x["TTCD"], batch_x["TMCL"],
-                                  batch_x["TTCD"], batch_x["TBCL"], batch_x["TBCD"]], dim=-1).float()
-            batch_x = _to_device(batch_x, device, frontend)
-            outputs = model(epoch, **batch_x)
-        val_losses.append(outputs["loss"].item())
-        tvs_gt = torch.squeeze(tvs_gt, dim=0).cpu().numpy()
-        tvs_pred = torch.squeeze(outputs["tvs_pred"], dim=0).float().cpu().numpy()
-        val_rmses.append(np.mean(list(metrics.tvs_metric_rmse(tvs_gt, tvs_pred).values())))
-        val_pccs.append(np.mean([v[0] for v in metrics.tvs_metric_ppc(tvs_gt, tvs_pred).values()]))
-        gt_frames, pred_frames = batch_x["phn_frames_49hz"], outputs["phn_fc_pred"]
-        total_frames += gt_frames.size(1)
-        corr_frames += int(torch.sum(torch.eq(gt_frames, pred_frames)).item())
-        gt_f, p_f = gt_frames.cpu().numpy(), pred_frames.cpu().numpy()
-        val_overlaps.append(metrics.evaluate_overlap(gt_f, p_f))
-        y, yhat = gt_f.squeeze(), p_f.squeeze()
-        p, r, f1, rval = metrics.get_stats(y, yhat, tolerance=0.02)
-        val_ps.append(p); val_rs.append(r); val_f1s.append(f1); val_rvals.append(rval)
+        outputs, _, y, yhat = _score_file(s, model, device, epoch, batch_x, frontend)
+        s["losses"].append(outputs["loss"].item())
         y_grp, yhat_grp = metrics.phn_frame_id2phn(y.tolist()), metrics.phn_frame_id2phn(yhat.tolist())
-        edit_d.append(metrics.compute_PER(y_grp, yhat_grp) / 100.0 * len(y_grp))
-        n_phn.append(len(y_grp))
-    return {
-        "val_mean_loss": float(np.mean(val_losses)), "val_mean_rmse": float(np.mean(val_rmses)),
-        "val_mean_pcc": float(np.mean(val_pccs)), "val_mean_FER": 1 - (corr_frames / total_frames),
-        "val_mean_PER": float(np.sum(edit_d) / np.sum(n_phn)), "val_mean_F1": float(np.mean(val_f1s)),
-        "val_mean_p": float(np.mean(val_ps)), "val_mean_r": float(np.mean(val_rs)), "val_mean_Rval": float(np.mean(val_rvals)),
-        "val_mean_overlap": float(np.mean(val_overlaps)),
-    }
+        s["edit_d"].append(metrics.compute_PER(y_grp, yhat_grp) / 100.0 * len(y_grp))
+        s["n_phn"].append(len(y_grp))
+    return metrics.eval_summary("val", **s)
 
 
 def _eval_frames(gt_frames, pred_frames):
@@ -217,19 +136,29 @@ def _stack_gt(batch_x):
                         batch_x["TTCD"], batch_x["TBCL"], batch_x["TBCD"]], dim=-1).float()
 
 
-def _tv_test_summary(rate, rmse_tvs, pcc_tvs, with_std=False):
-    names = hostlogic.TV_NAMES
-    m_rmse = {n: float(np.mean(rmse_tvs[n])) for n in names}
-    m_pcc = {n: float(np.mean(pcc_tvs[n])) for n in names}
-    out = {f"test_{rate}_mean_rmse": float(np.mean(list(m_rmse.values()))), f"test_{rate}_mean_pcc": float(np.mean(list(m_pcc.values())))}
-    if with_std:
-        out[f"test_{rate}_std_rmse"] = float(np.std(list(m_rmse.values())))
-        out[f"test_{rate}_std_pcc"] = float(np.std(list(m_pcc.values())))
-    for n in names:
-        out[f"test_{rate}_mean_{n}_pcc"] = m_pcc[n]
-    for n in names:
-        out[f"test_{rate}_mean_{n}_rmse"] = m_rmse[n]
-    return out
+_tv_test_summary = metrics.tv_test_summary
+
+
+def _scores():
+    """Per-utterance values of a host evaluation pass, under the argument names of metrics.eval_summary."""
+    return {k: [] for k in ("losses", "rmse", "pcc", "frames", "correct", "overlaps", "stats", "edit_d", "n_phn")}
+
+
+def _score_file(s, model, device, epoch, batch_x, frontend, pred_frames=lambda outputs: outputs["phn_fc_pred"]):
+    """One batch-1 evaluation pass of the host validate() / test() of both TV models: the forward, then the utterance's per-track
+    RMSE / PCC and frame scores appended to `s`.  Returns (outputs, device batch, gt frame labels, predicted frame labels); the
+    distance behind the PER differs per caller."""
+    with torch.no_grad():
+        tvs_gt = _stack_gt(batch_x)                     # from the host batch, before the upload
+        batch_x = _to_device(batch_x, device, frontend)
+        outputs = model(epoch, **batch_x)
+    tvs_gt = torch.squeeze(tvs_gt, dim=0).cpu().numpy()
+    tvs_pred = torch.squeeze(outputs["tvs_pred"], dim=0).float().cpu().numpy()
+    s["rmse"].append(list(metrics.tvs_metric_rmse(tvs_gt, tvs_pred).values()))
+    s["pcc"].append([v[0] for v in metrics.tvs_metric_ppc(tvs_gt, tvs_pred).values()])
+    frames, corr, overlap, stats, y, yhat = _eval_frames(batch_x["phn_frames_49hz"], pred_frames(outputs))
+    s["frames"].append(frames); s["correct"].append(corr); s["overlaps"].append(overlap); s["stats"].append(stats)
+    return outputs, batch_x, y, yhat
 
 
 def test(model, device, vocab, exp_dir, test_spk, test_dl, rate, log_step=100, num_epochs=0, device_metrics=False,
@@ -238,52 +167,23 @@ def test(model, device, vocab, exp_dir, test_spk, test_dl, rate, log_step=100, n
     keyed `test_{rate}_...` with rate in {'F', 'N'} (fast / normal speaking rate splits of the corpus).  `num_epochs` stands for
     the module-global `cfg.num_epochs` the reference passes as the epoch argument (:709)."""
     assert rate in ["F", "N"]
+    model.eval()
     if device_metrics:
         from .device_metrics import EvalAccumulator
-        model.eval()
         return _device_eval(model, device, num_epochs, test_dl, EvalAccumulator("test", rate=rate, per="frames"), frontend=frontend)
-    names = hostlogic.TV_NAMES
-    rmse_tvs, pcc_tvs = {n: [] for n in names}, {n: [] for n in names}
-    overlaps, ps, rs, f1s, rvals, edit_d, n_phn = [], [], [], [], [], [], []
-    total_frames = corr_frames = 0
-    model.eval()
+    s = _scores()
     for batch_x in test_dl:
-        with torch.no_grad():
-            tvs_gt = _stack_gt(batch_x)
-            batch_x = _to_device(batch_x, device, frontend)
-            outputs = model(num_epochs, **batch_x)
-        tvs_gt = torch.squeeze(tvs_gt, dim=0).cpu().numpy()
-        tvs_pred = torch.squeeze(outputs["tvs_pred"], dim=0).float().cpu().numpy()
-        frames, corr, overlap, (p, r, f1, rval), y, yhat = _eval_frames(batch_x["phn_frames_49hz"], outputs["phn_fc_pred"])
-        total_frames += frames
-        corr_frames += corr
-        overlaps.append(overlap)
-        ps.append(p); rs.append(r); f1s.append(f1); rvals.append(rval)
+        _, _, y, yhat = _score_file(s, model, device, num_epochs, batch_x, frontend)
         y_grp, yhat_grp = metrics.phn_frame_id2phn(y.tolist()), metrics.phn_frame_id2phn(yhat.tolist())
-        edit_d.append(metrics.edit_distance(y_grp, yhat_grp))
-        n_phn.append(len(y_grp))
-        rm, pc = metrics.tvs_metric_rmse(tvs_gt, tvs_pred), metrics.tvs_metric_ppc(tvs_gt, tvs_pred)
-        for n in names:
-            rmse_tvs[n].append(rm[n])
-            pcc_tvs[n].append(pc[n][0])
-    out = _tv_test_summary(rate, rmse_tvs, pcc_tvs)
-    out.update({f"test_{rate}_mean_FER": 1 - (corr_frames / total_frames),
-                f"test_{rate}_mean_PER": float(np.sum(edit_d) / np.sum(n_phn)),
-                f"test_{rate}_mean_overlap": float(np.mean(overlaps)), f"test_{rate}_mean_F1": float(np.mean(f1s)),
-                f"test_{rate}_mean_p": float(np.mean(ps)), f"test_{rate}_mean_r": float(np.mean(rs)),
-                f"test_{rate}_mean_Rval": float(np.mean(rvals))})
-    return out
+        s["edit_d"].append(metrics.edit_distance(y_grp, yhat_grp))
+        s["n_phn"].append(len(y_grp))
+    return metrics.eval_summary("test", rate=rate, **s)
 
 
 def default_cfg(**kw):
     """Hyper-parameters at the reference's argparse defaults (train/train_aptai.py:45-140)."""
-    cfg = SimpleNamespace(device="cuda", num_epochs=2, batch_size=16, learning_rate=1e-5, adam_beta1=0.9, adam_beta2=0.999,
-                          adam_epsilon=1e-8, adam_weight_decay=0.0, num_warmup_epochs=10, num_static_epochs=30, lr_decay=0.96,
-                          target_metric="val_mean_rmse", target_metric_bigger_better=False, graphed=False, exp_dir=None,
-                          vocab={f"p{i}": i for i in range(VOCAB_SIZE)}, cache_dir=None, device_metrics=False,
-                          source_rate=None, normalize_audio=False)
-    cfg.__dict__.update(kw)
-    return cfg
+    return loops.default_cfg(kw, batch_size=16, learning_rate=1e-5, target_metric="val_mean_rmse", graphed=False, exp_dir=None,
+                             vocab={f"p{i}": i for i in range(VOCAB_SIZE)}, cache_dir=None)
 
 
 def main(argv=None):
@@ -296,11 +196,7 @@ def main(argv=None):
     ap.add_argument("--batch_size", type=int, default=16)
     ap.add_argument("--seconds", type=float, default=10.0)
     ap.add_argument("--learning_rate", type=float, default=1e-5)
-    ap.add_argument("--max_grad_norm", type=float, default=None,
-                    help="clip the gradients at this global 2-norm inside the optimiser step (off by default)")
-    ap.add_argument("--source_rate", type=int, default=None,
-                    help="the corpus' sampling rate: the audio is uploaded at that rate and resampled to 16 kHz on the device")
-    ap.add_argument("--normalize_audio", action="store_true", help="zero-mean / unit-variance normalisation on the device")
+    loops.add_shared_arguments(ap)
     ap.add_argument("--graphed", action="store_true")
     ap.add_argument("--out", default="aptai_ckpt")
     a = ap.parse_args(argv)
@@ -312,8 +208,7 @@ def main(argv=None):
             Wav2Vec2Model(w2v).save_pretrained(tmp)
             model_dir = tmp
         cfg = default_cfg(num_epochs=a.num_epochs, batch_size=a.batch_size, learning_rate=a.learning_rate, graphed=a.graphed,
-                          huggingface_model_id=model_dir, pretrain_cfg=w2v, max_grad_norm=a.max_grad_norm, source_rate=a.source_rate,
-                          normalize_audio=a.normalize_audio)
+                          huggingface_model_id=model_dir, pretrain_cfg=w2v, **loops.shared_arguments(a))
         model, optimizer, lr_scheduler = load_model_optimizer(cfg)
     train_ds = SyntheticHPRC(a.steps_per_epoch * a.batch_size, a.seconds, vary_length=True, seed=1, cfg=w2v, source_rate=a.source_rate)
     val_ds = SyntheticHPRC(a.val_items, a.seconds, vary_length=True, seed=2, cfg=w2v, source_rate=a.source_rate)

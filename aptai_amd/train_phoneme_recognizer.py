@@ -17,13 +17,12 @@ import pickle
 import random
 import tempfile
 from pathlib import Path
-from types import SimpleNamespace
 from typing import Dict, Optional
 
 import numpy as np
 import torch
 
-from . import hostlogic, metrics
+from . import hostlogic, loops, metrics
 from .config import W2V2Config
 from .w2v2_pr import Wav2Vec2_PR
 from .wav2vec2 import Wav2Vec2Model
@@ -60,12 +59,7 @@ class SyntheticCommonPhone(torch.utils.data.Dataset):
 
 
 def _to_device(batch_x, device, frontend=None, host_lengths=False):
-    """The collate's batch on the device.  With a front end (cfg.source_rate / cfg.normalize_audio) the batch is a `collate_*_raw`
-    one: its packed audio is uploaded as it is and resampled / normalised there into `input_values` / `input_lengths`."""
-    if frontend is None:
-        return {k: v.to(device) for k, v in batch_x.items()}
-    from .frontend import raw_batch_to_device
-    return raw_batch_to_device(batch_x, frontend, device, "input_values", "input_lengths", host_lengths=host_lengths)
+    return loops.to_device(batch_x, device, frontend, "input_values", "input_lengths", host_lengths)
 
 
 def load_model_optimizer(args_cfg, vocab):
@@ -82,93 +76,50 @@ def load_model_optimizer(args_cfg, vocab):
     model = Wav2Vec2_PR(pretrain_cfg, getattr(args_cfg, "cache_dir", None), args_cfg.huggingface_model_id, vocab).to(args_cfg.device)
     if getattr(args_cfg, "freeze_feature_extractor", False):
         model.freeze_feature_encoder()
-    from .optim import Adam
-    optimizer = Adam(model.parameters(), lr=args_cfg.learning_rate, betas=(args_cfg.adam_beta1, args_cfg.adam_beta2),
-                     eps=args_cfg.adam_epsilon, weight_decay=args_cfg.adam_weight_decay,
-                     max_grad_norm=getattr(args_cfg, "max_grad_norm", None)).publish_to(model)
-    lr_scheduler = torch.optim.lr_scheduler.LambdaLR(
-        optimizer=optimizer, lr_lambda=hostlogic.get_lr_schedule(args_cfg.num_warmup_epochs, args_cfg.num_static_epochs, args_cfg.lr_decay))
+    optimizer, lr_scheduler = loops.adam_and_schedule(model.parameters(), args_cfg, publish_to=model)
     return model, optimizer, lr_scheduler
 
 
 def train(cfg, model, optimizer, lr_scheduler, vocab, train_dataloader, valid_dataloader, best_ckpt_path, last_ckpt_path,
           all_ckpt_path, log=print):
     """train/train_phoneme_recognizer.py:384-505.  Returns the per-epoch log dicts."""
-    eval_target = None
-    history = []
-    runner = None
-    from .frontend import make_frontend
-    frontend = make_frontend(cfg)            # None unless cfg.source_rate / cfg.normalize_audio: then the loaders use collate_pr_raw
-    # cfg.max_grad_norm: the optimiser clips at this global norm inside step(); the loop only adds the device-side norm and the
-    # "was clipped" flag into two device scalars per step and reads them once per epoch (optim.ClipMonitor)
-    clip = None
-    if getattr(cfg, "max_grad_norm", None) is not None:
-        from .optim import ClipMonitor
-        clip = ClipMonitor(optimizer)
-    best_ckpt_path, last_ckpt_path, all_ckpt_path = Path(best_ckpt_path), Path(last_ckpt_path), Path(all_ckpt_path)
-    best_ckpt_path.mkdir(parents=True, exist_ok=True)
+    run = loops.EpochDriver(cfg, model, optimizer, lr_scheduler, best_ckpt_path)
+    frontend = run.frontend                  # not None: the loaders use collate_pr_raw
+    last_ckpt_path, all_ckpt_path = Path(last_ckpt_path), Path(all_ckpt_path)
     last_ckpt_path.mkdir(parents=True, exist_ok=True)
     if cfg.save_all_epochs:
         all_ckpt_path.mkdir(parents=True, exist_ok=True)
-    for epoch in range(cfg.num_epochs):
-        epoch_train_steps = int(cfg.samples_per_epoch / cfg.batch_size)
-        # a random subset of this epoch's batches is trained on, the others are skipped (:406,413); `random` is the module the
-        # reference draws from, so `random.seed` reproduces an epoch's subset
-        subset_random = set(random.sample(range(len(train_dataloader)), epoch_train_steps))
-        subset_random_idx, sum_train_loss = 0, 0.0
-        model.train()
-        for batch_idx, batch_x in enumerate(train_dataloader):
-            if batch_idx not in subset_random:
-                continue
-            if getattr(cfg, "graphed", False):
-                # hipGraph replay of the same step; the collate pads each batch to its own longest utterance and label list
-                # (train/train_phoneme_recognizer.py:224-239), so one captured runner per (batch size, length bucket, label width)
-                if runner is None:
-                    from .graphed import BucketedGraphedStep
-                    runner = BucketedGraphedStep(model, optimizer)
-                outputs = runner.step(_to_device(batch_x, cfg.device, frontend, host_lengths=True))
-            else:
-                batch_x = _to_device(batch_x, cfg.device, frontend)
-                optimizer.zero_grad()
-                outputs = model(**batch_x)
-                outputs["loss"].backward()
-                optimizer.step()
-            if clip is not None:
-                clip.update()
-            sum_train_loss += float(outputs["loss"].detach())
-            log(f"\tepoch {epoch + 1} ~ batch {subset_random_idx + 1}/{epoch_train_steps}, train_loss: {float(outputs['loss'].detach()):.4f}")
-            subset_random_idx += 1
-        lr_scheduler.step()
-        if runner is not None:
-            runner.suspend()             # the eager validation below rebuilds its weight copies; the captured buckets stay
-        model.eval()
-        val_logs = validate(model, cfg.device, vocab, epoch, valid_dataloader, device_metrics=getattr(cfg, "device_metrics", False),
-                            frontend=frontend)
-        better = (eval_target is None
-                  or (cfg.target_metric_bigger_better and eval_target <= val_logs[cfg.target_metric])
-                  or (not cfg.target_metric_bigger_better and eval_target >= val_logs[cfg.target_metric]))
-        if better:
-            eval_target = val_logs[cfg.target_metric]
-            torch.save(model.state_dict(), best_ckpt_path / "pytorch_model.bin")
-            pickle.dump(model.get_config(), open(best_ckpt_path / "model_cfg.pkl", "wb"))
+
+    def save_epoch_and_last(epoch):
         if cfg.save_all_epochs:
             torch.save(model.state_dict(), all_ckpt_path / f"e{epoch:04d}.bin")
             if not (all_ckpt_path / "model_cfg.pkl").exists():
                 pickle.dump(model.get_config(), open(all_ckpt_path / "model_cfg.pkl", "wb"))
         torch.save(optimizer.state_dict(), last_ckpt_path / "optimizer.pt")
         torch.save({"last_epoch": cfg.num_epochs}, last_ckpt_path / "scheduler.pt")          # as written (:484)
-        torch.save(model.state_dict(), last_ckpt_path / "pytorch_model.bin")
-        pickle.dump(model.get_config(), open(last_ckpt_path / "model_cfg.pkl", "wb"))
-        epoch_log = dict(val_logs, epoch=epoch, mean_train_loss=sum_train_loss / max(epoch_train_steps, 1),
-                         lr=optimizer.param_groups[0]["lr"], saved=bool(better), trained_batches=subset_random_idx)
-        if clip is not None:
-            epoch_log.update(clip.epoch_log())
-        history.append(epoch_log)
+        loops.save_checkpoint(model, last_ckpt_path)
+
+    for epoch in range(cfg.num_epochs):
+        epoch_train_steps = int(cfg.samples_per_epoch / cfg.batch_size)
+        # a random subset of this epoch's batches is trained on, the others are skipped (:406,413); `random` is the module the
+        # reference draws from, so `random.seed` reproduces an epoch's subset
+        subset_random = set(random.sample(range(len(train_dataloader)), epoch_train_steps))
+        model.train()
+        for batch_idx, batch_x in enumerate(train_dataloader):
+            if batch_idx not in subset_random:
+                continue
+            if getattr(cfg, "graphed", False):
+                outputs = run.graphed_step(_to_device(batch_x, cfg.device, frontend, host_lengths=True))
+            else:
+                batch_x = _to_device(batch_x, cfg.device, frontend)
+                outputs = run.eager_step(lambda: model(**batch_x))
+            log(f"\tepoch {epoch + 1} ~ batch {run.steps}/{epoch_train_steps}, train_loss: {float(outputs['loss'].detach()):.4f}")
+        epoch_log = run.end_epoch(epoch, lambda: validate(model, cfg.device, vocab, epoch, valid_dataloader,
+                                                          device_metrics=getattr(cfg, "device_metrics", False), frontend=frontend),
+                                  planned_steps=epoch_train_steps, extra_checkpoints=lambda: save_epoch_and_last(epoch))
         log(f"Epoch {epoch + 1}/{cfg.num_epochs} -> lr: {epoch_log['lr']}| mean_train_loss: {epoch_log['mean_train_loss']}| "
-            f"mean_val_loss: {val_logs['mean_val_loss']}| val_per: {val_logs['mean_val_per']}")
-    if runner is not None:
-        runner.close()
-    return history
+            f"mean_val_loss: {epoch_log['mean_val_loss']}| val_per: {epoch_log['mean_val_per']}")
+    return run.close()
 
 
 def _decode(model, outputs) -> list:
@@ -216,7 +167,7 @@ def validate(model, device, vocab, epoch, validate_dataloader, log_step=100, dev
         val_losses.append(outputs["loss"].item())
         edit_d.append(metrics.edit_distance(phoneme_label, _decode(model, outputs)))
         n_phn.append(len(phoneme_label))
-    return {"mean_val_per": float(np.sum(edit_d) / np.sum(n_phn)), "mean_val_loss": float(np.mean(val_losses))}
+    return metrics.eval_summary("pr_val", edit_d, n_phn, losses=val_losses)
 
 
 def test(model, device, vocab, test_dl, dataset_name, log_step=100, laptop=False, device_metrics=False, frontend=None) -> Dict[str, float]:
@@ -235,18 +186,13 @@ def test(model, device, vocab, test_dl, dataset_name, log_step=100, laptop=False
             outputs = model(**batch_x)
         edit_d.append(metrics.edit_distance(phoneme_label, _decode(model, outputs)))
         n_phn.append(len(phoneme_label))
-    return {"mean_test_per": float(np.sum(edit_d) / np.sum(n_phn))}
+    return metrics.eval_summary("pr_test", edit_d, n_phn)
 
 
 def default_cfg(**kw):
     """Hyper-parameters at the reference's argparse defaults / start_train_phoneme_recognizer.sh (bs 2, lr 5e-6)."""
-    cfg = SimpleNamespace(device="cuda", num_epochs=2, batch_size=2, samples_per_epoch=8, learning_rate=5e-6, adam_beta1=0.9,
-                          adam_beta2=0.999, adam_epsilon=1e-8, adam_weight_decay=0.0, num_warmup_epochs=10, num_static_epochs=30,
-                          lr_decay=0.96, target_metric="mean_val_per", target_metric_bigger_better=False, final_dropout=0.1,
-                          num_hidden_layers=None, freeze_feature_extractor=False, save_all_epochs=False, cache_dir=None,
-                          device_metrics=False, source_rate=None, normalize_audio=False)
-    cfg.__dict__.update(kw)
-    return cfg
+    return loops.default_cfg(kw, batch_size=2, samples_per_epoch=8, learning_rate=5e-6, target_metric="mean_val_per", final_dropout=0.1,
+                             num_hidden_layers=None, freeze_feature_extractor=False, save_all_epochs=False, cache_dir=None)
 
 
 def main(argv=None):
@@ -260,11 +206,7 @@ def main(argv=None):
     ap.add_argument("--batch_size", type=int, default=16)
     ap.add_argument("--seconds", type=float, default=10.0)
     ap.add_argument("--learning_rate", type=float, default=5e-6)
-    ap.add_argument("--max_grad_norm", type=float, default=None,
-                    help="clip the gradients at this global 2-norm inside the optimiser step (off by default)")
-    ap.add_argument("--source_rate", type=int, default=None,
-                    help="the corpus' sampling rate: the audio is uploaded at that rate and resampled to 16 kHz on the device")
-    ap.add_argument("--normalize_audio", action="store_true", help="zero-mean / unit-variance normalisation on the device")
+    loops.add_shared_arguments(ap)
     ap.add_argument("--save_all_epochs", action="store_true")
     ap.add_argument("--out", default="pr_exp")
     a = ap.parse_args(argv)
@@ -278,7 +220,7 @@ def main(argv=None):
             model_dir = tmp
         cfg = default_cfg(num_epochs=a.num_epochs, batch_size=a.batch_size, samples_per_epoch=a.samples_per_epoch,
                           learning_rate=a.learning_rate, save_all_epochs=a.save_all_epochs, huggingface_model_id=model_dir,
-                          pretrain_cfg=w2v, max_grad_norm=a.max_grad_norm, source_rate=a.source_rate, normalize_audio=a.normalize_audio)
+                          pretrain_cfg=w2v, **loops.shared_arguments(a))
         model, optimizer, lr_scheduler = load_model_optimizer(cfg, vocab)
     collate = hostlogic.collate_pr_raw if (a.source_rate or a.normalize_audio) else hostlogic.collate_pr
     tr = torch.utils.data.DataLoader(SyntheticCommonPhone(a.train_items, a.seconds, len(vocab), seed=1, source_rate=a.source_rate),
