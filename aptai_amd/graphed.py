@@ -15,7 +15,9 @@ and replays them (~30 ``hipGraphLaunch`` per step).  Host-side randomness keeps 
  * dropout: kernels XOR a per-step device salt into their counter-RNG seeds (``aptai_set_seed_salt``), so every replay
    draws fresh masks while the forward and backward of one step regenerate identical ones.
 The optimiser step is issued eagerly after the last segment (aptai_amd.optim.Adam: one launch per parameter group; or any
-torch optimiser).  Nothing in a step synchronises host and device.
+torch optimiser).  Nothing in a step synchronises host and device: the host words a step sends (salt, frame bounds, a host
+batch) travel through ``_PinnedRing``.  ``_CapturingRunner`` holds what this runner shares with ``GraphedForceStep``: capture
+stream, salt and its binding, and the way back to the eager loop.
 """
 from __future__ import annotations
 
@@ -62,7 +64,79 @@ def _bind_bounds(stream_handle: int, bounds: torch.Tensor) -> None:
     _lib.call("aptai_set_frame_bounds", stream_handle, bounds.data_ptr())
 
 
-class GraphedAPTAIStep:
+class _PinnedRing:
+    """`slots` sets of pinned host buffers, one buffer per device tensor in `dst`, that take turns carrying a value to the device:
+    a pageable host-to-device copy would block the host until the GPU has drained, and one pinned buffer could be refilled while
+    its copy is still in flight.  The only wait is for the copy that last read the slot being handed out."""
+
+    def __init__(self, dst, slots: int):
+        self.dst = tuple(dst)
+        self.host = [tuple(torch.empty(t.shape, dtype=t.dtype).pin_memory() for t in self.dst) for _ in range(slots)]
+        self.views = [tuple(t.numpy() for t in bufs) for bufs in self.host]       # numpy views of the pinned buffers
+        self.events: List[Optional[torch.cuda.Event]] = [None] * slots
+        self.turn = 0
+
+    def next(self):
+        """The numpy views of the next slot, to be filled and then sent with send()."""
+        ev = self.events[self.turn]
+        if ev is not None:
+            ev.synchronize()                                    # the copies that last read this slot have finished
+        return self.views[self.turn]
+
+    def send(self) -> None:
+        """Asynchronous copies of the slot next() handed out into the device tensors, on the current stream."""
+        slot = self.turn
+        self.turn = (slot + 1) % len(self.host)
+        for d, h in zip(self.dst, self.host[slot]):
+            d.copy_(h, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self.events[slot] = ev
+
+
+class _CapturingRunner:
+    """What the two capturing runners share: the capture stream, the per-step dropout salt bound to it, and the way back."""
+
+    def _init_capture(self, dev, salt_seed: int) -> None:
+        # the per-step salt travels through a small ring of pinned buffers.  It is bound to THIS runner's capture stream
+        # (include/aptai_hip.h: no process-global state); the module-level registry keeps the two words alive until the binding
+        # is cleared, whatever happens to the runner object
+        self.salt = torch.zeros(2, device=dev, dtype=torch.int32)
+        self._salt_ring = _PinnedRing((self.salt,), 4)
+        self._salt_gen = np.random.RandomState(salt_seed)
+        self._cap_stream = torch.cuda.Stream(device=dev)
+        _bind_salt(self._cap_stream.cuda_stream, self.salt)
+
+    def _next_salt(self) -> None:
+        buf, = self._salt_ring.next()
+        buf[:] = self._salt_gen.randint(-2 ** 31, 2 ** 31 - 1, size=2).astype(np.int32)
+        self._salt_ring.send()
+
+    def _unbind(self) -> bool:
+        """Drops the salt and bounds bindings of the capture stream; False when that had been done already."""
+        if getattr(self, "_cap_stream", None) is None:
+            return False
+        _unbind_salt(self._cap_stream.cuda_stream)
+        self._cap_stream = None
+        return True
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        # a runner dropped without close() must not leave the library a pointer into a freed tensor; the model's weight
+        # cache is left alone here (a newer runner of the same model may own it by now)
+        try:
+            self._unbind()
+        except Exception:               # noqa: BLE001 - interpreter shutdown
+            pass
+
+
+class GraphedAPTAIStep(_CapturingRunner):
     def __init__(self, model, optimizer: torch.optim.Optimizer, batch: Dict[str, torch.Tensor], reducer=None):
         assert model.training, "call model.train() first"
         self.model, self.opt, self.reducer = model, optimizer, reducer
@@ -96,21 +170,12 @@ class GraphedAPTAIStep:
         else:
             self.tv_tgt = torch.zeros((B, g.T, model.n_tv), device=dev, dtype=torch.float32)
             self.phn_tgt = torch.zeros((B, g.T), device=dev, dtype=torch.int64)
-        self.salt = torch.zeros(2, device=dev, dtype=torch.int32)
-        self._salt_ring = [torch.zeros(2, dtype=torch.int32).pin_memory() for _ in range(4)]
-        self._salt_events = [None] * 4
-        self._salt_turn = 0
-        self._salt_gen = np.random.RandomState(0xC0FFEE + w.base_seed)
-        # the salt is bound to THIS runner's capture stream (include/aptai_hip.h: no process-global state); the module-level
-        # registry keeps the two words alive until the binding is cleared, whatever happens to the runner object
-        self._cap_stream = torch.cuda.Stream(device=dev)
-        _bind_salt(self._cap_stream.cuda_stream, self.salt)
+        self._init_capture(dev, 0xC0FFEE + w.base_seed)
         # frame bounds of the batch inside the captured shape (BucketedGraphedStep feeds shorter batches): by default the shape itself
         self.bounds = torch.tensor([g.Tl[0], g.T], device=dev, dtype=torch.int32)
-        self._bounds_ring = [torch.zeros(2, dtype=torch.int32).pin_memory() for _ in range(4)]
-        self._bounds_events = [None] * 4
-        self._bounds_turn = 0
+        self._bounds_ring = _PinnedRing((self.bounds,), 4)
         self._bounds_host = (g.Tl[0], g.T)
+        self._stage_ring = None                                  # pinned staging of host batches: made on the first one (set_batch)
         _bind_bounds(self._cap_stream.cuda_stream, self.bounds)
         self.set_batch(batch)
         # one eager step first: allocates every persistent scratch buffer, loads the code objects and sets the kernel
@@ -141,16 +206,15 @@ class GraphedAPTAIStep:
         if batch["audio_inputs"].device.type == "cpu":
             # staging copies through numpy: single-threaded memcpy / cast.  torch's copy_ goes parallel above 32 K elements
             # and the OpenMP workers then spin on the cores the launching thread needs (host time per step 8 -> 19 ms).
-            st = self._host_stage()
-            np.copyto(st["audio_np"], batch["audio_inputs"].detach().numpy(), casting="same_kind")
-            np.copyto(st["lens_np"], fl.numpy(), casting="same_kind")
+            if self._stage_ring is None:
+                self._stage_ring = _PinnedRing((self.audio, self.lens_i32, self.tv_tgt, self.phn_tgt), 2)
+            audio, lens, tv, phn = self._stage_ring.next()
+            np.copyto(audio, batch["audio_inputs"].detach().numpy(), casting="same_kind")
+            np.copyto(lens, fl.numpy(), casting="same_kind")
             for j, t in enumerate(tracks):                       # f64 (B, T) tracks -> one (B, T, n_tv) f32 block
-                st["tv_np"][:, :, j] = t.detach().numpy()
-            np.copyto(st["phn_np"], batch["phn_frames_49hz"].numpy(), casting="same_kind")
-            for dst, key in ((self.audio, "audio"), (self.lens_i32, "lens"), (self.tv_tgt, "tv"), (self.phn_tgt, "phn")):
-                dst.copy_(st[key], non_blocking=True)
-            st["event"] = torch.cuda.Event()
-            st["event"].record()
+                tv[:, :, j] = t.detach().numpy()
+            np.copyto(phn, batch["phn_frames_49hz"].numpy(), casting="same_kind")
+            self._stage_ring.send()
             return
         self.audio.copy_(batch["audio_inputs"].float())
         self.lens_i32.copy_(fl.to(torch.int32))
@@ -163,15 +227,9 @@ class GraphedAPTAIStep:
         two words travel through a ring of pinned buffers)."""
         if (conv0_frames, frames) == self._bounds_host:
             return
-        slot = self._bounds_turn
-        self._bounds_turn = (slot + 1) % len(self._bounds_ring)
-        if self._bounds_events[slot] is not None:
-            self._bounds_events[slot].synchronize()
-        self._bounds_ring[slot][0], self._bounds_ring[slot][1] = int(conv0_frames), int(frames)
-        self.bounds.copy_(self._bounds_ring[slot], non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        self._bounds_events[slot] = ev
+        buf, = self._bounds_ring.next()
+        buf[0], buf[1] = int(conv0_frames), int(frames)
+        self._bounds_ring.send()
         self._bounds_host = (conv0_frames, frames)
 
     def _set_batch_pr(self, batch: Dict[str, torch.Tensor]) -> None:
@@ -193,35 +251,11 @@ class GraphedAPTAIStep:
             self.labels.fill_(-100)
         self.labels[:, :lab.shape[1]].copy_(lab.to(torch.int32), non_blocking=True)
 
-    def _host_stage(self):
-        ring = getattr(self, "_stage_ring", None)
-        if ring is None:
-            mk = lambda ref: torch.empty(ref.shape, dtype=ref.dtype).pin_memory()
-            ring = [dict(audio=mk(self.audio), lens=mk(self.lens_i32), tv=mk(self.tv_tgt), phn=mk(self.phn_tgt), event=None)
-                    for _ in range(2)]
-            for st in ring:
-                for key in ("audio", "lens", "tv", "phn"):
-                    st[key + "_np"] = st[key].numpy()            # views of the pinned buffers
-            self._stage_ring, self._stage_turn = ring, 0
-        st = ring[self._stage_turn]
-        self._stage_turn ^= 1
-        if st["event"] is not None:
-            st["event"].synchronize()                            # the copies that last read this slot have finished
-        return st
-
     def _host_randomness(self):
-        cfg, g = self.cfg, self.g
-        # the per-step salt travels through a small ring of pinned buffers (a pageable H2D copy would block the host until
-        # the GPU has drained); the SpecAugment mask is sampled by a kernel inside the front segment from the same salt
-        slot = self._salt_turn
-        self._salt_turn = (slot + 1) % len(self._salt_ring)
-        if self._salt_events[slot] is not None:
-            self._salt_events[slot].synchronize()
-        self._salt_ring[slot].copy_(torch.from_numpy(self._salt_gen.randint(-2 ** 31, 2 ** 31 - 1, size=2).astype(np.int32)))
-        self.salt.copy_(self._salt_ring[slot], non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        self._salt_events[slot] = ev
+        """A fresh salt for the step (the SpecAugment mask is sampled by a kernel inside the front segment from the same salt) and
+        LayerDrop's choice of the layers that run."""
+        cfg = self.cfg
+        self._next_salt()
         keep = [True] * cfg.num_hidden_layers
         if cfg.layerdrop > 0:
             keep = [float(torch.rand([], generator=self.w._layerdrop_gen)) >= cfg.layerdrop for _ in keep]
@@ -258,7 +292,7 @@ class GraphedAPTAIStep:
                 w._conv_weights()
             if not getattr(self.opt, "publishes_copies", False):     # else the optimiser kernel refreshes the copies itself
                 w._refresh_layer_copies(force=True)
-            self.lw = [w._layer_weights(i, g.M) for i in range(L)]
+            self.lw = [w._layer_weights(i) for i in range(L)]
             fp, pc = w.feature_projection, w.encoder.pos_conv_embed.conv
             w._cached(("proj",), [fp.projection.weight], lambda: ops.cast_bf16(fp.projection.weight))
             w._cached(("posconv",), [pc.parametrizations.weight.original0, pc.parametrizations.weight.original1],
@@ -337,36 +371,13 @@ class GraphedAPTAIStep:
         if self.fin is not None:
             self.grads[w.encoder.layer_norm.weight], self.grads[w.encoder.layer_norm.bias] = fin_grads
 
-        # -- layers backward (reverse capture order = replay order).  APTAI_WGRAD_OVERLAP=1 (experiment, OFF by default): the layer's
-        # grouped weight-gradient launch as its own graph, replayed on a side stream beside the NEXT layer's dgrad chain (nothing
-        # downstream reads it before the optimiser), hoping its 486 tiles fill the launch gaps and one-round tails of the ~12
-        # dependent kernels of that chain.  Measured on one box, interleaved: 9.57 / 9.57 ms inline vs 9.93 / 9.97 ms overlapped -
-        # two chip-filling launches at once evict each other's operand panels from L2 and lose more than the gaps they fill.
-        # (The tensors the side graph reads stay referenced in `self._wpending`, so the shared graph pool never hands their memory
-        # to a later segment.)
+        # -- layers backward (reverse capture order = replay order)
         self.g_bwd = [None] * L
-        self.g_bww = [None] * L
-        self._wpending = [None] * L
         self.layer_grads = [None] * L
-        self.overlap_wgrad = (os.environ.get("APTAI_WGRAD_OVERLAP", "0") != "0") and self.group_reducer is None
-        self._w_stream = torch.cuda.Stream(device=self.dev) if self.overlap_wgrad else None
         for i in range(L - 1, -1, -1):
             gr = mk()
-            if self.overlap_wgrad:
-                with torch.cuda.graph(gr, pool=pool, stream=self._cap_stream, capture_error_mode=_CAPTURE_MODE):
-                    res = self.impl[i].bwd(self.s_layer[i], (self.dX[i + 1],), True, defer_wgrad=True)
-                if len(res) == 3:
-                    dx, ln_grads, self._wpending[i] = res
-                    gw = mk()
-                    with torch.cuda.graph(gw, pool=pool, stream=self._cap_stream, capture_error_mode=_CAPTURE_MODE):
-                        wg = self.impl[i].bwd_wgrad(self._wpending[i])
-                    self.g_bww[i] = gw
-                    pg = tuple(ln_grads) + tuple(wg)
-                else:                                   # APTAI_GROUPED_WGRAD=0: nothing to defer
-                    dx, pg = res
-            else:
-                with torch.cuda.graph(gr, pool=pool, stream=self._cap_stream, capture_error_mode=_CAPTURE_MODE):
-                    dx, pg = self.impl[i].bwd(self.s_layer[i], (self.dX[i + 1],), True)
+            with torch.cuda.graph(gr, pool=pool, stream=self._cap_stream, capture_error_mode=_CAPTURE_MODE):
+                dx, pg = self.impl[i].bwd(self.s_layer[i], (self.dX[i + 1],), True)
             self.g_bwd[i] = gr
             self.dX[i] = dx
             self.layer_grads[i] = list(zip(self.lparams[i], pg))
@@ -392,7 +403,7 @@ class GraphedAPTAIStep:
                 with torch.cuda.graph(self.g_ln, pool=pool, stream=self._cap_stream, capture_error_mode=_CAPTURE_MODE):
                     ops.ln_finalize_multi(self._ln_table, n_jobs, max_cols)
         # optimiser under the backward pass (step()): the parameters of layer i whose gradients are final when its backward segment ends
-        self.adam_overlap = (self.group_reducer is None and not self.overlap_wgrad and hasattr(self.opt, "launch_early")
+        self.adam_overlap = (self.group_reducer is None and hasattr(self.opt, "launch_early")
                              and os.environ.get("APTAI_ADAM_OVERLAP", "0") != "0")
         self._o_stream = torch.cuda.Stream(device=self.dev) if self.adam_overlap else None
         self._early_params = [[p for k, (p, _) in enumerate(self.layer_grads[i]) if p.requires_grad and (k >= 4 or self.g_ln is None)]
@@ -452,15 +463,11 @@ class GraphedAPTAIStep:
             self.loss_norm.scalars()                 # counts launched at the top of the step have arrived
         self.g_tail.replay()
         if red is not None:
-            red.launch("heads", [gt for p, gt in self.grads.items() if p.requires_grad and any(p is q for q in self.hparams)])
-        cur = torch.cuda.current_stream(self.dev) if (self.overlap_wgrad or overlap_opt) else None
+            red.launch("heads", self._head_front_grads()[0])
+        cur = torch.cuda.current_stream(self.dev) if overlap_opt else None
         for i in range(L - 1, -1, -1):
             if keep[i]:
                 self.g_bwd[i].replay()
-                if self.g_bww[i] is not None:  # the layer's weight gradients on the side stream, beside layer i-1's dgrad chain
-                    self._w_stream.wait_stream(cur)
-                    with torch.cuda.stream(self._w_stream):
-                        self.g_bww[i].replay()
                 if overlap_opt and early[i]:
                     self._o_stream.wait_stream(cur)
                     self.opt.launch_early(early[i], self._o_stream)
@@ -471,10 +478,8 @@ class GraphedAPTAIStep:
         self.g_front_bwd.replay()
         if self.g_ln is not None:
             self.g_ln.replay()                 # every LayerNorm dgamma / dbeta of the step in one launch
-        if self.overlap_wgrad:
-            cur.wait_stream(self._w_stream)    # every weight gradient is in place before the optimiser reads it
         if red is not None:
-            red.launch("front", [gt for p, gt in self.grads.items() if p.requires_grad and not any(p is q for q in self.hparams)])
+            red.launch("front", self._head_front_grads()[1])
             red.finish()
         if not overlap_opt:
             self._assign_grads(keep)
@@ -494,13 +499,20 @@ class GraphedAPTAIStep:
     def plan_groups(self):
         """[(name, gradient elements)] of the per-segment gradient groups in the order step() hands them to dp.GradGroupReducer
         (heads, layers L-1 .. 0, front): input of dp.collective_plan."""
-        heads = [gt for p, gt in self.grads.items() if p.requires_grad and any(p is q for q in self.hparams)]
-        front = [gt for p, gt in self.grads.items() if p.requires_grad and not any(p is q for q in self.hparams)]
+        heads, front = self._head_front_grads()
         out = [("heads", sum(t.numel() for t in heads))]
         for i in range(self.cfg.num_hidden_layers - 1, -1, -1):
             out.append((f"layer{i}", sum(t.numel() for t in self._layer_grad_tensors(i))))
         out.append(("front", sum(t.numel() for t in front)))
         return out
+
+    def _head_front_grads(self):
+        """(heads, front): the gradient buffers of the trainable parameters outside the layers, split by the segment that writes them."""
+        heads, front = [], []
+        for p, gt in self.grads.items():
+            if p.requires_grad:
+                (heads if any(p is q for q in self.hparams) else front).append(gt)
+        return heads, front
 
     def _layer_grad_tensors(self, i: int) -> List[torch.Tensor]:
         """Distinct gradient buffers of layer i (the q/k/v weight and bias gradients are row slices of one buffer each)."""
@@ -516,28 +528,9 @@ class GraphedAPTAIStep:
 
     def close(self):
         """Back to the eager loop: drop the salt binding of the capture stream and the frozen weight cache."""
-        if getattr(self, "_cap_stream", None) is not None:
-            _unbind_salt(self._cap_stream.cuda_stream)
-            self._cap_stream = None
+        if self._unbind():
             self.w._cache_mode = None
             self.w._cache.clear()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def __del__(self):
-        # a runner dropped without close() must not leave the library a pointer into a freed tensor; the model's weight
-        # cache is left alone here (a newer runner of the same model may own it by now)
-        try:
-            if getattr(self, "_cap_stream", None) is not None:
-                _unbind_salt(self._cap_stream.cuda_stream)
-                self._cap_stream = None
-        except Exception:               # noqa: BLE001 - interpreter shutdown
-            pass
 
 
 class BucketedGraphedStep:
@@ -645,7 +638,7 @@ class BucketedGraphedStep:
         return False
 
 
-class GraphedForceStep:
+class GraphedForceStep(_CapturingRunner):
     """hipGraph runner for the Force_APTAI train step (models/force_aptai.py:80-178, train/train_force_aptai.py:392-531): TWO graphs,
 
         encoder (frozen recogniser in inference mode + best-path decode, on a side stream)  |  heads forward + loss + heads backward
@@ -674,14 +667,8 @@ class GraphedForceStep:
         g = self.g
         n_tv = model.rnn.linear[3].weight.shape[0]
         self.tv_tgt = torch.zeros((B, g.T, n_tv), device=dev, dtype=torch.float32)
-        self.salt = torch.zeros(2, device=dev, dtype=torch.int32)
-        self._salt_ring = [torch.zeros(2, dtype=torch.int32).pin_memory() for _ in range(4)]
-        self._salt_events = [None] * 4
-        self._salt_turn = 0
-        self._salt_gen = np.random.RandomState(0xF0CE + w.base_seed)
-        self._cap_stream = torch.cuda.Stream(device=dev)
+        self._init_capture(dev, 0xF0CE + w.base_seed)
         self._enc_stream = torch.cuda.Stream(device=dev)
-        _bind_salt(self._cap_stream.cuda_stream, self.salt)
         # one eager step: scratch buffers, code objects, weight copies
         model.zero_grad(set_to_none=True)
         model(0, **batch)["loss"].backward()
@@ -730,35 +717,6 @@ class GraphedForceStep:
         self.model.w2v2_pr.wav2vec2._step += 1
         self._have_enc = True
 
-    def _salt_step(self):
-        slot = self._salt_turn
-        self._salt_turn = (slot + 1) % len(self._salt_ring)
-        if self._salt_events[slot] is not None:
-            self._salt_events[slot].synchronize()
-        self._salt_ring[slot].copy_(torch.from_numpy(self._salt_gen.randint(-2 ** 31, 2 ** 31 - 1, size=2).astype(np.int32)))
-        self.salt.copy_(self._salt_ring[slot], non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        self._salt_events[slot] = ev
-
-    def _assign_grads(self, keep) -> None:
-        """Every trainable parameter's `.grad` = its static gradient buffer (None for a layer LayerDrop skipped this step)."""
-        for p, gt in self.grads.items():
-            if p.requires_grad:
-                p.grad = gt
-        for i in range(self.cfg.num_hidden_layers):
-            for p, gt in self.layer_grads[i]:
-                if p.requires_grad:
-                    p.grad = gt if keep[i] else None
-        if not getattr(self, "_checked", False):
-            names = {id(p): n for n, p in self.model.named_parameters()}
-            for p in self.model.parameters():
-                if p.grad is not None and (p.grad.dtype != p.dtype or p.grad.shape != p.shape or not p.grad.is_contiguous()
-                                           or p.grad.device != p.device):
-                    raise RuntimeError(f"static gradient of {names[id(p)]} has dtype {p.grad.dtype} shape {tuple(p.grad.shape)} "
-                                       f"contiguous={p.grad.is_contiguous()} (parameter: {p.dtype} {tuple(p.shape)})")
-            self._checked = True
-
     # ------------------------------------------------------------------ one optimiser step
     def step(self, batch: Optional[Dict[str, torch.Tensor]] = None, next_batch: Optional[Dict[str, torch.Tensor]] = None):
         """Heads of `batch` (default: the batch given last) + optimiser step; the encoder pass of `next_batch` (default: `batch`
@@ -775,7 +733,7 @@ class GraphedForceStep:
         self.h_ac.copy_(e.ac, non_blocking=True); self.h_ids.copy_(e.ids, non_blocking=True)
         self.h_nlen.copy_(e.nlen, non_blocking=True); self.h_fl.copy_(e.frame_lens, non_blocking=True)
         self._launch_encoder(next_batch if next_batch is not None else batch)      # waits for the four copies above
-        self._salt_step()
+        self._next_salt()
         self.g_heads.replay()
         for p, gt in zip(self.P, self.pgrads):
             if p.requires_grad:
@@ -794,20 +752,4 @@ class GraphedForceStep:
     def close(self):
         if getattr(self, "_cap_stream", None) is not None:
             torch.cuda.synchronize(self.dev)
-            _unbind_salt(self._cap_stream.cuda_stream)
-            self._cap_stream = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def __del__(self):
-        try:
-            if getattr(self, "_cap_stream", None) is not None:
-                _unbind_salt(self._cap_stream.cuda_stream)
-                self._cap_stream = None
-        except Exception:               # noqa: BLE001 - interpreter shutdown
-            pass
+            self._unbind()

@@ -174,7 +174,7 @@ class _LayerImpl:
             s.x1 = ffn_in
         s.u = torch.empty((M, I), device=x.device, dtype=torch.bfloat16) if need else None
         # with gradients: s.u holds dropmask/(1-p) * gelu'(pre-activation), the factor the dgrad epilogue multiplies by
-        s.hact = ops.gemm(ffn_in, w.w1, M, I, H, bias=w.b1, gelu=True, out_pre=s.u, pre_dgelu=need and _PRE_DGELU, dropout_p=p_a,
+        s.hact = ops.gemm(ffn_in, w.w1, M, I, H, bias=w.b1, gelu=True, out_pre=s.u, pre_dgelu=need, dropout_p=p_a,
                           seed=_seed(self.seed, 3))
         res2 = s.s1 if pre else ffn_in
         s.s2 = ops.gemm(s.hact, w.w2, M, H, I, bias=w.b2, residual=res2, dropout_p=p_h, seed=_seed(self.seed, 4))
@@ -242,11 +242,8 @@ class _LayerImpl:
         y = s2 if pre else ops.layernorm_fwd(s2, ln2w, ln2b, cfg.layer_norm_eps, save_stats=False)[0]
         return (y,), None
 
-    def bwd(self, s, grads, x_needs, defer_wgrad=False):
-        """dgrad chain on the caller's stream; the weight/bias gradients are independent of that chain and can go to a side
-        stream (APTAI_SIDE_STREAM=1).  Off by default: each GEMM already fills the 256 CUs, the A/B was neutral.
-        defer_wgrad (graph runner): return (dx, (LayerNorm grads, None), pending) WITHOUT the layer's grouped weight-gradient
-        launch; `bwd_wgrad(pending)` issues it - the runner replays it on a side stream beside the NEXT layer's backward."""
+    def bwd(self, s, grads, x_needs):
+        """The dgrad chain, then every weight and bias gradient of the layer in one grouped launch."""
         cfg, g, w = self.cfg, self.g, self.w
         M, H, I = g.M, cfg.hidden_size, cfg.intermediate_size
         heads = cfg.num_attention_heads
@@ -256,16 +253,6 @@ class _LayerImpl:
         # (a loss that reaches this layer through its map alone leaves the hidden state's gradient undefined: zero)
         dy = grads[0].contiguous() if grads[0] is not None else torch.zeros_like(s.x)
         pre = cfg.do_stable_layer_norm
-        sk = w.split_k
-        main = torch.cuda.current_stream()
-        side = _side_stream(dy.device)
-
-        def on_side(fn):
-            if not _USE_SIDE_STREAM:
-                return fn()
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                return fn()
         # ---- FFN block
         if pre:
             ds2 = dy                                             # y = s1 + D(ffn)
@@ -276,17 +263,7 @@ class _LayerImpl:
             if d_ffn_out is None:
                 d_ffn_out = ds2
             ffn_in = s.x1
-        grouped = _GROUPED_WGRAD
-        if not grouped:
-            dw2, dbias2 = on_side(lambda: (ops.gemm(d_ffn_out, s.hact, H, I, M, a_kmajor=True, b_kmajor=True, out_f32=True, split_k=sk[3]),
-                                           ops.colsum(d_ffn_out, M, H)))
-        if _PRE_DGELU:
-            du = ops.gemm(d_ffn_out, w.w2, M, I, H, b_kmajor=True, mul_aux=s.u)
-        else:                                        # APTAI_PRE_DGELU=0: recompute mask and gelu' in the dgrad epilogue (A/B)
-            du = ops.gemm(d_ffn_out, w.w2, M, I, H, b_kmajor=True, dgelu_aux=s.u, dropout_p=p_a, seed=_seed(self.seed, 3))
-        if not grouped:
-            dw1, dbias1 = on_side(lambda: (ops.gemm(du, ffn_in, I, H, M, a_kmajor=True, b_kmajor=True, out_f32=True, split_k=sk[2]),
-                                           ops.colsum(du, M, I)))
+        du = ops.gemm(d_ffn_out, w.w2, M, I, H, b_kmajor=True, mul_aux=s.u)
         if pre:
             dn2 = ops.gemm(du, w.w1, M, H, I, b_kmajor=True)
             ds1, d_att_out, dg2, db2 = ops.layernorm_bwd(dn2, s.s1, s.m2, s.r2, ln2w, dres=ds2, dropout_p=p_h,
@@ -297,9 +274,6 @@ class _LayerImpl:
         if d_att_out is None:
             d_att_out = ds1
         # ---- attention block
-        if not grouped:
-            dwo, dbo = on_side(lambda: (ops.gemm(d_att_out, s.ctx, H, H, M, a_kmajor=True, b_kmajor=True, out_f32=True, split_k=sk[1]),
-                                        ops.colsum(d_att_out, M, H)))
         dctx = ops.gemm(d_att_out, w.wo, M, H, H, b_kmajor=True)
         # no loss term of the models touches padded frames, so their context gradient is exactly zero and the kernel skips them - unless
         # a layer above had a gradient on its map: the maps' padded QUERY rows are part of the returned tensor (as in the reference), and
@@ -313,64 +287,26 @@ class _LayerImpl:
             if st is not None:
                 st.seen = True
         attn_in = s.n1 if pre else s.x
-        if not grouped:
-            dwqkv, dbqkv = on_side(lambda: (ops.gemm(dqkv, attn_in, 3 * H, H, M, a_kmajor=True, b_kmajor=True, out_f32=True, split_k=sk[0]),
-                                            ops.colsum(dqkv, M, 3 * H)))
         if pre:
             dn1 = ops.gemm(dqkv, w.wqkv, M, H, 3 * H, b_kmajor=True)
             dx, _, dg1, db1 = ops.layernorm_bwd(dn1, s.x, s.m1, s.r1, ln1w, dres=ds1)
         else:
             dx = ops.gemm(dqkv, w.wqkv, M, H, 3 * H, b_kmajor=True, residual=ds1)
-        if grouped and defer_wgrad:
-            pending = SimpleNamespace(d_ffn_out=d_ffn_out, hact=s.hact, du=du, ffn_in=ffn_in, d_att_out=d_att_out, ctx=s.ctx, dqkv=dqkv,
-                                      attn_in=attn_in, M=M, H=H, I=I)
-            return dx, (dg1, db1, dg2, db2), pending
-        if grouped:
-            # all weight and bias gradients of the layer in ONE launch (aptai_gemm_bf16_grouped): 4 x (dY^T X) + 4 x (1^T dY),
-            # 432 + 54 full-K tiles for wav2vec2-base = one round of the 512 block slots, no split-K slabs, no reduce kernels
-            tn = dict(a_kmajor=True, b_kmajor=True, out_f32=True)
-            ones = ops.ones_kmajor(M, dy.device)
-            dw2, dw1, dwo, dwqkv, r2, r1, ro, rq = ops.gemm_grouped([
-                (d_ffn_out, s.hact, H, I, M, tn), (du, ffn_in, I, H, M, tn), (d_att_out, s.ctx, H, H, M, tn),
-                (dqkv, attn_in, 3 * H, H, M, tn),
-                (ones, d_ffn_out, 8, H, M, tn), (ones, du, 8, I, M, tn), (ones, d_att_out, 8, H, M, tn),
-                (ones, dqkv, 8, 3 * H, M, tn)])
-            dbias2, dbias1, dbo, dbqkv = r2[0], r1[0], ro[0], rq[0]
-        main.wait_stream(side)
+        # all weight and bias gradients of the layer in ONE launch (aptai_gemm_bf16_grouped): 4 x (dY^T X) + 4 x (1^T dY),
+        # 432 + 54 full-K tiles for wav2vec2-base = one round of the 512 block slots, no split-K slabs, no reduce kernels
+        tn = dict(a_kmajor=True, b_kmajor=True, out_f32=True)
+        ones = ops.ones_kmajor(M, dy.device)
+        dw2, dw1, dwo, dwqkv, r2, r1, ro, rq = ops.gemm_grouped([
+            (d_ffn_out, s.hact, H, I, M, tn), (du, ffn_in, I, H, M, tn), (d_att_out, s.ctx, H, H, M, tn),
+            (dqkv, attn_in, 3 * H, H, M, tn),
+            (ones, d_ffn_out, 8, H, M, tn), (ones, du, 8, I, M, tn), (ones, d_att_out, 8, H, M, tn),
+            (ones, dqkv, 8, 3 * H, M, tn)])
+        dbias2, dbias1, dbo, dbqkv = r2[0], r1[0], ro[0], rq[0]
         return dx, (dg1, db1, dg2, db2, dwqkv[0:H], dwqkv[H:2 * H], dwqkv[2 * H:3 * H], dbqkv[0:H], dbqkv[H:2 * H],
                     dbqkv[2 * H:3 * H], dwo, dbo, dw1, dbias1, dw2, dbias2)
 
 
-    @staticmethod
-    def bwd_wgrad(p):
-        """The grouped weight / bias gradient launch of one layer from the tensors its dgrad chain left behind (see bwd).  Returns
-        the 12 Linear-parameter gradients in the order of bwd's tuple (after the four LayerNorm gradients)."""
-        M, H, I = p.M, p.H, p.I
-        tn = dict(a_kmajor=True, b_kmajor=True, out_f32=True)
-        ones = ops.ones_kmajor(M, p.du.device)
-        dw2, dw1, dwo, dwqkv, r2, r1, ro, rq = ops.gemm_grouped([
-            (p.d_ffn_out, p.hact, H, I, M, tn), (p.du, p.ffn_in, I, H, M, tn), (p.d_att_out, p.ctx, H, H, M, tn),
-            (p.dqkv, p.attn_in, 3 * H, H, M, tn),
-            (ones, p.d_ffn_out, 8, H, M, tn), (ones, p.du, 8, I, M, tn), (ones, p.d_att_out, 8, H, M, tn),
-            (ones, p.dqkv, 8, 3 * H, M, tn)])
-        dbias2, dbias1, dbo, dbqkv = r2[0], r1[0], ro[0], rq[0]
-        return (dwqkv[0:H], dwqkv[H:2 * H], dwqkv[2 * H:3 * H], dbqkv[0:H], dbqkv[H:2 * H], dbqkv[2 * H:3 * H], dwo, dbo, dw1, dbias1,
-                dw2, dbias2)
-
-
-_SIDE_STREAMS = {}
-_GROUPED_WGRAD = os.environ.get("APTAI_GROUPED_WGRAD", "1") != "0"
-_PRE_DGELU = os.environ.get("APTAI_PRE_DGELU", "1") != "0"
 _SPEC_ON_DEVICE = os.environ.get("APTAI_SPEC_ON_DEVICE", "1") != "0"      # =0: numpy sampler with HF's RNG order (host round trip)
-_USE_SIDE_STREAM = os.environ.get("APTAI_SIDE_STREAM", "0") != "0"     # measured neutral on MI355X (A/B 15.95 vs 15.98 ms/step)
-
-
-def _side_stream(device):
-    st = _SIDE_STREAMS.get(device)
-    if st is None:
-        st = torch.cuda.Stream(device=device)
-        _SIDE_STREAMS[device] = st
-    return st
 
 
 # =================================================================================== front end of the encoder
@@ -733,20 +669,8 @@ class Wav2Vec2Model(nn.Module):
             plan.version = ver
             plan.after_training = bool(trainable) and not synced
 
-    def _layer_weights(self, i: int, M: int):
-        e = self._layer_plan().entries[i]
-        e.split_k = self._split_k(M)
-        return e, self._layer_params(i)
-
-    def _split_k(self, M: int):
-        """split-K factors for the four wgrad GEMMs (qkv, out, ffn1, ffn2): fill ~2 blocks per CU."""
-        H, I = self.config.hidden_size, self.config.intermediate_size
-
-        def pick(rows, cols):
-            tiles = ((rows + 127) // 128) * ((cols + 127) // 128)
-            s = max(1, min(16, 512 // max(tiles, 1)))
-            return max(1, min(s, M // 512 if M >= 512 else 1))
-        return (pick(3 * H, H), pick(H, H), pick(I, H), pick(H, I))
+    def _layer_weights(self, i: int):
+        return self._layer_plan().entries[i], self._layer_params(i)
 
     def _scratch(self, key, numel, dev):
         """Persistent zero-initialised bf16 scratch (the zero gap rows of the packed positional-conv operands are
@@ -1158,7 +1082,7 @@ class Wav2Vec2Model(nn.Module):
             h32 = h.float()
             for i, layer in enumerate(self.encoder.layers):
                 hidden.append(h if h is not None else h32)
-                wt, _lin = self._layer_weights(i, g.M)
+                wt, _lin = self._layer_weights(i)
                 impl = _LayerImpl(cfg, g, lens_i32, wt, False, 0)
                 impl.want_attn = want_attn
                 h, h32 = impl.fwd_f32res(h, h32, [layer.layer_norm.weight, layer.layer_norm.bias, layer.final_layer_norm.weight,
@@ -1180,7 +1104,7 @@ class Wav2Vec2Model(nn.Module):
                 if want_attn:
                     attn.append(None)
                 continue
-            w, lin_params = self._layer_weights(i, g.M)
+            w, lin_params = self._layer_weights(i)
             impl = _LayerImpl(cfg, g, lens_i32, w, training, _seed(seed, 100 + i))
             if getattr(self, "_encoder_precision", "bf16") == "mxfp8" and not training:
                 impl.mx = self._mx_layer_weights(i)

@@ -445,3 +445,22 @@ def test_optimiser_under_the_backward_pass_changes_no_bit(monkeypatch):
         assert st == st1 and torch.equal(m, m1) and torch.equal(v, v1), n
         steps.add(st)
     assert len(steps) > 1, steps          # LayerDrop did skip a layer in some step: the case the early launches must get right
+
+
+def test_pinned_ring_delivers_every_value_in_order():
+    """Seven values back to back through a ring of two slots, no host synchronisation in between: each slot is reused three
+    times, so a slot refilled before its previous copy had been read would show as a wrong or repeated row."""
+    import numpy as np
+    from aptai_amd.graphed import _PinnedRing
+    dst = torch.zeros(2, device="cuda", dtype=torch.int32)
+    got = torch.zeros((7, 2), device="cuda", dtype=torch.int32)
+    ring = _PinnedRing((dst,), 2)
+    want = np.arange(14, dtype=np.int32).reshape(7, 2) * 1000003 - 5
+    for i in range(7):
+        buf, = ring.next()
+        buf[:] = want[i]
+        ring.send()
+        got[i].copy_(dst)
+    torch.cuda.synchronize()
+    assert ring.turn == 7 % 2
+    assert torch.equal(got.cpu(), torch.from_numpy(want))
