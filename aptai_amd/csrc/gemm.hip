@@ -61,8 +61,10 @@ void epi_trace(const GemmArgs& g, int tile) {
 // BM_T = 128: wave tile 64 x 64, 2 blocks per CU.  BM_T = 64 (K-contiguous A only): wave tile 32 x 64, 24 KiB stages, 3 blocks
 // per CU = 768 slots - for [8192] x 768 outputs, whose 384 big tiles fill only 0.75 of one round of 512 slots while their 768
 // half tiles are exactly one round of 768.
-template <bool A_KM, bool B_KM, bool OUT_F32, int BM_T = 128>
-__device__ __forceinline__ void gemm_tile_body(GemmArgs g, const int bid, const int batch, const int split) {
+// ROWSUM (grouped weight gradients, both operands K-major): a tile of the first tile column of a problem that carries `rowsum` also
+// writes rowsum[m] = sum_k A[k][m] for its 128 output rows - the bias gradient, from the dY fragments the tile holds anyway.
+template <bool A_KM, bool B_KM, bool OUT_F32, int BM_T = 128, bool ROWSUM = false>
+__device__ __forceinline__ void gemm_tile_body(GemmArgs g, const int bid, const int batch, const int split, float* rowsum = nullptr) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     APTAI_STAMP(0);
     const int tid = threadIdx.x;
@@ -104,6 +106,15 @@ __device__ __forceinline__ void gemm_tile_body(GemmArgs g, const int bid, const 
     for (int i = 0; i < NI; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+    // Row sums: the two waves of the tile's first column block issue one more MFMA per A fragment and k-step against a register
+    // fragment of bf16 ones (no LDS read, no staging), in the K order of the tile's own chain; every row of that product is the sum.
+    static_assert(!ROWSUM || (A_KM && B_KM && OUT_F32 && BM_T == 128), "row sums ride on the K-major fp32 weight-gradient tile");
+    const bool rs_wave = ROWSUM && rowsum != nullptr && tile_n == 0 && wn == 0;      // block-uniform but for the wave's column half
+    const bf16x8 ones8 = __builtin_bit_cast(bf16x8, (short8v){0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80});
+    f32x4 racc[ROWSUM ? NI : 1];
+#pragma unroll
+    for (int i = 0; i < (ROWSUM ? NI : 1); ++i) racc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
     const int wave_base_tid = wave * 64;
     const bool wave_active = (m0 + wm * WM < g.M) && (n0 + wn * 64 < g.N);
@@ -224,6 +235,12 @@ __device__ __forceinline__ void gemm_tile_body(GemmArgs g, const int bid, const 
 #pragma unroll
                         for (int j = 0; j < 4; ++j)
                             acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[j], af[i], acc[i][j], 0, 0, 0);
+                    if constexpr (ROWSUM) {
+                        if (rs_wave) {
+#pragma unroll
+                            for (int i = 0; i < NI; ++i) racc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones8, af[i], racc[i], 0, 0, 0);
+                        }
+                    }
                 }
 #undef APTAI_TIE8
             }
@@ -333,10 +350,26 @@ __device__ __forceinline__ void gemm_tile_body(GemmArgs g, const int bid, const 
 #pragma unroll
                         for (int j = 0; j < 4; ++j)
                             acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[j], af[i], acc[i][j], 0, 0, 0);
+                    if constexpr (ROWSUM) {            // builds without the ring (APTAI_GEMM_RING5=0)
+                        if (rs_wave) {
+#pragma unroll
+                            for (int i = 0; i < NI; ++i) racc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones8, af[i], racc[i], 0, 0, 0);
+                        }
+                    }
                 }
             }
         }
     }
+    }
+    if constexpr (ROWSUM) {
+        // racc[i][r] of lane l is output row m = wm*64 + i*16 + (l & 15), product row (l >> 4) * 4 + r: lanes 0..15 hold row 0
+        if (rs_wave && lane < 16) {
+#pragma unroll
+            for (int i = 0; i < NI; ++i) {
+                const int m = m0 + wm * WM + i * 16 + lane;
+                if (m < g.M) rowsum[m] = racc[i][0];
+            }
+        }
     }
 
     // ------------------------------------------------------------------ epilogue
@@ -493,18 +526,21 @@ constexpr int MAX_GROUP = 8;
 struct GroupArgs {
     GemmArgs p[MAX_GROUP];
     int tile_end[MAX_GROUP];        // running sum of tiles_m * tiles_n
+    float* rowsum[MAX_GROUP];       // optional (both operands K-major, fp32 out): rowsum[m] = sum_k A[k][m], M floats; null = none
     int n, total;
 };
 
+// The both-K-major instantiation asks for two blocks per CU: its 80 KiB ring fits no third, and under the three-block register budget
+// the four row-sum accumulators spilled (168 VGPRs + 12 B of scratch; 154 without them).
 template <bool A_KM, bool B_KM, bool OUT_F32>
-__global__ __launch_bounds__(NTHREADS, 3) void gemm_grouped_kernel(GroupArgs ga) {
+__global__ __launch_bounds__(NTHREADS, (A_KM && B_KM && APTAI_GEMM_RING5) ? 2 : 3) void gemm_grouped_kernel(GroupArgs ga) {
     const int bid = xcd_remap(blockIdx.x, ga.total);
     int pi = 0;
 #pragma unroll
     for (int i = 1; i < MAX_GROUP; ++i)
         if (i < ga.n && bid >= ga.tile_end[i - 1]) pi = i;
     const int first = pi ? ga.tile_end[pi - 1] : 0;
-    gemm_tile_body<A_KM, B_KM, OUT_F32>(ga.p[pi], bid - first, -1, 0);
+    gemm_tile_body<A_KM, B_KM, OUT_F32, 128, A_KM && B_KM && OUT_F32>(ga.p[pi], bid - first, -1, 0, ga.rowsum[pi]);
 }
 
 // out[i] = (accumulate ? out[i] : 0) + sum_s slabs[s][i]
@@ -1717,7 +1753,7 @@ static int gemm_bf16_run(const aptai_gemm_desc* d, void* stream, long hash_ld, i
 }
 extern "C" int aptai_gemm_bf16(const aptai_gemm_desc* d, void* stream) { return gemm_bf16_run(d, stream, d ? d->N : 0, 0); }
 
-extern "C" int aptai_gemm_bf16_grouped(const aptai_gemm_desc* descs, int n, void* stream_) {
+extern "C" int aptai_gemm_bf16_grouped_rowsum(const aptai_gemm_desc* descs, float* const* rowsums, int n, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     APTAI_REQUIRE(descs != nullptr && n >= 1 && n <= MAX_GROUP, "aptai_gemm_bf16_grouped: need 1..%d problems, got %d", MAX_GROUP, n);
     GroupArgs ga;
@@ -1725,6 +1761,13 @@ extern "C" int aptai_gemm_bf16_grouped(const aptai_gemm_desc* descs, int n, void
     int total = 0;
     for (int i = 0; i < n; ++i) {
         const aptai_gemm_desc* d = descs + i;
+        if (rowsums != nullptr && rowsums[i] != nullptr) {       // refused by name before the general checks
+            APTAI_REQUIRE(d->a_kmajor && d->b_kmajor, "aptai_gemm_bf16_grouped: problem %d: row sums need both operands K-major", i);
+            APTAI_REQUIRE(d->out_f32, "aptai_gemm_bf16_grouped: problem %d: row sums need fp32 output", i);
+            APTAI_REQUIRE(d->split_k <= 1, "aptai_gemm_bf16_grouped: problem %d: row sums cannot be split over K slabs (each slab would hold a partial sum)", i);
+            APTAI_REQUIRE((uintptr_t)rowsums[i] % 4 == 0, "aptai_gemm_bf16_grouped: problem %d: row sums must be 4-byte aligned", i);
+            ga.rowsum[i] = rowsums[i];
+        }
         const int brc = validate_desc(d);
         if (brc != APTAI_OK) return brc;
         // 128-row tiles; rastered only where both operands are K-major (see plan_gemm)
@@ -1744,6 +1787,10 @@ extern "C" int aptai_gemm_bf16_grouped(const aptai_gemm_desc* descs, int n, void
     return with_layout("aptai_gemm_bf16_grouped", descs[0].a_kmajor != 0, descs[0].b_kmajor != 0, descs[0].out_f32 != 0, [&](auto a, auto b, auto f) {
         return launch_kernel<gemm_grouped_kernel<a(), b(), f()>>({NTHREADS, smem_for<a(), b()>(), "gemm_grouped_kernel"}, dim3(total), stream, ga);
     });
+}
+
+extern "C" int aptai_gemm_bf16_grouped(const aptai_gemm_desc* descs, int n, void* stream) {
+    return aptai_gemm_bf16_grouped_rowsum(descs, nullptr, n, stream);
 }
 
 extern "C" int64_t aptai_gemm_sk_workspace_bytes(void) { return sk_workspace_bytes(); }

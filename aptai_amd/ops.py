@@ -236,27 +236,49 @@ def gemm(a: torch.Tensor, b: torch.Tensor, M: int, N: int, K: int, **kw) -> torc
 
 def gemm_grouped(problems) -> list:
     """One launch for up to 8 independent GEMMs of one operand layout (aptai_gemm_bf16_grouped).
-    problems: iterable of (a, b, M, N, K, kwargs-dict) with the keywords of gemm(); returns the outputs in order."""
+    problems: iterable of (a, b, M, N, K, kwargs-dict) with the keywords of gemm(); returns the outputs in order.
+    A problem whose dict carries rowsum=True or rowsum=<fp32 tensor [M]> (both operands K-major, fp32 output) also yields the fp32 vector [M] of the column sums of
+    its K-major A (aptai_gemm_bf16_grouped_rowsum) - the bias gradient beside a weight gradient dY^T X; these vectors follow the outputs
+    in the returned list, in problem order."""
     problems = list(problems)
     descs = (GemmDesc * len(problems))()
-    outs, keep = [], []
+    outs, keep, sums = [], [], []
+    rs_ptrs = (c_void_p * len(problems))()
     flops = 0.0
-    for d, (a, b, M, N, K, kw) in zip(descs, problems):
+    for i, (d, (a, b, M, N, K, kw)) in enumerate(zip(descs, problems)):
+        kw = dict(kw)
+        want_sum = kw.pop("rowsum", False)
         out, ws = _gemm_desc(d, a, b, M, N, K, **kw)
         outs.append(out)
         keep.append(ws)
+        if want_sum is not False and want_sum is not None:
+            # True = a fresh vector; a caller's own fp32 tensor of M elements is written in place
+            rs = want_sum if isinstance(want_sum, torch.Tensor) else torch.empty((M,), device=a.device, dtype=torch.float32)
+            _dev(rs)
+            if rs.dtype != torch.float32 or rs.numel() != M or not rs.is_contiguous():
+                raise ValueError("rowsum takes a contiguous fp32 tensor of M elements")
+            rs_ptrs[i] = rs.data_ptr()
+            sums.append(rs)
         flops += 2.0 * M * N * K
+
+    def launch():
+        if sums:
+            _lib.check(_lib.lib().aptai_gemm_bf16_grouped_rowsum(descs, rs_ptrs, len(problems), c_void_p(_stream())),
+                       "aptai_gemm_bf16_grouped_rowsum")
+        else:
+            _lib.check(_lib.lib().aptai_gemm_bf16_grouped(descs, len(problems), c_void_p(_stream())), "aptai_gemm_bf16_grouped")
+
     pr = _probe
     d0 = descs[0]
     if pr is not None and pr.key == (bool(d0.a_kmajor), bool(d0.b_kmajor), bool(d0.out_f32)) and not torch.cuda.is_current_stream_capturing():
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        _lib.check(_lib.lib().aptai_gemm_bf16_grouped(descs, len(problems), c_void_p(_stream())), "aptai_gemm_bf16_grouped")
+        launch()
         e1.record()
         pr.records.append((flops, e0, e1))
-        return outs
-    _lib.check(_lib.lib().aptai_gemm_bf16_grouped(descs, len(problems), c_void_p(_stream())), "aptai_gemm_bf16_grouped")
-    return outs
+        return outs + sums
+    launch()
+    return outs + sums
 
 
 _ONES = {}

@@ -292,16 +292,13 @@ class _LayerImpl:
             dx, _, dg1, db1 = ops.layernorm_bwd(dn1, s.x, s.m1, s.r1, ln1w, dres=ds1)
         else:
             dx = ops.gemm(dqkv, w.wqkv, M, H, 3 * H, b_kmajor=True, residual=ds1)
-        # all weight and bias gradients of the layer in ONE launch (aptai_gemm_bf16_grouped): 4 x (dY^T X) + 4 x (1^T dY),
-        # 432 + 54 full-K tiles for wav2vec2-base = one round of the 512 block slots, no split-K slabs, no reduce kernels
-        tn = dict(a_kmajor=True, b_kmajor=True, out_f32=True)
-        ones = ops.ones_kmajor(M, dy.device)
-        dw2, dw1, dwo, dwqkv, r2, r1, ro, rq = ops.gemm_grouped([
+        # all weight and bias gradients of the layer in ONE launch (aptai_gemm_bf16_grouped_rowsum): 4 x (dY^T X), each with the row sums
+        # of its dY = the bias gradient, formed by the tiles of the first tile column from the dY fragments they hold anyway:
+        # 432 full-K tiles for wav2vec2-base inside one round of the 512 block slots, no split-K slabs, no reduce kernels, no ones problems
+        tn = dict(a_kmajor=True, b_kmajor=True, out_f32=True, rowsum=True)
+        dw2, dw1, dwo, dwqkv, dbias2, dbias1, dbo, dbqkv = ops.gemm_grouped([
             (d_ffn_out, s.hact, H, I, M, tn), (du, ffn_in, I, H, M, tn), (d_att_out, s.ctx, H, H, M, tn),
-            (dqkv, attn_in, 3 * H, H, M, tn),
-            (ones, d_ffn_out, 8, H, M, tn), (ones, du, 8, I, M, tn), (ones, d_att_out, 8, H, M, tn),
-            (ones, dqkv, 8, 3 * H, M, tn)])
-        dbias2, dbias1, dbo, dbqkv = r2[0], r1[0], ro[0], rq[0]
+            (dqkv, attn_in, 3 * H, H, M, tn)])
         return dx, (dg1, db1, dg2, db2, dwqkv[0:H], dwqkv[H:2 * H], dwqkv[2 * H:3 * H], dbqkv[0:H], dbqkv[H:2 * H],
                     dbqkv[2 * H:3 * H], dwo, dbo, dw1, dbias1, dw2, dbias2)
 

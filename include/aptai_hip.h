@@ -115,6 +115,15 @@ int aptai_gemm_bf16(const aptai_gemm_desc* desc, void* stream);
  * their full-K tiles fill the 256 CUs once, where each alone needs split-K slabs and a reduce pass.  A bias gradient is
  * the problem M = 8, A = ones[K][8] (K-major), row 0 of the [8][N] fp32 result. */
 int aptai_gemm_bf16_grouped(const aptai_gemm_desc* descs, int n, void* stream);
+/* The same launch with an optional fp32 row-sum output per problem: rowsums is null or an array of n device pointers, null = none.
+ * rowsums[i][m] = sum_k A_i[k][m] for the M_i output rows of problem i, i.e. the column sums of a K-major A: with A = dY of a weight
+ * gradient dW = dY^T X that is the bias gradient, so it needs no ones[K][8] problem of its own.  The tiles of the problem's first
+ * tile column form it from the A fragments they already hold, with one more MFMA per fragment against a register of ones, in the K
+ * order of the tile's own accumulation (no atomics: same inputs, same bits; the same bits as row 0 of the ones problem).  Each of the
+ * M_i floats is written once; nothing beyond them is touched.  Refused with APTAI_ERR_INVALID: a row-sum pointer on a problem whose
+ * operands are not both K-major, whose output is not fp32, or that asks for split-K slabs (each slab would hold a partial sum).
+ * aptai_gemm_bf16_grouped is this entry with rowsums = null. */
+int aptai_gemm_bf16_grouped_rowsum(const aptai_gemm_desc* descs, float* const* rowsums, int n, void* stream);
 /* What aptai_gemm_bf16 would launch for `desc` in this process (environment knobs included), without touching the device: the same
  * validation and the same planner, so a refused descriptor returns the status and aptai_last_error() text of aptai_gemm_bf16. */
 typedef struct {
