@@ -81,25 +81,11 @@ __device__ __forceinline__ void gemm_tile_body(GemmArgs g, const int bid, const 
     constexpr int STAGE_T = A_BYTES_T + BN * BK * 2;
     constexpr int NPASS = BM_T / 16;                    // epilogue passes of 16 rows
     static_assert(BM_T == 128 || (BM_T == 64 && !A_KM), "64-row tiles are built for K-contiguous A only");
-    constexpr bool RING5 = A_KM && B_KM && BM_T == 128 && APTAI_GEMM_RING5;
+    constexpr bool RING5 = A_KM && B_KM;                // both operands K-major: the five-slot ring below (128-row tiles only)
     const int m0 = tile_m * BM_T, n0 = tile_n * BN;
 
-    if (batch >= 0) {
-        const int bo = batch / g.nb_inner, bi = batch % g.nb_inner;
-        g.A += bo * g.sA[0] + bi * g.sA[1];
-        g.B += bo * g.sB[0] + bi * g.sB[1];
-        const long co = bo * g.sC[0] + bi * g.sC[1];
-        g.C = (OUT_F32 && !(g.flags & APTAI_EPI_SPLIT_OUT)) ? (void*)((float*)g.C + co) : (void*)((bf16_t*)g.C + co);
-        if (g.out_pre) g.out_pre += co;
-        if (g.bias) g.bias += bo * g.sBias[0] + bi * g.sBias[1];
-        if (g.residual) g.residual += bo * g.sR[0] + bi * g.sR[1];
-        if (g.aux) g.aux += bo * g.sAux[0] + bi * g.sAux[1];
-    }
-    const int total_kt = g.K / BK;
-    const int kt_begin = split * g.ktiles_per_split;
-    int kt_end = kt_begin + g.ktiles_per_split;
-    kt_end = kt_end < total_kt ? kt_end : total_kt;
-    const int nk = kt_end - kt_begin;
+    if (batch >= 0) batch_offset<OUT_F32>(g, batch / g.nb_inner, batch % g.nb_inner);
+    const auto [kt_begin, nk] = splitk_range(g, split);
 
     f32x4 acc[NI][4];
 #pragma unroll
@@ -109,7 +95,7 @@ __device__ __forceinline__ void gemm_tile_body(GemmArgs g, const int bid, const 
 
     // Row sums: the two waves of the tile's first column block issue one more MFMA per A fragment and k-step against a register
     // fragment of bf16 ones (no LDS read, no staging), in the K order of the tile's own chain; every row of that product is the sum.
-    static_assert(!ROWSUM || (A_KM && B_KM && OUT_F32 && BM_T == 128), "row sums ride on the K-major fp32 weight-gradient tile");
+    static_assert(!ROWSUM || (RING5 && OUT_F32), "row sums ride on the ring loop of the K-major fp32 weight-gradient tile");
     const bool rs_wave = ROWSUM && rowsum != nullptr && tile_n == 0 && wn == 0;      // block-uniform but for the wave's column half
     const bf16x8 ones8 = __builtin_bit_cast(bf16x8, (short8v){0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80});
     f32x4 racc[ROWSUM ? NI : 1];
@@ -169,7 +155,7 @@ __device__ __forceinline__ void gemm_tile_body(GemmArgs g, const int bid, const 
                 hb[it] += hstepB;
             }
         };
-        // per-lane byte offsets of the 16 transposing reads of one half-stage (read_frag<true> with ks = 0): A fragments
+        // per-lane byte offsets of the 16 transposing reads of one half-stage (read_frag_tr_asm with ks = 0): A fragments
         // 0..3 (lo, hi) in [0, 8 KiB), B fragments in [8 KiB, 16 KiB)
         uint32_t frag_off[16];
         {
@@ -260,7 +246,7 @@ __device__ __forceinline__ void gemm_tile_body(GemmArgs g, const int bid, const 
         // a wave whose 64 x 64 quadrant lies wholly outside the problem (grouped positional conv: 48 channels per group;
         // bias-gradient problems: M = 8; heads: N = 64) stages and synchronises but issues no LDS reads and no MFMAs
         if (wave_active) {
-            if constexpr (!A_KM && !B_KM && APTAI_GEMM_HOIST) {
+            if constexpr (!A_KM && !B_KM) {
                 // K-contiguous operands: all 16 ds_read_b128 of the K-tile are issued before the first MFMA (sched_barrier
                 // keeps the compiler from sinking them next to their uses): one exposed LDS latency per K-tile instead of
                 // one per fragment group (+9 % at K = 3072).  With transposing reads (K-major operands) the same hoist
@@ -269,9 +255,9 @@ __device__ __forceinline__ void gemm_tile_body(GemmArgs g, const int bid, const 
 #pragma unroll
                 for (int ks = 0; ks < 2; ++ks) {
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) bfr[ks][j] = read_frag<B_KM>(sb, wn * 64 + j * 16, ks, lane);
+                    for (int j = 0; j < 4; ++j) bfr[ks][j] = read_frag(sb, wn * 64 + j * 16, ks, lane);
 #pragma unroll
-                    for (int i = 0; i < NI; ++i) af[ks][i] = read_frag<A_KM>(sa, wm * WM + i * 16, ks, lane);
+                    for (int i = 0; i < NI; ++i) af[ks][i] = read_frag(sa, wm * WM + i * 16, ks, lane);
                 }
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -281,7 +267,7 @@ __device__ __forceinline__ void gemm_tile_body(GemmArgs g, const int bid, const 
 #pragma unroll
                         for (int j = 0; j < 4; ++j)
                             acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[ks][j], af[ks][i], acc[i][j], 0, 0, 0);
-            } else if constexpr (BM_T == 64 && !A_KM && B_KM && APTAI_GEMM_M64_ASM) {
+            } else if constexpr (BM_T == 64) {
                 // 64-row NN tiles (the dgrads): every LDS read of the K-tile through inline asm, issued up front in the order
                 // B(k-half 0) x8, A(0) x2, B(1) x8, A(1) x2; LDS reads return in order, so lgkmcnt(10) = the first half is back
                 short4v bl[2][4], bh[2][4];
@@ -313,49 +299,27 @@ __device__ __forceinline__ void gemm_tile_body(GemmArgs g, const int bid, const 
                                                                                 __builtin_bit_cast(bf16x8, aa[ks][i]), acc[i][j], 0, 0, 0);
                 }
             } else {
+                static_assert(BM_T == 128 && !A_KM && B_KM, "the one layout left: every other one has its branch above");
+                // 128-row NN tiles: the K-major B fragments arrive through read_frag_tr_asm (no compiler vmcnt(0) behind the
+                // staging loads: NN FFN2 dgrad 58 -> 55 us), A through plain ds_read_b128, one lgkmcnt(0) per k-half.  The 64-row
+                // NN tiles have their own all-asm branch above; in this form they lost to the builtin (57 vs 60 us).
 #pragma unroll
                 for (int ks = 0; ks < 2; ++ks) {
                     bf16x8 af[NI], bfr[4];
-                    // K-major fragments of the 128-row tiles arrive through read_frag_tr_asm (no compiler vmcnt(0) behind the
-                    // staging loads: NN FFN2 dgrad 58 -> 55 us).  The 64-row NN tiles have their own all-asm branch above; with
-                    // only the B reads in asm and one lgkmcnt(0) per k-half they lost to the builtin (57 vs 60 us).
-                    constexpr bool ASM_TR = BM_T == 128;
-                    short4v tl[NI + 4], th[NI + 4];
+                    short4v tl[4], th[4];
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        if constexpr (B_KM && ASM_TR) read_frag_tr_asm(sb, wn * 64 + j * 16, ks, lane, tl[NI + j], th[NI + j]);
-                        else bfr[j] = read_frag<B_KM>(sb, wn * 64 + j * 16, ks, lane);
-                    }
+                    for (int j = 0; j < 4; ++j) read_frag_tr_asm(sb, wn * 64 + j * 16, ks, lane, tl[j], th[j]);
 #pragma unroll
-                    for (int i = 0; i < NI; ++i) {
-                        if constexpr (A_KM && ASM_TR) read_frag_tr_asm(sa, wm * WM + i * 16, ks, lane, tl[i], th[i]);
-                        else af[i] = read_frag<A_KM>(sa, wm * WM + i * 16, ks, lane);
-                    }
-                    if constexpr (B_KM && ASM_TR) {
-                        asm volatile("s_waitcnt lgkmcnt(0)"
-                                     : "+v"(tl[NI]), "+v"(tl[NI + 1]), "+v"(tl[NI + 2]), "+v"(tl[NI + 3]), "+v"(th[NI]), "+v"(th[NI + 1]),
-                                       "+v"(th[NI + 2]), "+v"(th[NI + 3]));
+                    for (int i = 0; i < NI; ++i) af[i] = read_frag(sa, wm * WM + i * 16, ks, lane);
+                    asm volatile("s_waitcnt lgkmcnt(0)"
+                                 : "+v"(tl[0]), "+v"(tl[1]), "+v"(tl[2]), "+v"(tl[3]), "+v"(th[0]), "+v"(th[1]), "+v"(th[2]), "+v"(th[3]));
 #pragma unroll
-                        for (int j = 0; j < 4; ++j) bfr[j] = combine_tr(tl[NI + j], th[NI + j]);
-                    }
-                    if constexpr (A_KM && ASM_TR) {
-                        static_assert(!A_KM || NI == 4, "K-major A is built for 128-row tiles");
-                        asm volatile("s_waitcnt lgkmcnt(0)"
-                                     : "+v"(tl[0]), "+v"(tl[1]), "+v"(tl[2]), "+v"(tl[3]), "+v"(th[0]), "+v"(th[1]), "+v"(th[2]), "+v"(th[3]));
-#pragma unroll
-                        for (int i = 0; i < NI; ++i) af[i] = combine_tr(tl[i], th[i]);
-                    }
+                    for (int j = 0; j < 4; ++j) bfr[j] = combine_tr(tl[j], th[j]);
 #pragma unroll
                     for (int i = 0; i < NI; ++i)
 #pragma unroll
                         for (int j = 0; j < 4; ++j)
                             acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[j], af[i], acc[i][j], 0, 0, 0);
-                    if constexpr (ROWSUM) {            // builds without the ring (APTAI_GEMM_RING5=0)
-                        if (rs_wave) {
-#pragma unroll
-                            for (int i = 0; i < NI; ++i) racc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones8, af[i], racc[i], 0, 0, 0);
-                        }
-                    }
                 }
             }
         }
@@ -377,11 +341,10 @@ __device__ __forceinline__ void gemm_tile_body(GemmArgs g, const int bid, const 
     //          LDS staging instead of serialising pass after pass.
     // Phase 1: accumulators -> fp32 LDS tile [128][128] (row pitch 528 B: conflict-free 16-B writes of 16 rows).
     // acc[i][j][r]: m = wm*64 + i*16 + (lane&15);  n = wn*64 + j*16 + (lane>>4)*4 + r
-    // The body is compiled per flag word (epi_dispatch; block-uniform branch); thread / tile indices enter through opaque copies so
-    // that the addresses of all those bodies are not hoisted above the main loop as loop invariants.
+    // The body is compiled per flag word (epi_dispatch; block-uniform branch); thread / tile indices enter through opaque copies (epi_idx).
     APTAI_STAMP(2);
-    int tid_e = tid, lane_e = lane, m0_e = __builtin_amdgcn_readfirstlane(m0), n0_e = __builtin_amdgcn_readfirstlane(n0);
-    asm volatile("" : "+v"(tid_e), "+v"(lane_e), "+s"(m0_e), "+s"(n0_e));
+    int tid_e, lane_e, m0_e, n0_e;
+    epi_idx(tid, lane, m0, n0, tid_e, lane_e, m0_e, n0_e);
     const int fx = epi_flag_word(g);
     auto body = [&](auto w) {
         constexpr int FM = decltype(w)::value;
@@ -440,28 +403,8 @@ __device__ __forceinline__ void gemm_tile_body(GemmArgs g, const int bid, const 
             float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
 #pragma unroll
             for (int r = 0; r < 8; ++r) v[r] = (flags & (APTAI_EPI_BIAS | APTAI_EPI_ALPHA)) ? fmaf(v[r], alpha, bias8[r]) : v[r];
-            if (OUT_F32) {
-                if (flags & APTAI_EPI_BIAS_ROW) {
-                    const float bm = g.bias[m];
-#pragma unroll
-                    for (int r = 0; r < 8; ++r) v[r] += bm;
-                }
-                if (flags & APTAI_EPI_RESIDUAL_F32) {             // fp32 residual stream (inference-only encoder): += res32[m][n..n+7]
-                    const float* R = (const float*)g.residual + (long)m * g.ldr + n;
-                    const f32x4 r0 = *(const f32x4*)R, r1 = *(const f32x4*)(R + 4);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) { v[r] += r0[r]; v[4 + r] += r1[r]; }
-                }
-                if (flags & APTAI_EPI_SPLIT_OUT) {               // exact-index mode: the result leaves as the next GEMM's split A operand
-                    split_out_store(g, flags, v, (long)m, n);
-                    return;
-                }
-                float* C = (float*)g.C + (long)split * g.slab_stride + (long)m * g.ldc + n;
-                *(f32x4*)C = (f32x4){v[0], v[1], v[2], v[3]};
-                *(f32x4*)(C + 4) = (f32x4){v[4], v[5], v[6], v[7]};
-                return;
-            }
-            epilogue_chunk<FM>(v, g, flags, (long)m, n, auxq, resq, sd0, sd1);
+            if (OUT_F32) store_f32_tail(g, flags, v, m, n, split);
+            else epilogue_chunk<FM>(v, g, flags, (long)m, n, auxq, resq, sd0, sd1);
         };
         if constexpr (!OUT_F32 && FM < 0) {
 #pragma unroll 1
@@ -492,21 +435,6 @@ __device__ __forceinline__ void gemm_tile_body(GemmArgs g, const int bid, const 
 
 template <bool A_KM, bool B_KM, bool OUT_F32>
 __global__ __launch_bounds__(NTHREADS, 3) void gemm_kernel(GemmArgs g) {
-#ifdef APTAI_EXP_STAGGER
-    if (g.exp_sleep > 0) {
-        bool late = true;
-        if (g.exp_cu_count != nullptr) {
-            unsigned hwid, xcc;
-            asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-            asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-            __shared__ unsigned arrival;
-            if (threadIdx.x == 0) arrival = atomicAdd(g.exp_cu_count + ((xcc & 7u) * 256u + ((hwid >> 8) & 0xffu)), 1u);
-            __syncthreads();
-            late = arrival == 1u;        // the CU's second block of the FIRST round only: later blocks inherit the offset
-        }
-        if (late) for (int i = 0; i < g.exp_sleep; ++i) __builtin_amdgcn_s_sleep(31);   // ~1 us each
-    }
-#endif
     gemm_tile_body<A_KM, B_KM, OUT_F32>(g, xcd_remap(blockIdx.x, g.tiles_m * g.tiles_n), gridDim.y > 1 ? (int)blockIdx.y : -1,
                                         blockIdx.z);
 }
@@ -533,7 +461,7 @@ struct GroupArgs {
 // The both-K-major instantiation asks for two blocks per CU: its 80 KiB ring fits no third, and under the three-block register budget
 // the four row-sum accumulators spilled (168 VGPRs + 12 B of scratch; 154 without them).
 template <bool A_KM, bool B_KM, bool OUT_F32>
-__global__ __launch_bounds__(NTHREADS, (A_KM && B_KM && APTAI_GEMM_RING5) ? 2 : 3) void gemm_grouped_kernel(GroupArgs ga) {
+__global__ __launch_bounds__(NTHREADS, (A_KM && B_KM) ? 2 : 3) void gemm_grouped_kernel(GroupArgs ga) {
     const int bid = xcd_remap(blockIdx.x, ga.total);
     int pi = 0;
 #pragma unroll
@@ -553,29 +481,6 @@ __global__ void splitk_reduce_kernel(const float* __restrict__ slabs, float* __r
         ((f32x4*)out)[i] = s;
     }
 }
-
-template <bool A_KM, bool B_KM, bool OUT_F32>
-int launch_gemm128(const GemmArgs& g, dim3 grid, hipStream_t stream) {
-    constexpr auto kern = gemm_kernel<A_KM, B_KM, OUT_F32>;
-    constexpr int smem = smem_for<A_KM, B_KM>();
-#ifdef APTAI_EXP_STAGGER
-    {   // development: per-call sleep and LDS request (occupancy) from the environment (tools/stagger_probe.py)
-        GemmArgs ge = g;
-        const char* e = getenv("APTAI_EXP_SLEEP");
-        ge.exp_sleep = e ? atoi(e) : 0;
-        const char* c = getenv("APTAI_EXP_CU_COUNT");          // device pointer (decimal) of 2048 zeroed words
-        ge.exp_cu_count = c ? (unsigned*)(uintptr_t)strtoull(c, nullptr, 10) : nullptr;
-        const char* m = getenv("APTAI_EXP_SMEM");
-        const int sm = m ? atoi(m) : smem;
-        (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, sm > smem ? sm : smem);
-        APTAI_LAUNCH(kern, grid, dim3(NTHREADS), sm > smem ? sm : smem, stream, ge);
-        APTAI_CHECK_LAUNCH("gemm_kernel");
-        return APTAI_OK;
-    }
-#endif
-    return launch_kernel<kern>({NTHREADS, smem, "gemm_kernel"}, grid, stream, g);
-}
-
 
 // =====================================================================================================================
 // 256 x 256 x 64 tile, 512 threads = 8 waves (2 M-groups x 4 N-columns), one block per CU, 128 KiB of LDS.
@@ -822,26 +727,8 @@ __device__ __forceinline__ void gemm256_epilogue_body(const GemmArgs& g, char* s
 #pragma unroll
                     for (int r = 0; r < 8; ++r) v[r] = fmaf(v[r], alpha, bias8[r]);
                 }
-                if (OUT_F32) {
-                    if (flags & APTAI_EPI_RESIDUAL_F32) {             // fp32 residual stream (inference-only encoder)
-                        const float* R = (const float*)g.residual + (long)m * g.ldr + n;
-                        const f32x4 r0 = *(const f32x4*)R, r1 = *(const f32x4*)(R + 4);
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) { v[r] += r0[r]; v[4 + r] += r1[r]; }
-                    }
-                    if (flags & APTAI_EPI_BIAS_ROW) { const float bm = g.bias[m];
-#pragma unroll
-                        for (int r = 0; r < 8; ++r) v[r] += bm; }
-                    if (flags & APTAI_EPI_BIAS_ROW) { const float bm = g.bias[m];
-#pragma unroll
-                    for (int r = 0; r < 8; ++r) v[r] += bm; }
-                if (flags & APTAI_EPI_SPLIT_OUT) { split_out_store(g, flags, v, (long)m, n); continue; }
-                    float* C = (float*)g.C + (long)split * g.slab_stride + (long)m * g.ldc + n;
-                    *(f32x4*)C = (f32x4){v[0], v[1], v[2], v[3]};
-                    *(f32x4*)(C + 4) = (f32x4){v[4], v[5], v[6], v[7]};
-                    continue;
-                }
-                epilogue_chunk<FM>(v, g, flags, (long)m, n, auxv[cur][k], resv[cur][k], sd0, sd1);
+                if (OUT_F32) store_f32_tail(g, flags, v, m, n, split);
+                else epilogue_chunk<FM>(v, g, flags, (long)m, n, auxv[cur][k], resv[cur][k], sd0, sd1);
             }
             if (HEAVY) __builtin_amdgcn_sched_barrier(0);
         }
@@ -853,11 +740,8 @@ template <bool OUT_F32>
 __device__ __forceinline__ void gemm256_epilogue(const GemmArgs& g, char* smem, const int m0, const int n0, const int split,
                                                  const f32x4 (&acc)[2][2][4][2], const int tid, const int lane, const int wr,
                                                  const int wc) {
-    // Everything the epilogue derives from the thread / tile indices is recomputed from opaque copies: otherwise the addresses of
-    // all the specialised bodies are hoisted above the main loop as loop invariants and spill INSIDE it (measured: main loop 18.4 ->
-    // 23.4 us per tile at K = 768).
-    int tid_e = tid, lane_e = lane, m0_e = __builtin_amdgcn_readfirstlane(m0), n0_e = __builtin_amdgcn_readfirstlane(n0);
-    asm volatile("" : "+v"(tid_e), "+v"(lane_e), "+s"(m0_e), "+s"(n0_e));
+    int tid_e, lane_e, m0_e, n0_e;                      // everything the bodies derive from the indices starts from opaque copies
+    epi_idx(tid, lane, m0, n0, tid_e, lane_e, m0_e, n0_e);
     const int fx = epi_flag_word(g);
     if (OUT_F32) {                                      // fp32 outputs (weight gradients, exact mode): alpha / bias / fp32 residual only
         gemm256_epilogue_body<true, -1>(g, smem, m0_e, n0_e, split, acc, tid_e, lane_e, wr, wc, fx);
@@ -882,25 +766,12 @@ __global__ __launch_bounds__(T2_THREADS, 2) void gemm256_kernel(GemmArgs g) {
     int tile_m, tile_n;
     raster2d(bid, g.tiles_m, g.tiles_n, g.raster_gm, tile_m, tile_n);
     const int m0 = tile_m * T2_BM, n0 = tile_n * T2_BN;
-    if (gridDim.y > 1) {
-        const int bo = blockIdx.y / g.nb_inner, bi = blockIdx.y % g.nb_inner;
-        g.A += bo * g.sA[0] + bi * g.sA[1];
-        g.B += bo * g.sB[0] + bi * g.sB[1];
-        const long co = bo * g.sC[0] + bi * g.sC[1];
-        g.C = (OUT_F32 && !(g.flags & APTAI_EPI_SPLIT_OUT)) ? (void*)((float*)g.C + co) : (void*)((bf16_t*)g.C + co);
-        if (g.out_pre) g.out_pre += co;
-        if (g.bias) g.bias += bo * g.sBias[0] + bi * g.sBias[1];
-        if (g.residual) g.residual += bo * g.sR[0] + bi * g.sR[1];
-        if (g.aux) g.aux += bo * g.sAux[0] + bi * g.sAux[1];
-    }
+    if (gridDim.y > 1) batch_offset<OUT_F32>(g, blockIdx.y / g.nb_inner, blockIdx.y % g.nb_inner);
     const int split = blockIdx.z;
-    const int total_kt = g.K / BK;
-    const int kt_begin = split * g.ktiles_per_split;
-    int kt_end = kt_begin + g.ktiles_per_split;
-    kt_end = kt_end < total_kt ? kt_end : total_kt;
+    const auto [kt_begin, nk] = splitk_range(g, split);
     f32x4 acc[2][2][4][2];                              // [qm][qn][i][j]
     APTAI_STAMP(0);
-    gemm256_mainloop<A_KM, B_KM>(g, smem, m0, n0, kt_begin, kt_end - kt_begin, acc, tid, lane, wr, wc, wave_base_tid);
+    gemm256_mainloop<A_KM, B_KM>(g, smem, m0, n0, kt_begin, nk, acc, tid, lane, wr, wc, wave_base_tid);
     APTAI_STAMP(2);
     gemm256_epilogue<OUT_F32>(g, smem, m0, n0, split, acc, tid, lane, wr, wc);
     APTAI_STAMP(3);
@@ -1139,7 +1010,7 @@ __device__ __forceinline__ const bf16_t* stage3_src(const bf16_t* __restrict__ b
 template <bool KM>
 __device__ __forceinline__ bf16x8 read_frag3(const char* lds_tile, int row_base, int ks, int lane) {
     if (!KM) {
-        return read_frag<false>(lds_tile, row_base, ks, lane);
+        return read_frag(lds_tile, row_base, ks, lane);
     } else {
         const char* panel = lds_tile + (row_base >> 6) * 8192;
         const int rb = row_base & 63;
@@ -1168,31 +1039,13 @@ __global__ __launch_bounds__(T3_THREADS, 1) void gemm192_kernel(GemmArgs g) {
     const int wave_base_tid = wave * 64;
 
     const int nwg = g.tiles_m * g.tiles_n;
-    int bid = blockIdx.x;
-    {
-        const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }
+    const int bid = xcd_remap(blockIdx.x, nwg);
     int tile_m, tile_n;
     raster2d(bid, g.tiles_m, g.tiles_n, g.raster_gm, tile_m, tile_n);
     const int m0 = tile_m * T3_BM, n0 = tile_n * T3_BN;
-    if (gridDim.y > 1) {
-        const int bo = blockIdx.y / g.nb_inner, bi = blockIdx.y % g.nb_inner;
-        g.A += bo * g.sA[0] + bi * g.sA[1];
-        g.B += bo * g.sB[0] + bi * g.sB[1];
-        const long co = bo * g.sC[0] + bi * g.sC[1];
-        g.C = (OUT_F32 && !(g.flags & APTAI_EPI_SPLIT_OUT)) ? (void*)((float*)g.C + co) : (void*)((bf16_t*)g.C + co);
-        if (g.out_pre) g.out_pre += co;
-        if (g.bias) g.bias += bo * g.sBias[0] + bi * g.sBias[1];
-        if (g.residual) g.residual += bo * g.sR[0] + bi * g.sR[1];
-        if (g.aux) g.aux += bo * g.sAux[0] + bi * g.sAux[1];
-    }
+    if (gridDim.y > 1) batch_offset<OUT_F32>(g, blockIdx.y / g.nb_inner, blockIdx.y % g.nb_inner);
     const int split = blockIdx.z;
-    const int total_kt = g.K / BK;
-    const int kt_begin = split * g.ktiles_per_split;
-    int kt_end = kt_begin + g.ktiles_per_split;
-    kt_end = kt_end < total_kt ? kt_end : total_kt;
-    const int nk = kt_end - kt_begin;
+    const auto [kt_begin, nk] = splitk_range(g, split);
 
     // staging sources advance by one K-tile per stage() call (stages are issued in K order)
     const bf16_t* pa[2];
@@ -1223,7 +1076,7 @@ __global__ __launch_bounds__(T3_THREADS, 1) void gemm192_kernel(GemmArgs g) {
 #pragma unroll
         for (int j = 0; j < 3; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
-    if constexpr (!A_KM && B_KM && APTAI_GEMM192_ASM) {
+    if constexpr (!A_KM && B_KM) {
         // dgrad layout (A K-contiguous, B K-major): every LDS read through inline asm with counted waits.  Behind an LDS-DMA the
         // compiler puts `s_waitcnt vmcnt(0)` in front of each ds_read_tr builtin (section "asm transposing reads" of the 128-tile
         // kernel), which drains this kernel's three-stage ring at every K-tile: the builtin form ran at the speed of the 64-row
@@ -1372,10 +1225,10 @@ __global__ __launch_bounds__(T3_THREADS, 1) void gemm192_kernel(GemmArgs g) {
 
     // ------------------------------------------------------------------ epilogue (same scheme as gemm_kernel)
     // 128 x 192 outputs = 3072 chunks of 8 columns = 6 passes x 512 threads; chunk c -> row c / 24, column 8 * (c % 24)
-    // compiled per flag word, indices through opaque copies (see gemm_tile_body)
+    // compiled per flag word, indices through opaque copies (epi_idx)
     APTAI_STAMP(2);
-    int tid_e = tid, lane_e = lane, m0_e = __builtin_amdgcn_readfirstlane(m0), n0_e = __builtin_amdgcn_readfirstlane(n0);
-    asm volatile("" : "+v"(tid_e), "+v"(lane_e), "+s"(m0_e), "+s"(n0_e));
+    int tid_e, lane_e, m0_e, n0_e;
+    epi_idx(tid, lane, m0, n0, tid_e, lane_e, m0_e, n0_e);
     const int fx = epi_flag_word(g);
     auto body = [&](auto w) {
         constexpr int FM = decltype(w)::value;
@@ -1386,7 +1239,7 @@ __global__ __launch_bounds__(T3_THREADS, 1) void gemm192_kernel(GemmArgs g) {
             resv[pass] = (u32x4){0u, 0u, 0u, 0u};
             auxv[pass] = (u32x4){0u, 0u, 0u, 0u};
         }
-        if (!OUT_F32 && (flags & (APTAI_EPI_RESIDUAL | APTAI_EPI_DGELU | APTAI_EPI_MUL_AUX))) {     // uniform; addresses clamped, no per-lane_e branches
+        if (!OUT_F32 && (flags & (APTAI_EPI_RESIDUAL | APTAI_EPI_DGELU | APTAI_EPI_MUL_AUX))) {     // uniform; addresses clamped, no per-lane branches
     #pragma unroll
             for (int pass = 0; pass < 6; ++pass) {
                 const int c = pass * T3_THREADS + tid_e, ml = c / 24, cl = (c - ml * 24) * 8;
@@ -1427,19 +1280,7 @@ __global__ __launch_bounds__(T3_THREADS, 1) void gemm192_kernel(GemmArgs g) {
                 for (int r = 0; r < 8; ++r) v[r] *= alpha;
             }
             if (OUT_F32) {
-                if (flags & APTAI_EPI_RESIDUAL_F32) {             // fp32 residual stream (inference-only encoder): += res32[m][n..n+7]
-                    const float* R = (const float*)g.residual + (long)m * g.ldr + n;
-                    const f32x4 r0 = *(const f32x4*)R, r1 = *(const f32x4*)(R + 4);
-    #pragma unroll
-                    for (int r = 0; r < 4; ++r) { v[r] += r0[r]; v[4 + r] += r1[r]; }
-                }
-                if (flags & APTAI_EPI_BIAS_ROW) { const float bm = g.bias[m];
-#pragma unroll
-                    for (int r = 0; r < 8; ++r) v[r] += bm; }
-                if (flags & APTAI_EPI_SPLIT_OUT) { split_out_store(g, flags, v, (long)m, n); continue; }
-                float* C = (float*)g.C + (long)split * g.slab_stride + (long)m * g.ldc + n;
-                *(f32x4*)C = (f32x4){v[0], v[1], v[2], v[3]};
-                *(f32x4*)(C + 4) = (f32x4){v[4], v[5], v[6], v[7]};
+                store_f32_tail(g, flags, v, m, n, split);
                 continue;
             }
             epilogue_chunk<FM>(v, g, flags, (long)m, n, auxv[pass], resv[pass], sd0, sd1);
@@ -1718,7 +1559,7 @@ static int launch_plan(const aptai_gemm_desc* d, const aptai_gemm_plan_info& p, 
         case 256: return launch_kernel<gemm256_kernel<A, B, F>>({T2_THREADS, T2_SMEM, "gemm256_kernel"}, grid, stream, g);
         case 257: return launch_gemm256_sk<A, B, F>(g, d->sk_workspace, stream);
         case 448: return launch_gemm_t4(g, B, stream);
-        default: return launch_gemm128<A, B, F>(g, grid, stream);
+        default: return launch_kernel<gemm_kernel<A, B, F>>({NTHREADS, smem_for<A, B>(), "gemm_kernel"}, grid, stream, g);
         }
     });
     if (rc != APTAI_OK) return rc;

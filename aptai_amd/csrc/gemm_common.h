@@ -5,29 +5,16 @@
 
 namespace aptai_gemm {
 
-
-#ifndef APTAI_GEMM_HOIST
-#define APTAI_GEMM_HOIST 1
-#endif
 constexpr int BM = 128, BN = 128, BK = 64;
 constexpr int NTHREADS = 256;
 constexpr int STAGE_BYTES = (BM * BK + BN * BK) * 2;   // 32 KiB
 constexpr int OPER_BYTES = BM * BK * 2;                // 16 KiB per operand tile
 constexpr int EPI_PITCH = BN * 4 + 16;                 // fp32 epilogue tile row pitch (bytes)
 constexpr int SMEM_BYTES = BM * EPI_PITCH > 2 * STAGE_BYTES ? BM * EPI_PITCH : 2 * STAGE_BYTES;
-#ifndef APTAI_GEMM_RING5
-#define APTAI_GEMM_RING5 1
-#endif
-#ifndef APTAI_GEMM_M64_ASM
-#define APTAI_GEMM_M64_ASM 1
-#endif
-#ifndef APTAI_GEMM192_ASM
-#define APTAI_GEMM192_ASM 1
-#endif
 constexpr int RING_HALF_BYTES = (BM + BN) * 32 * 2;    // 16 KiB: 32 k-rows of both operands
 constexpr int SMEM_RING_BYTES = 5 * RING_HALF_BYTES;   // 80 KiB: two blocks per CU use all of the 160 KiB
 static_assert(SMEM_RING_BYTES >= BM * EPI_PITCH, "the epilogue tile must fit the ring");
-template <bool A_KM, bool B_KM> constexpr int smem_for() { return (A_KM && B_KM && APTAI_GEMM_RING5) ? SMEM_RING_BYTES : SMEM_BYTES; }
+template <bool A_KM, bool B_KM> constexpr int smem_for() { return (A_KM && B_KM) ? SMEM_RING_BYTES : SMEM_BYTES; }
 
 struct GemmArgs {
     const bf16_t* A; long lda;
@@ -52,16 +39,33 @@ struct GemmArgs {
     int colscale_n; float colscale;   // columns [0, colscale_n) of the bf16 output are multiplied by colscale (after alpha / bias)
     int split_pieces;                 // APTAI_EPI_SPLIT_OUT: 3 or 6 bf16 pieces per fp32 result (C is bf16, ldc in bf16 elements)
     int split_bcol;                   // ... columns >= split_bcol in the weight-side piece order
-#ifdef APTAI_EXP_STAGGER
-    int exp_sleep;                    // development (tools/ab builds): s_sleep(127) iterations at the start of every SECOND block to arrive on a CU
-    unsigned* exp_cu_count;           // ... per-CU arrival counters (2048 words, zeroed by the caller before the launch), or null = every block sleeps
-#endif
     // 2-level batching: blockIdx.y = outer * nb_inner + inner; element offsets per level
     int nb_inner;
     long sA[2], sB[2], sC[2], sBias[2], sR[2], sAux[2];
 };
 
+// batch (bo, bi) of a 2-level batched launch: every operand pointer of the block's own copy of g moves to its problem
+template <bool OUT_F32>
+__device__ __forceinline__ void batch_offset(GemmArgs& g, const int bo, const int bi) {
+    g.A += bo * g.sA[0] + bi * g.sA[1];
+    g.B += bo * g.sB[0] + bi * g.sB[1];
+    const long co = bo * g.sC[0] + bi * g.sC[1];
+    g.C = (OUT_F32 && !(g.flags & APTAI_EPI_SPLIT_OUT)) ? (void*)((float*)g.C + co) : (void*)((bf16_t*)g.C + co);
+    if (g.out_pre) g.out_pre += co;
+    if (g.bias) g.bias += bo * g.sBias[0] + bi * g.sBias[1];
+    if (g.residual) g.residual += bo * g.sR[0] + bi * g.sR[1];
+    if (g.aux) g.aux += bo * g.sAux[0] + bi * g.sAux[1];
+}
 
+// the K-tiles of split-K slab `split`: [kt_begin, kt_begin + nk)
+struct KRange { int kt_begin, nk; };
+__device__ __forceinline__ KRange splitk_range(const GemmArgs& g, const int split) {
+    const int total_kt = g.K / BK;
+    const int kt_begin = split * g.ktiles_per_split;
+    int kt_end = kt_begin + g.ktiles_per_split;
+    kt_end = kt_end < total_kt ? kt_end : total_kt;
+    return {kt_begin, kt_end - kt_begin};
+}
 
 __device__ __forceinline__ int km_swz(int krow) { return ((krow & 3) << 2) | ((krow >> 2) & 3); }
 
@@ -181,11 +185,17 @@ __device__ __forceinline__ void epilogue_chunk(float (&v)[8], const GemmArgs& g,
 #pragma unroll
         for (int r = 0; r < 4; ++r) { v[2 * r] += lo_bf(resq[r]); v[2 * r + 1] += hi_bf(resq[r]); }
     }
-#ifdef APTAI_EXP_NOSTORE
-    if (g.M < 0)
-#endif
     *(u32x4*)((bf16_t*)g.C + m * g.ldc + n) =
         (u32x4){pack2bf(v[0], v[1]), pack2bf(v[2], v[3]), pack2bf(v[4], v[5]), pack2bf(v[6], v[7])};
+}
+
+// Thread / tile indices of an epilogue, as opaque copies: everything the per-flag-word bodies derive from them is computed behind this
+// point, otherwise the addresses of all those bodies are hoisted above the main loop as loop invariants and spill INSIDE it (measured on
+// the 256 x 256 tile: main loop 18.4 -> 23.4 us at K = 768).  Four plain ints of the caller, not a struct: with a struct captured whole
+// by the bodies' closures the register allocation of the main loops came out different.
+__device__ __forceinline__ void epi_idx(const int tid, const int lane, const int m0, const int n0, int& tid_e, int& lane_e, int& m0_e, int& n0_e) {
+    tid_e = tid, lane_e = lane, m0_e = __builtin_amdgcn_readfirstlane(m0), n0_e = __builtin_amdgcn_readfirstlane(n0);
+    asm volatile("" : "+v"(tid_e), "+v"(lane_e), "+s"(m0_e), "+s"(n0_e));
 }
 
 // ---- global -> LDS staging of one operand tile (1024 x 16-B chunks, 4 per thread).
@@ -209,29 +219,14 @@ __device__ __forceinline__ const bf16_t* stage_src(const bf16_t* __restrict__ ba
     }
 }
 
-// ---- fragment reads (16 rows x 32 k) for MFMA 16x16x32
-template <bool KM>
+// ---- fragment reads (16 rows x 32 k) for MFMA 16x16x32.  K-contiguous operand: one ds_read_b128
 __device__ __forceinline__ bf16x8 read_frag(const char* lds_tile, int row_base, int ks, int lane) {
-    if (!KM) {
-        const int row = row_base + (lane & 15);
-        const int q = ks * 4 + (lane >> 4);
-        return *(const bf16x8*)(lds_tile + row * 128 + ((q ^ (row & 7)) << 4));
-    } else {
-        const int g = lane >> 4, i = lane & 15, qq = i >> 2, p = i & 3;
-        const int ch = (row_base >> 3) + (p >> 1);
-        const int sub = (p & 1) << 3;
-        const int k_lo = ks * 32 + g * 8 + qq;
-        const int k_hi = k_lo + 4;
-        const char* a0 = lds_tile + k_lo * 256 + ((ch ^ km_swz(k_lo)) << 4) + sub;
-        const char* a1 = lds_tile + k_hi * 256 + ((ch ^ km_swz(k_hi)) << 4) + sub;
-        short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) short4v*)a0);
-        short4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) short4v*)a1);
-        short8v r = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        return __builtin_bit_cast(bf16x8, r);
-    }
+    const int row = row_base + (lane & 15);
+    const int q = ks * 4 + (lane >> 4);
+    return *(const bf16x8*)(lds_tile + row * 128 + ((q ^ (row & 7)) << 4));
 }
 
-// The same K-major fragment through inline asm, in two 4-element halves that the caller completes with combine_tr() after its
+// A K-major fragment ([64 k][256 B] image, km_swz) through inline asm, in two 4-element halves that the caller completes with combine_tr() after its
 // own `s_waitcnt lgkmcnt`.  Why: behind an LDS-DMA the compiler puts `s_waitcnt vmcnt(0)` in front of every
 // __builtin_amdgcn_ds_read_tr16_b64 (it cannot tell which LDS bytes the DMA writes), i.e. right after the staging loads of the
 // NEXT K-tile have been issued - the block then waits for them before it computes the current one and only the other blocks of
@@ -263,7 +258,7 @@ struct Frag {
     short4v lo, hi;
     __device__ __forceinline__ void read(const char* lds_tile, int row_base, int ks, int lane) {
         if constexpr (KM) read_frag_tr_asm(lds_tile, row_base, ks, lane, lo, hi);
-        else v = read_frag<false>(lds_tile, row_base, ks, lane);
+        else v = read_frag(lds_tile, row_base, ks, lane);
     }
     __device__ __forceinline__ bf16x8 get() const {
         if constexpr (KM) return combine_tr(lo, hi);
@@ -313,6 +308,29 @@ __device__ __forceinline__ void split_out_store(const GemmArgs& g, const int fla
         put(1, md); put(2, h);
         if (g.split_pieces == 6) { put(3, md); put(4, lw); put(5, h); }
     }
+}
+
+// The tail of every fp32-output epilogue, 8 consecutive results of row m behind alpha / column bias.  The order is fixed for all tiles:
+// fp32 residual, row bias (once), then the split-piece store or the two 16-byte stores into slab `split`.
+__device__ __forceinline__ void store_f32_tail(const GemmArgs& g, const int flags, float (&v)[8], const int m, const int n, const int split) {
+    if (flags & APTAI_EPI_RESIDUAL_F32) {                // fp32 residual stream (inference-only encoder): += res32[m][n..n+7]
+        const float* R = (const float*)g.residual + (long)m * g.ldr + n;
+        const f32x4 r0 = *(const f32x4*)R, r1 = *(const f32x4*)(R + 4);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) { v[r] += r0[r]; v[4 + r] += r1[r]; }
+    }
+    if (flags & APTAI_EPI_BIAS_ROW) {
+        const float bm = g.bias[m];
+#pragma unroll
+        for (int r = 0; r < 8; ++r) v[r] += bm;
+    }
+    if (flags & APTAI_EPI_SPLIT_OUT) {                   // exact-index mode: the result leaves as the next GEMM's split A operand
+        split_out_store(g, flags, v, (long)m, n);
+        return;
+    }
+    float* C = (float*)g.C + (long)split * g.slab_stride + (long)m * g.ldc + n;
+    *(f32x4*)C = (f32x4){v[0], v[1], v[2], v[3]};
+    *(f32x4*)(C + 4) = (f32x4){v[4], v[5], v[6], v[7]};
 }
 
 // ---- host side: the one launcher of the family.  Kern is a kernel instantiation, so the dynamic-LDS attribute is set once per

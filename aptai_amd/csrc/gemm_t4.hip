@@ -352,9 +352,8 @@ __global__ __launch_bounds__(T4_THREADS, 2) void gemm_t4_kernel(GemmArgs g) {
     const int m0 = tile_m * T4_BM, n0 = tile_n * T4_BN;
     f32x4 acc[4][6];                                    // [i][j]: rows wr * 64 + i * 16, columns wc * 96 + j * 16
     t4_mainloop<B_KM>(g, smem, m0, n0, 0, g.K / BK, acc, tid, lane, wave, wr, wc);
-    // (indices through opaque copies: keeps the specialised epilogue bodies' address arithmetic out of the main loop, see gemm.hip)
-    int tid_e = tid, lane_e = lane, m0_e = __builtin_amdgcn_readfirstlane(m0), n0_e = __builtin_amdgcn_readfirstlane(n0);
-    asm volatile("" : "+v"(tid_e), "+v"(lane_e), "+s"(m0_e), "+s"(n0_e));
+    int tid_e, lane_e, m0_e, n0_e;                      // indices through opaque copies
+    epi_idx(tid, lane, m0, n0, tid_e, lane_e, m0_e, n0_e);
     const int fx = epi_flag_word(g);
     epi_dispatch(fx, [&](auto w) { t4_epilogue_body<decltype(w)::value>(g, smem, m0_e, n0_e, acc, tid_e, lane_e, wr, wc, fx); });
 }

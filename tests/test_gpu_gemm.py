@@ -3,6 +3,8 @@
 Inputs are rounded to bf16 first, so the only differences are fp32 accumulation order and the final
 bf16 rounding of the output (rel 2^-8): tolerance 1e-2 * scale.  Integer-valued cases must be exact.
 """
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -275,3 +277,45 @@ def test_256x192_tile_equals_the_128_tile_bit_for_bit(M, N, K, km):
         assert torch.equal(o1, o2), (sorted(h), (o1.float() - o2.float()).abs().max().item())
         if "out_pre" in h:
             assert torch.equal(p1, p2)
+
+
+_BIAS_ROW_TILES = (128, 192, 256)
+
+
+@functools.lru_cache(maxsize=None)
+def _bias_row_problem(with_res):
+    """NT, fp32 output, bias indexed by the output ROW, optionally an fp32 residual: inputs, the fp32 CPU reference (computed once) and the
+    outputs of the three tiles that take the flag (launched once)."""
+    from aptai_amd import ops
+    M, N, K = 272, 264, 128          # partial tiles both ways for 128 x 128, 128 x 192 and 256 x 256; two 256-row tiles; two K-tiles
+    g = torch.Generator().manual_seed(272 + 264 + 128)
+    a, b = _rand((M, K), g), _rand((N, K), g)
+    bias = torch.randn(M, generator=g) * 16          # ~ the spread of the products at K = 128: a doubled or missing bias is an O(output) error
+    res = torch.randn(M, N, generator=g) * 16
+    ref = a.float() @ b.float().t() + bias[:, None]
+    kw = {}
+    if with_res:
+        ref = ref + res
+        kw["residual_f32"] = res.cuda()
+    outs = {t: ops.gemm(a.cuda(), b.cuda(), M, N, K, out_f32=True, bias_row=bias.cuda(), tile=t, **kw).cpu() for t in _BIAS_ROW_TILES}
+    return ref, outs
+
+
+@pytest.mark.parametrize("with_res", [False, True], ids=["plain", "residual_f32"])
+@pytest.mark.parametrize("tile", _BIAS_ROW_TILES)
+def test_nt_f32_bias_row_is_added_once(tile, with_res):
+    """ops.gemm(..., out_f32=True, bias_row=...) on every tile that accepts the flag (not through the `ops` fixture: the other tile values
+    refuse it by design).  The output is fp32, so the only difference from the reference is summation order, bounded by
+    K 2^-24 sum|a b| ~ 6e-4 absolute on an output scale of ~60: tolerance 1e-4 * max|ref| (the file's 1e-2 would let a missing or doubled
+    bias term of a small row through)."""
+    ref, outs = _bias_row_problem(with_res)
+    assert outs[tile].dtype == torch.float32
+    _cmp(outs[tile], ref, tol=1e-4)
+
+
+@pytest.mark.parametrize("with_res", [False, True], ids=["plain", "residual_f32"])
+def test_nt_f32_bias_row_tiles_agree(with_res):
+    """One fp32 tail for all tiles: fp32 residual, then the row bias once - the three kernels agree with each other."""
+    _, outs = _bias_row_problem(with_res)
+    for t in _BIAS_ROW_TILES[1:]:
+        _cmp(outs[t], outs[_BIAS_ROW_TILES[0]], tol=1e-4)
