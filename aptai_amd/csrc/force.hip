@@ -327,6 +327,114 @@ __global__ __launch_bounds__(256) void xattn_softmax_bwd_kernel(const float* __r
     const float s1 = wave_sum(a * da), s2 = wave_sum(dl);
     if (ok) d_raw[row * N + lane] = a * (da - s1) + dl - __expf(al) * s2;
 }
+// Wide form, 64 < N <= 255 (and N = 64 with forward-sum rows): still one wave per (b,t) row; lane l holds the SL slots l, l + 64,
+// l + 128, l + 192 (the lane-strided layout of ctc_lpe_kernel's classes).  Per-lane maxima and sums run over the lane's slots in
+// ascending order and then go through the same wave_max / wave_sum trees as above: a masked slot contributes exp(~-1000) = 0.f
+// exactly, so a transcript that would fit the narrow kernel gets the narrow kernel's bits in its own columns, whatever N is.
+// fs_rows: [-1 | att_log[0..N) | zeros] at pitch ld_fs = round_up(N + 1, 64) <= 64 (SL + 1); column c = att_log column c - 1, which
+// for lane 0 of slot group j >= 1 sits in lane 63's group j - 1.  align: lowest SLOT index among equal maxima (not lowest lane).
+template <int SL>
+__global__ __launch_bounds__(256) void xattn_softmax_fwd_wide_kernel(const float* __restrict__ raw, const int* __restrict__ ids,
+                                                                     float* __restrict__ energy, float* __restrict__ att,
+                                                                     float* __restrict__ att_log, int64_t* __restrict__ align,
+                                                                     float* __restrict__ fs_rows, int ld_fs, int B, int T, int N) {
+    const long row = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const int lane = threadIdx.x & 63;
+    if (row >= (long)B * T) return;
+    const int b = (int)(row / T);
+    float m1[SL], e[SL], ex[SL], al[SL];
+    float pm = -INFINITY;
+#pragma unroll
+    for (int j = 0; j < SL; ++j) {
+        const int n = j * 64 + lane;
+        const bool ok = n < N;
+        m1[j] = ok ? ((ids[b * N + n] != 0) ? 0.f : -1000.f) : 0.f;
+        e[j] = ok ? raw[row * N + n] + m1[j] : -INFINITY;
+        pm = fmaxf(pm, e[j]);
+    }
+    float mx = wave_max(pm);
+    float ps = 0.f;
+#pragma unroll
+    for (int j = 0; j < SL; ++j) {
+        ex[j] = (j * 64 + lane < N) ? __expf(e[j] - mx) : 0.f;
+        ps = j == 0 ? ex[0] : ps + ex[j];
+    }
+    float se = wave_sum(ps);
+    pm = -INFINITY;
+#pragma unroll
+    for (int j = 0; j < SL; ++j) {
+        const int n = j * 64 + lane;
+        const bool ok = n < N;
+        if (ok) { energy[row * N + n] = e[j]; att[row * N + n] = ex[j] / se; }
+        e[j] = ok ? e[j] + m1[j] : -INFINITY;                       // the second -1000
+        pm = fmaxf(pm, e[j]);
+    }
+    mx = wave_max(pm);
+#pragma unroll
+    for (int j = 0; j < SL; ++j) {
+        ex[j] = (j * 64 + lane < N) ? expf(e[j] - mx) : 0.f;
+        ps = j == 0 ? ex[0] : ps + ex[j];
+    }
+    se = wave_sum(ps);
+    const float lse = mx + logf(se);
+    float best = -INFINITY;
+    int bi = lane;
+#pragma unroll
+    for (int j = 0; j < SL; ++j) {
+        const int n = j * 64 + lane;
+        const bool ok = n < N;
+        al[j] = e[j] - lse;
+        if (ok) att_log[row * N + n] = al[j];
+        const float v = ok ? al[j] : -INFINITY;
+        if (j == 0 || v > best) { best = v; bi = n; }               // ascending slots, strict >: the lane's lowest slot wins its ties
+    }
+    if (fs_rows) {
+        const int groups = ld_fs >> 6;                              // wave-uniform: every lane takes part in the shuffles below
+#pragma unroll
+        for (int j = 0; j <= SL; ++j) {
+            if (j < groups) {
+                const float up = j < SL ? __shfl_up(al[j < SL ? j : 0], 1, 64) : 0.f;
+                const float wrap = j >= 1 ? __shfl(al[j >= 1 ? j - 1 : 0], 63, 64) : -1.f;
+                const int c = j * 64 + lane;
+                fs_rows[row * ld_fs + c] = c <= N ? (lane == 0 ? wrap : up) : 0.f;
+            }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ob = __shfl_xor(best, o, 64);
+        const int oi = __shfl_xor(bi, o, 64);
+        if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+    }
+    if (lane == 0 && align) align[row] = bi;
+}
+template <int SL>
+__global__ __launch_bounds__(256) void xattn_softmax_bwd_wide_kernel(const float* __restrict__ att, const float* __restrict__ att_log,
+                                                                     const float* __restrict__ d_att, const float* __restrict__ d_attlog,
+                                                                     long ld_dattlog, float* __restrict__ d_raw, long rows, int N) {
+    const long row = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const int lane = threadIdx.x & 63;
+    if (row >= rows) return;
+    float a[SL], da[SL], al[SL], dl[SL];
+    float p1 = 0.f, p2 = 0.f;
+#pragma unroll
+    for (int j = 0; j < SL; ++j) {
+        const int n = j * 64 + lane;
+        const bool ok = n < N;
+        a[j] = ok ? att[row * N + n] : 0.f;
+        da[j] = (ok && d_att) ? d_att[row * N + n] : 0.f;
+        al[j] = ok ? att_log[row * N + n] : 0.f;
+        dl[j] = (ok && d_attlog) ? d_attlog[row * ld_dattlog + n] : 0.f;
+        p1 = j == 0 ? a[0] * da[0] : p1 + a[j] * da[j];
+        p2 = j == 0 ? dl[0] : p2 + dl[j];
+    }
+    const float s1 = wave_sum(p1), s2 = wave_sum(p2);
+#pragma unroll
+    for (int j = 0; j < SL; ++j) {
+        const int n = j * 64 + lane;
+        if (n < N) d_raw[row * N + n] = a[j] * (da[j] - s1) + dl[j] - __expf(al[j]) * s2;
+    }
+}
 
 // ------------------------------------------------------------------------------------------ fp32 LayerNorm (cols % 64 == 0, <= 1024)
 __global__ __launch_bounds__(256) void ln32_fwd_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
@@ -613,7 +721,7 @@ extern "C" int aptai_embed_pe_fwd(const int32_t* ids, const float* emb, const fl
 }
 extern "C" int aptai_embed_bwd(const int32_t* ids, const float* dout, float* demb_zeroed, int64_t rows, int64_t D, float dropout_p,
                                uint64_t seed, void* stream) {
-    APTAI_REQUIRE(ids && dout && demb_zeroed && rows > 0 && rows <= 8192, "aptai_embed_bwd: bad arguments (at most 8192 rows)");
+    APTAI_REQUIRE(ids && dout && demb_zeroed && rows > 0 && rows <= 8192, "aptai_embed_bwd: bad arguments (at most 8192 rows = batch * phoneme slots, got %ld)", (long)rows);
     const uint32_t thr = drop_thr16(dropout_p);
     APTAI_LAUNCH(embed_bwd_kernel, dim3((unsigned)rows), dim3(128), 0, (hipStream_t)stream, ids, dout, demb_zeroed, (int)rows, (int)D,
                  drop_scale(thr), (uint32_t)seed, (uint32_t)(seed >> 32), thr);
@@ -623,8 +731,8 @@ extern "C" int aptai_embed_bwd(const int32_t* ids, const float* dout, float* dem
 
 extern "C" int aptai_xattn_softmax_fwd(const float* raw, const int32_t* phn_ids, float* energy, float* att, float* att_log,
                                        int64_t* align, float* fs_rows, int64_t B, int64_t T, int64_t N, void* stream) {
-    APTAI_REQUIRE(raw && phn_ids && energy && att && att_log && N > 0 && N <= 64, "aptai_xattn_softmax_fwd: bad arguments (N <= 64)");
-    APTAI_REQUIRE(fs_rows == nullptr || N <= 63, "aptai_xattn_softmax_fwd: the forward-sum rows hold at most 63 phoneme slots");
+    APTAI_REQUIRE(raw && phn_ids && energy && att && att_log && N > 0 && N <= 64, "aptai_xattn_softmax_fwd: bad arguments (N <= 64; aptai_xattn_softmax_fwd_wide takes up to 255)");
+    APTAI_REQUIRE(fs_rows == nullptr || N <= 63, "aptai_xattn_softmax_fwd: 64-float forward-sum rows hold at most 63 phoneme slots (aptai_xattn_softmax_fwd_wide: up to 255)");
     APTAI_LAUNCH(xattn_softmax_fwd_kernel, dim3((unsigned)ceil_div(B * T * 64, 256)), dim3(256), 0, (hipStream_t)stream, raw, phn_ids,
                  energy, att, att_log, align, fs_rows, (int)B, (int)T, (int)N);
     APTAI_CHECK_LAUNCH("xattn_softmax_fwd_kernel");
@@ -632,10 +740,52 @@ extern "C" int aptai_xattn_softmax_fwd(const float* raw, const int32_t* phn_ids,
 }
 extern "C" int aptai_xattn_softmax_bwd(const float* att, const float* att_log, const float* d_att, const float* d_attlog,
                                        int64_t ld_dattlog, float* d_raw, int64_t rows, int64_t N, void* stream) {
-    APTAI_REQUIRE(att && att_log && d_raw && N > 0 && N <= 64, "aptai_xattn_softmax_bwd: bad arguments");
+    APTAI_REQUIRE(att && att_log && d_raw && N > 0 && N <= 64, "aptai_xattn_softmax_bwd: bad arguments (N <= 64; aptai_xattn_softmax_bwd_wide takes up to 255)");
     APTAI_LAUNCH(xattn_softmax_bwd_kernel, dim3((unsigned)ceil_div(rows * 64, 256)), dim3(256), 0, (hipStream_t)stream, att, att_log,
                  d_att, d_attlog, (long)(ld_dattlog > 0 ? ld_dattlog : N), d_raw, (long)rows, (int)N);
     APTAI_CHECK_LAUNCH("xattn_softmax_bwd_kernel");
+    return APTAI_OK;
+}
+// 64 <= N <= 255: SL = slots per lane (2, 3 or 4; N = 64 runs with 2 so that its forward-sum rows get their second 64 columns)
+extern "C" int aptai_xattn_softmax_fwd_wide(const float* raw, const int32_t* phn_ids, float* energy, float* att, float* att_log,
+                                            int64_t* align, float* fs_rows, int64_t ld_fs, int64_t B, int64_t T, int64_t N,
+                                            void* stream) {
+    APTAI_REQUIRE(raw && phn_ids && energy && att && att_log && B > 0 && T > 0 && N >= 64 && N <= 255,
+                  "aptai_xattn_softmax_fwd_wide: bad arguments (64 <= N <= 255, got N = %ld)", (long)N);
+    APTAI_REQUIRE(fs_rows == nullptr || ld_fs == ceil_div(N + 1, 64) * 64,
+                  "aptai_xattn_softmax_fwd_wide: forward-sum rows of N = %ld slots (255 at most) have pitch round_up(N + 1, 64), got %ld",
+                  (long)N, (long)ld_fs);
+    const dim3 grid((unsigned)ceil_div(B * T * 64, 256)), block(256);
+    if (N <= 128)
+        APTAI_LAUNCH(xattn_softmax_fwd_wide_kernel<2>, grid, block, 0, (hipStream_t)stream, raw, phn_ids, energy, att, att_log, align,
+                     fs_rows, (int)ld_fs, (int)B, (int)T, (int)N);
+    else if (N <= 192)
+        APTAI_LAUNCH(xattn_softmax_fwd_wide_kernel<3>, grid, block, 0, (hipStream_t)stream, raw, phn_ids, energy, att, att_log, align,
+                     fs_rows, (int)ld_fs, (int)B, (int)T, (int)N);
+    else
+        APTAI_LAUNCH(xattn_softmax_fwd_wide_kernel<4>, grid, block, 0, (hipStream_t)stream, raw, phn_ids, energy, att, att_log, align,
+                     fs_rows, (int)ld_fs, (int)B, (int)T, (int)N);
+    APTAI_CHECK_LAUNCH("xattn_softmax_fwd_wide_kernel");
+    return APTAI_OK;
+}
+extern "C" int aptai_xattn_softmax_bwd_wide(const float* att, const float* att_log, const float* d_att, const float* d_attlog,
+                                            int64_t ld_dattlog, float* d_raw, int64_t rows, int64_t N, void* stream) {
+    APTAI_REQUIRE(att && att_log && d_raw && rows > 0 && N >= 64 && N <= 255,
+                  "aptai_xattn_softmax_bwd_wide: bad arguments (64 <= N <= 255, got N = %ld)", (long)N);
+    APTAI_REQUIRE(ld_dattlog == 0 || ld_dattlog >= N, "aptai_xattn_softmax_bwd_wide: d_attlog pitch %ld below N = %ld", (long)ld_dattlog,
+                  (long)N);
+    const dim3 grid((unsigned)ceil_div(rows * 64, 256)), block(256);
+    const long ld = (long)(ld_dattlog > 0 ? ld_dattlog : N);
+    if (N <= 128)
+        APTAI_LAUNCH(xattn_softmax_bwd_wide_kernel<2>, grid, block, 0, (hipStream_t)stream, att, att_log, d_att, d_attlog, ld, d_raw,
+                     (long)rows, (int)N);
+    else if (N <= 192)
+        APTAI_LAUNCH(xattn_softmax_bwd_wide_kernel<3>, grid, block, 0, (hipStream_t)stream, att, att_log, d_att, d_attlog, ld, d_raw,
+                     (long)rows, (int)N);
+    else
+        APTAI_LAUNCH(xattn_softmax_bwd_wide_kernel<4>, grid, block, 0, (hipStream_t)stream, att, att_log, d_att, d_attlog, ld, d_raw,
+                     (long)rows, (int)N);
+    APTAI_CHECK_LAUNCH("xattn_softmax_bwd_wide_kernel");
     return APTAI_OK;
 }
 

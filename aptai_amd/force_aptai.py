@@ -1,6 +1,7 @@
 """``Force_APTAI`` — drop-in for models/force_aptai.py:19-323 on MI355X: frozen ``Wav2Vec2_PR`` encoder (inference
 only, models/w2v2_pr.py:124-127) -> cross-attention forced aligner + BiLSTM regression.  Same constructor
-``(pr_model_path, device, vocab)``, ``forward(epoch, **batch)`` dict keys, helpers and state-dict keys.
+``(pr_model_path, device, vocab)``, ``forward(epoch, **batch)`` dict keys, helpers and state-dict keys.  ``max_phn_seq_len``
+(keyword, default 60 as in the reference, up to 255) is the number of phoneme slots per utterance.
 
 Differences from the shipped reference, all forced by defects recorded in SURVEY.md §0:
  * batch > 1 works (the reference's ``RNN.forward`` raises NameError at models/modules.py:207; intent followed);
@@ -25,7 +26,19 @@ from .modules import CrossAttention, ForwardSumLoss, LowPassFilterLayer, Positio
 from .w2v2_pr import Wav2Vec2_PR
 from .wav2vec2 import _seed
 
-_NPHN = 60
+_NPHN = 60                              # the reference's max_phn_seq_len (models/force_aptai.py:36): the default slot count
+MAX_PHN_SLOTS = ops.XATTN_MAX_SLOTS     # 255: what the wide softmax pair and the CTC kernels (256 classes, 511 states) hold
+
+
+def labels_to_slots(labels, cap):
+    """The phoneme slots of `Force_APTAI.transcript = "labels"`: `labels` int [B][L], padded with negative values (-100) ->
+    (ids int32 [B][cap], zero where the label is padding, padded or cut to `cap` slots; lens int32 [B], the count of labels >= 0
+    BEFORE the cut, so that a transcript that does not fit still shows).  Pure tensor arithmetic on the labels' device."""
+    valid = labels >= 0
+    ids = torch.where(valid, labels, torch.zeros_like(labels)).to(torch.int32)
+    L = ids.shape[1]
+    ids = torch.nn.functional.pad(ids, (0, cap - L)) if L < cap else ids[:, :cap]
+    return ids.contiguous(), valid.sum(dim=1).to(torch.int32)
 
 
 def force_heads_fwd(ac, st, P):
@@ -37,20 +50,21 @@ def force_heads_fwd(ac, st, P):
     g = st.g
     B, Tp, T, M, H = g.B, g.Tp, g.T, g.M, ac.shape[1]
     dev = ac.device
+    N = st.nphn                                        # phoneme slots per utterance (Force_APTAI.max_phn_seq_len, 60 by default)
+    ld = ops.fs_row_pitch(N)                           # floats per forward-sum row: 64 up to 63 slots, 256 at 255
     s = SimpleNamespace()
-    s.phn = ops.embed_pe_fwd(st.ids, emb_w, st.pe, _NPHN, st.p_hid, _seed(st.seed, 1))                    # [B*60][128]
+    s.phn = ops.embed_pe_fwd(st.ids, emb_w, st.pe, N, st.p_hid, _seed(st.seed, 1))                        # [B*N][128]
     fh = ops.linear_f32(ac, fl_w, fl_b, rows=M)                                                           # [M][128]
     s.fhd = ops.dropout_f32(fh, st.p_hid, _seed(st.seed, 2))
     s.cat = torch.empty((M, 256), device=dev, dtype=torch.float32)
     q = s.cat[:, 128:]
     ops.linear_f32(s.fhd, q_w, q_b, out=q, ldc=256)
-    s.k = ops.linear_f32(s.phn, k_w, k_b)                                                                  # [B*60][128]
-    raw = ops.sgemm(q, 256, 1, s.k, 1, 128, Tp, _NPHN, 128, batch=B, bsa=Tp * 256, bsb=_NPHN * 128, bsc=Tp * _NPHN)
+    s.k = ops.linear_f32(s.phn, k_w, k_b)                                                                  # [B*N][128]
+    raw = ops.sgemm(q, 256, 1, s.k, 1, 128, Tp, N, 128, batch=B, bsa=Tp * 256, bsb=N * 128, bsc=Tp * N)
     # forward-sum (CTC) input rows [blank = -1 | att_log | 0], written by the same kernel
-    s.pad = torch.empty((M, 64), device=dev, dtype=torch.float32)
-    s.energy, s.att, s.att_log, s.align = ops.xattn_softmax_fwd(raw, st.ids, B, Tp, _NPHN, fs_rows=s.pad)
-    ops.sgemm(s.att, _NPHN, 1, s.k, 128, 1, Tp, 128, _NPHN, out=s.cat, ldc=256, batch=B, bsa=Tp * _NPHN, bsb=_NPHN * 128,
-              bsc=Tp * 256)
+    s.pad = torch.empty((M, ld), device=dev, dtype=torch.float32)
+    s.energy, s.att, s.att_log, s.align = ops.xattn_softmax_fwd(raw, st.ids, B, Tp, N, fs_rows=s.pad)
+    ops.sgemm(s.att, N, 1, s.k, 128, 1, Tp, 128, N, out=s.cat, ldc=256, batch=B, bsa=Tp * N, bsb=N * 128, bsc=Tp * 256)
     s.att_out, s.lm, s.lr = ops.layernorm_f32_fwd(s.cat, ln_w, ln_b)
     # rows in the LSTM kernels' gate-interleaved order (csrc/lstm.hip: column dir * 1024 + unit * 4 + gate of xproj / gates / dgates)
     perm = ops.lstm_gate_perm(dev)[0]
@@ -69,7 +83,7 @@ def force_heads_fwd(ac, st, P):
     s.dummy_phn = torch.zeros((B, T), device=dev, dtype=torch.int64)
     s.sc, _ = ops.aptai_loss_fwd(s.tvs, st.tv_tgt, s.dummy_logits, 1, Tp, s.dummy_phn, B, T, n_tv, 1, 1.0, 0.0, want_pred=False)
     # forward-sum (CTC) alignment loss on [blank=-1 | att_log]
-    s.fs_loss, s.nll, _, s.alpha = ops.ctc_fwd(s.pad, 64, Tp, st.fs_targets, st.frame_lens, st.text_lens, B, T, _NPHN + 1,
+    s.fs_loss, s.nll, _, s.alpha = ops.ctc_fwd(s.pad, ld, Tp, st.fs_targets, st.frame_lens, st.text_lens, B, T, N + 1,
                                                blank=0, reduction="mean", zero_infinity=True, vocab_sizes_i32=st.vocab_sizes,
                                                want_log_probs=False)
     tv_loss = s.sc[1].clone()
@@ -78,12 +92,12 @@ def force_heads_fwd(ac, st, P):
     align = s.align
     if getattr(st, "readout", "argmax") == "monotonic":
         # Viterbi read-out of the trellis the forward-sum loss trains (topology 1: every phoneme owns >= 1 frame, no jumps back):
-        # the att_log rows sit at column 1 of the 64-float forward-sum rows.  More phonemes than frames -> the argmax indices stay.
-        ft, _, score, _ = ops.ctc_viterbi(s.pad[:, 1:], 64, Tp, st.mono_targets, st.frame_lens, st.text_lens, B, T, _NPHN,
+        # the att_log rows sit at column 1 of the forward-sum rows.  More phonemes than frames -> the argmax indices stay.
+        ft, _, score, _ = ops.ctc_viterbi(s.pad[:, 1:], ld, Tp, st.mono_targets, st.frame_lens, st.text_lens, B, T, N,
                                           topology="monotonic", vocab_sizes_i32=st.text_lens, want_token_score=False)
         align = s.align.clone()
         align[:, :T] = torch.where((ft >= 0) & torch.isfinite(score)[:, None], ft.long(), s.align[:, :T])
-    frame_phns = ops.gather_alignment(st.ids, align, st.frame_lens, B, Tp, _NPHN)
+    frame_phns = ops.gather_alignment(st.ids, align, st.frame_lens, B, Tp, N)
     return (loss, tv_loss, align_loss, s.tvs, frame_phns, s.att_log, s.att_out, s.hout, align), s
 
 
@@ -95,6 +109,11 @@ def force_heads_bwd(s, st, P, ac, gloss=None):
     B, Tp, T, M, H = g.B, g.Tp, g.T, g.M, ac.shape[1]
     dev = ac.device
     n_tv = l3_w.shape[0]
+    N = st.nphn
+    ld = ops.fs_row_pitch(N)
+    if B * N > 8192:
+        raise ValueError(f"Force_APTAI backward: batch {B} x max_phn_seq_len {N} = {B * N} phoneme rows, the embedding gradient "
+                         "kernel (aptai_embed_bwd) takes 8192 at most")
     gl = torch.ones(1, device=ac.device, dtype=torch.float32) if gloss is None else gloss.float().reshape(1)
     # ---- TV branch
     norm = getattr(st, "norm_scalars", None)             # data parallel: global valid TV count / world (dp.GlobalLossNorm)
@@ -123,23 +142,22 @@ def force_heads_bwd(s, st, P, ac, gloss=None):
     dwhh0, dwhh1 = dwhh0[inv[:1024]], dwhh1[inv[:1024]]
     dcat, dln_w, dln_b = ops.layernorm_f32_bwd(datt_out, s.cat, s.lm, s.lr, ln_w)
     # ---- cross attention
-    d_att = ops.sgemm(dcat, 256, 1, s.k, 1, 128, Tp, _NPHN, 128, batch=B, bsa=Tp * 256, bsb=_NPHN * 128, bsc=Tp * _NPHN)
-    dk = ops.sgemm(s.att, 1, _NPHN, dcat, 256, 1, _NPHN, 128, Tp, batch=B, bsa=Tp * _NPHN, bsb=Tp * 256, bsc=_NPHN * 128)
-    dpad = ops.ctc_bwd(s.pad, 64, Tp, st.fs_targets, st.frame_lens, st.text_lens, B, T, _NPHN + 1, s.alpha, s.nll,
+    d_att = ops.sgemm(dcat, 256, 1, s.k, 1, 128, Tp, N, 128, batch=B, bsa=Tp * 256, bsb=N * 128, bsc=Tp * N)
+    dk = ops.sgemm(s.att, 1, N, dcat, 256, 1, N, 128, Tp, batch=B, bsa=Tp * N, bsb=Tp * 256, bsc=N * 128)
+    dpad = ops.ctc_bwd(s.pad, ld, Tp, st.fs_targets, st.frame_lens, st.text_lens, B, T, N + 1, s.alpha, s.nll,
                        (0.6 * gl).contiguous(), blank=0, reduction="mean", zero_infinity=True, vocab_sizes_i32=st.vocab_sizes,
-                       ldd=64, out_dtype=torch.float32)
-    d_raw = ops.xattn_softmax_bwd(s.att, s.att_log, d_att, dpad[:, 1:], ld_dattlog=64)     # columns 1..60 of the 64-float rows, in place
+                       ldd=ld, out_dtype=torch.float32)
+    d_raw = ops.xattn_softmax_bwd(s.att, s.att_log, d_att, dpad[:, 1:], ld_dattlog=ld)     # columns 1..N of the forward-sum rows, in place
     dq = dcat[:, 128:].contiguous()
-    ops.sgemm(d_raw, _NPHN, 1, s.k, 128, 1, Tp, 128, _NPHN, out=dq, ldc=128, accumulate=True, batch=B, bsa=Tp * _NPHN,
-              bsb=_NPHN * 128, bsc=Tp * 128)
-    ops.sgemm(d_raw, 1, _NPHN, s.cat[:, 128:], 256, 1, _NPHN, 128, Tp, out=dk, ldc=128, accumulate=True, batch=B,
-              bsa=Tp * _NPHN, bsb=Tp * 256, bsc=_NPHN * 128)
+    ops.sgemm(d_raw, N, 1, s.k, 128, 1, Tp, 128, N, out=dq, ldc=128, accumulate=True, batch=B, bsa=Tp * N, bsb=N * 128, bsc=Tp * 128)
+    ops.sgemm(d_raw, 1, N, s.cat[:, 128:], 256, 1, N, 128, Tp, out=dk, ldc=128, accumulate=True, batch=B, bsa=Tp * N, bsb=Tp * 256,
+              bsc=N * 128)
     dq_w = ops.sgemm(dq, 1, 128, s.fhd, 128, 1, 128, 128, M)
     dq_b = ops.colsum_f32(dq, M, 128)
     dfhd = ops.sgemm(dq, 128, 1, q_w, 128, 1, M, 128, 128)
-    dk_w = ops.sgemm(dk, 1, 128, s.phn, 128, 1, 128, 128, B * _NPHN)
-    dk_b = ops.colsum_f32(dk, B * _NPHN, 128)
-    dphn = ops.sgemm(dk, 128, 1, k_w, 128, 1, B * _NPHN, 128, 128)
+    dk_w = ops.sgemm(dk, 1, 128, s.phn, 128, 1, 128, 128, B * N)
+    dk_b = ops.colsum_f32(dk, B * N, 128)
+    dphn = ops.sgemm(dk, 128, 1, k_w, 128, 1, B * N, 128, 128)
     demb = ops.embed_bwd(st.ids, dphn, emb_w.shape[0], st.p_hid, _seed(st.seed, 1))
     dfh = ops.dropout_f32(dfhd, st.p_hid, _seed(st.seed, 2))
     dfl_wT = ops.sgemm(ac, 1, H, dfh, 128, 1, H, 128, M)                                                    # [H][128]
@@ -166,16 +184,20 @@ class _ForceHeadsFn(torch.autograd.Function):
 
 
 class Force_APTAI(nn.Module):
-    def __init__(self, pr_model_path, device, vocab):
+    def __init__(self, pr_model_path, device, vocab, max_phn_seq_len=_NPHN):
         super().__init__()
         assert os.path.exists(pr_model_path)
+        # phoneme slots per utterance; a transcript must stay BELOW it (models/force_aptai.py:111), so 255 slots take 254 phonemes
+        if isinstance(max_phn_seq_len, bool) or not isinstance(max_phn_seq_len, (int, np.integer)) \
+                or not 2 <= int(max_phn_seq_len) <= MAX_PHN_SLOTS:
+            raise ValueError(f"Force_APTAI: max_phn_seq_len must be an integer in 2..{MAX_PHN_SLOTS}, not {max_phn_seq_len!r}")
         self.vocab = vocab
         self.device = device
         self.i = 0
         self.dp_loss_norm = None       # aptai_amd.dp.GlobalLossNorm under data parallelism
         self.hidden_drop = 0.2
         self.rnn_drop = 0.1
-        self.max_phn_seq_len = _NPHN
+        self.max_phn_seq_len = int(max_phn_seq_len)
         self.frame_hidden_dim = 128
         self.phn_hidden_dim = 128
         self.att_hidden_dim = 128
@@ -195,7 +217,7 @@ class Force_APTAI(nn.Module):
         self.frame_lin = nn.Linear(H, self.frame_hidden_dim)
         self.frame_drop = nn.Dropout(self.hidden_drop)
         self.phn_emb_layer = nn.Embedding(len(self.vocab), self.phn_hidden_dim, padding_idx=0)
-        self.pe_phn = PositionalEncoding(self.phn_hidden_dim, max_len=_NPHN, dropout=self.hidden_drop)
+        self.pe_phn = PositionalEncoding(self.phn_hidden_dim, max_len=self.max_phn_seq_len, dropout=self.hidden_drop)
         self.rnn = RNN(self.rnn_in_dim, 9, self.rnn_drop)
         self.tv_lowpass = LowPassFilterLayer(self.device, 10, 49, 9)
         for param in self.w2v2_pr.parameters():
@@ -213,14 +235,30 @@ class Force_APTAI(nn.Module):
     # read-out that belongs to the forward-sum loss; aptai_ctc_viterbi topology 1).  Losses, tvs_pred and gradients do not depend on it.
     alignment_readout = "argmax"
 
+    # where the phoneme sequence comes from: "decoded" (the reference: the frozen recogniser's best path) or "labels" (opt-in: the
+    # batch's `phoneme_labels`, the known transcript - labels_to_slots; no decode error can reach the aligner).  get_alignment and
+    # get_faptai_output take a waveform alone and always decode.
+    transcript = "decoded"
+
+    def _transcript(self) -> str:
+        if self.transcript not in ("decoded", "labels"):
+            raise ValueError(f"Force_APTAI.transcript must be 'decoded' or 'labels', not {self.transcript!r}")
+        return self.transcript
+
+    def _too_long(self, n) -> str:
+        return ('Need longer max phoneme sequence length.'
+                f' ({n} phonemes do not fit max_phn_seq_len={self.max_phn_seq_len}: a transcript must be shorter than it;'
+                f' Force_APTAI(..., max_phn_seq_len=) takes up to {MAX_PHN_SLOTS})')
+
     def _readout(self) -> str:
         if self.alignment_readout not in ("argmax", "monotonic"):
             raise ValueError(f"Force_APTAI.alignment_readout must be 'argmax' or 'monotonic', not {self.alignment_readout!r}")
         return self.alignment_readout
 
     # ------------------------------------------------------------------ shared body
-    def _encode(self, audio_inputs, audio_lengths, phn_pred_list=None):
-        """Frozen recogniser (inference) + device best-path decode on the CURRENT stream: everything the heads read from it."""
+    def _encode(self, audio_inputs, audio_lengths, phn_pred_list=None, labels=None):
+        """Frozen recogniser (inference) + device best-path decode on the CURRENT stream: everything the heads read from it.
+        `labels` (transcript = "labels"): the phoneme slots come from them and nothing is decoded."""
         pr = self.w2v2_pr
         pr.eval()                                                      # models/w2v2_pr.py:125: the recogniser always runs in eval mode
         with torch.no_grad():
@@ -228,19 +266,28 @@ class Force_APTAI(nn.Module):
             out, _ = pr._logits_eval(audio_inputs, lens1d[:, None])
             dev = out._flat_last.device
             frame_lens = pr.wav2vec2._get_feat_extract_output_lengths(lens1d.to(dev)).to(torch.int32).contiguous()
-            if phn_pred_list is None:
-                ids, nlen = pr._decode_device(out, self.max_phn_seq_len)      # int32 [B][60] zero-padded, int32 [B]
+            nlen_full = None
+            if phn_pred_list is None and labels is not None:
+                ids, nlen, nlen_full = self._label_slots(labels, dev)
+            elif phn_pred_list is None:
+                ids, nlen = pr._decode_device(out, self.max_phn_seq_len)      # int32 [B][slots] zero-padded, int32 [B]
             else:
                 padded = []
                 for lst in phn_pred_list:
-                    assert len(lst) < self.max_phn_seq_len, 'Need longer max phoneme sequence length.'
+                    assert len(lst) < self.max_phn_seq_len, self._too_long(len(lst))
                     padded.append(np.pad(np.asarray(lst, dtype=np.int64), (0, self.max_phn_seq_len - len(lst)), mode='constant'))
                 ids = torch.tensor(np.array(padded), dtype=torch.int32, device=dev)
                 nlen = torch.tensor([len(l) for l in phn_pred_list], dtype=torch.int32, device=dev)
         # with the fp32 residual stream the heads read the UNROUNDED last hidden state (the fp32 GEMM takes either dtype)
         ac = getattr(out, "_flat_last_f32", None)
         return SimpleNamespace(g=out._geom, ac=ac if ac is not None else out._flat_last, ids=ids, nlen=nlen, frame_lens=frame_lens,
-                               step=pr.wav2vec2._step)
+                               step=pr.wav2vec2._step, nlen_full=nlen_full)
+
+    def _label_slots(self, labels, dev):
+        """(ids, lengths the kernels see, label counts the host checks) of transcript = "labels".  The kernels get the count cut to
+        slots - 1, so a transcript that is too long cannot send them past a row; the uncut count is what trips the assertion."""
+        ids, n = labels_to_slots(labels.to(dev), self.max_phn_seq_len)
+        return ids, n.clamp(max=self.max_phn_seq_len - 1), n
 
     def prefetch(self, audio_inputs, audio_lengths):
         """Run the frozen recogniser for a batch on a side stream NOW; the next forward / _run called with these same tensors
@@ -322,7 +369,8 @@ class Force_APTAI(nn.Module):
         consts = self._consts(g.B, dev)
         # models/modules.py:209-212: the batch-1 branch runs the LSTM unpacked over ALL frames
         rnn_lens = consts["full_T"](g.T) if g.B == 1 else frame_lens
-        st = SimpleNamespace(g=g, ids=ids, pe=self.pe_phn.pe.reshape(_NPHN, -1).contiguous(), taps=self.tv_lowpass.taps(),
+        st = SimpleNamespace(g=g, ids=ids, nphn=self.max_phn_seq_len, pe=self.pe_phn.pe.reshape(self.max_phn_seq_len, -1).contiguous(),
+                             taps=self.tv_lowpass.taps(),
                              p_hid=self.hidden_drop if tr else 0.0, p_rnn=self.rnn_drop if tr else 0.0,
                              seed=_seed(pr.wav2vec2.base_seed, step, 4242),
                              tv_tgt=tv_targets.contiguous(), fs_targets=consts["fs_targets"], frame_lens=frame_lens, rnn_lens=rnn_lens,
@@ -340,14 +388,17 @@ class Force_APTAI(nn.Module):
              self.rnn.linear[0].bias, self.rnn.linear[3].weight, self.rnn.linear[3].bias)
         return st, P
 
-    def _run(self, audio_inputs, audio_lengths, tv_targets=None, phn_pred_list=None, _ac_override=None, _prefetch_next=None):
+    def _run(self, audio_inputs, audio_lengths, tv_targets=None, phn_pred_list=None, _ac_override=None, _prefetch_next=None,
+             labels=None):
         """Encoder (inference) -> decode -> heads.  Nothing in here synchronises host and device: the best-path decode, the
         phoneme slots, every length vector and the alignment read-out stay on the device; `_lists` makes the Python lists the
         reference returns with one round of transfers at the very end."""
         pr = self.w2v2_pr
         enc = self._take_prefetched(audio_inputs, audio_lengths) if phn_pred_list is None else None
         if enc is None:
-            enc = self._encode(audio_inputs, audio_lengths, phn_pred_list)
+            enc = self._encode(audio_inputs, audio_lengths, phn_pred_list, labels)
+        elif labels is not None:                                       # a prefetched pass decoded: the known transcript replaces it
+            enc.ids, enc.nlen, enc.nlen_full = self._label_slots(labels, enc.ids.device)
         if _prefetch_next is not None:                                 # the NEXT batch's encoder pass goes out before this batch's heads
             self.prefetch(*_prefetch_next)
         g, ids, nlen, frame_lens = enc.g, enc.ids, enc.nlen, enc.frame_lens
@@ -355,11 +406,13 @@ class Force_APTAI(nn.Module):
         ac = enc.ac if _ac_override is None else _ac_override          # test hook: heads on given embeddings
         st, P = self._heads_state(g, ids, nlen, frame_lens, tv_targets, enc.step)
         res = _ForceHeadsFn.apply(ac, st, *P)
-        return res, g, (ids, nlen, frame_lens, phn_pred_list)
+        nlen_full = getattr(enc, "nlen_full", None)
+        return res, g, (ids, nlen if nlen_full is None else nlen_full, frame_lens, phn_pred_list)
 
     def _consts(self, B, dev):
-        """Batch-size dependent constants (forward-sum targets 1..60, the all-frames length of the batch-1 branch)."""
-        key = (B, str(dev))
+        """Batch-size dependent constants (forward-sum targets 1..slots, the all-frames length of the batch-1 branch)."""
+        N = self.max_phn_seq_len
+        key = (B, str(dev), N)
         c = getattr(self, "_const_cache", {}).get(key)
         if c is None:
             full = {}
@@ -368,8 +421,8 @@ class Force_APTAI(nn.Module):
                 if T not in full:
                     full[T] = torch.full((B,), T, dtype=torch.int32, device=dev)
                 return full[T]
-            c = {"fs_targets": torch.arange(1, _NPHN + 1, dtype=torch.int32, device=dev)[None, :].repeat(B, 1).contiguous(),
-                 "mono_targets": torch.arange(_NPHN, dtype=torch.int32, device=dev)[None, :].repeat(B, 1).contiguous(),
+            c = {"fs_targets": torch.arange(1, N + 1, dtype=torch.int32, device=dev)[None, :].repeat(B, 1).contiguous(),
+                 "mono_targets": torch.arange(N, dtype=torch.int32, device=dev)[None, :].repeat(B, 1).contiguous(),
                  "full_T": full_T}
             self._const_cache = dict(getattr(self, "_const_cache", {}))
             self._const_cache[key] = c
@@ -389,8 +442,8 @@ class Force_APTAI(nn.Module):
         ops.lstm_check(host[2 * B:], ids.device)
         table = ids.cpu().numpy()
         if given is None:
-            # models/force_aptai.py:111 (checked once the lengths are on the host; the device decode filled 60 slots at most)
-            assert all(v < self.max_phn_seq_len for v in n), 'Need longer max phoneme sequence length.'
+            # models/force_aptai.py:111 (checked once the lengths are on the host; the device decode filled the slots at most)
+            assert all(v < self.max_phn_seq_len for v in n), self._too_long(max(n))
             given = [table[b, :n[b]].astype(np.int64) for b in range(len(n))]
         return given, fl, n, table
 
@@ -399,7 +452,8 @@ class Force_APTAI(nn.Module):
         """`_prefetch_next = (audio_inputs, audio_lengths)` of the batch the NEXT call will receive (the same tensor objects)
         starts its frozen-encoder pass on a side stream beside this call's heads (see prefetch)."""
         tv_targets = torch.stack([LA, LP, JA, TTCL, TTCD, TMCL, TMCD, TBCL, TBCD], dim=-1).float()
-        res, g, dec = self._run(audio_inputs, audio_lengths, tv_targets, _phn_pred_list, _ac_override, _prefetch_next)
+        labels = phoneme_labels if (self._transcript() == "labels" and _phn_pred_list is None) else None
+        res, g, dec = self._run(audio_inputs, audio_lengths, tv_targets, _phn_pred_list, _ac_override, _prefetch_next, labels)
         loss, tv_loss, align_loss, tvs, frame_phns = res[:5]
         if _device_outputs:
             # private route of the device-resident evaluation (train_force_aptai._device_eval): the tensors `_run` already holds,
@@ -413,11 +467,20 @@ class Force_APTAI(nn.Module):
         return {'loss': loss, 'tv_loss': tv_loss, 'align_loss': align_loss, 'tvs_pred': tvs,
                 'pred_frame_phns': pred_frame_phns, 'pred_ctc_phn_seq': phn_pred_list}
 
-    def load_state_dict(self, *args, **kwargs):
+    def load_state_dict(self, state_dict, *args, **kwargs):
         # the captured encoder passes of prefetch() hold the addresses of the recogniser's bf16 weight copies, which are rebuilt
         # when the parameters change: drop the graphs (they are re-captured on the next prefetches)
         self._enc_graphs, self._enc_seen, self._prefetched = {}, {}, None
-        return super().load_state_dict(*args, **kwargs)
+        # `pe_phn.pe` is a pure function of (max_phn_seq_len, width) whose rows do not depend on the row count: a checkpoint written
+        # at another max_phn_seq_len loads, and this module keeps its own table
+        pe, own = state_dict.get("pe_phn.pe"), self.pe_phn.pe
+        if pe is not None and pe.shape != own.shape and pe.shape[1:] == own.shape[1:]:
+            meta = getattr(state_dict, "_metadata", None)
+            state_dict = state_dict.copy()
+            state_dict["pe_phn.pe"] = own
+            if meta is not None:
+                state_dict._metadata = meta
+        return super().load_state_dict(state_dict, *args, **kwargs)
 
     def set_encoder_precision(self, precision: str = "bf16"):
         """"bf16_f32res" (default here): bf16 GEMMs, fp32 residual stream; "bf16": all-bf16 stream; "mxfp8": the frozen recogniser's
@@ -427,7 +490,10 @@ class Force_APTAI(nn.Module):
         return self
 
     def get_config(self):
-        return {'pr_model_path': self.pr_model_path, 'w2v2_pr_cfg': self.w2v2_pr_cfg, 'device': self.device, 'vocab': self.vocab}
+        cfg = {'pr_model_path': self.pr_model_path, 'w2v2_pr_cfg': self.w2v2_pr_cfg, 'device': self.device, 'vocab': self.vocab}
+        if self.max_phn_seq_len != _NPHN:                              # default-cap pickles stay what they were
+            cfg['max_phn_seq_len'] = self.max_phn_seq_len
+        return cfg
 
     def _wav(self, wav):
         device = next(self.parameters()).device
@@ -443,7 +509,7 @@ class Force_APTAI(nn.Module):
             wav_input, wav_len = self._wav(wav)
             res, g, dec = self._run(wav_input, wav_len.reshape(-1))
             _, frame_seq_lens, phn_seq_lens, _ = self._lists(dec)
-            att = res[5].view(g.B, g.Tp, _NPHN)[0]
+            att = res[5].view(g.B, g.Tp, self.max_phn_seq_len)[0]
             return {'alignment': att[0:frame_seq_lens[0], 0:phn_seq_lens[0]].permute(1, 0).cpu().numpy()}
 
     def get_faptai_output(self, wav):

@@ -271,12 +271,13 @@ class _FwdSumFn(torch.autograd.Function):
     def forward(ctx, att, text_lens_i32, mel_lens_i32, blank_logprob):
         B, _, T, N = att.shape
         dev = att.device
-        rows = torch.zeros((B * T, 64), device=dev, dtype=torch.float32)
+        ld = ops.fs_row_pitch(N)                               # [blank | att | zeros] at the pitch the CTC kernels read the rows with
+        rows = torch.zeros((B * T, ld), device=dev, dtype=torch.float32)
         rows[:, 0] = blank_logprob
         rows[:, 1:1 + N] = att.reshape(B * T, N)
         targets = torch.arange(1, N + 1, dtype=torch.int32, device=dev)[None, :].repeat(B, 1).contiguous()
         vs = (text_lens_i32 + 1).contiguous()
-        loss, nll, _, ws = ops.ctc_fwd(rows, 64, T, targets, mel_lens_i32, text_lens_i32, B, T, N + 1, blank=0, reduction="mean",
+        loss, nll, _, ws = ops.ctc_fwd(rows, ld, T, targets, mel_lens_i32, text_lens_i32, B, T, N + 1, blank=0, reduction="mean",
                                        zero_infinity=True, vocab_sizes_i32=vs, want_log_probs=False)
         ctx.saved = (rows, targets, mel_lens_i32, text_lens_i32, vs, ws, nll, (B, T, N))
         return loss.reshape(())
@@ -284,8 +285,9 @@ class _FwdSumFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         rows, targets, mel, txt, vs, ws, nll, (B, T, N) = ctx.saved
-        d = ops.ctc_bwd(rows, 64, T, targets, mel, txt, B, T, N + 1, ws, nll, g.float().reshape(1).contiguous(), blank=0, reduction="mean",
-                        zero_infinity=True, vocab_sizes_i32=vs, ldd=64, out_dtype=torch.float32)
+        ld = rows.shape[1]
+        d = ops.ctc_bwd(rows, ld, T, targets, mel, txt, B, T, N + 1, ws, nll, g.float().reshape(1).contiguous(), blank=0, reduction="mean",
+                        zero_infinity=True, vocab_sizes_i32=vs, ldd=ld, out_dtype=torch.float32)
         return d[:, 1:1 + N].reshape(B, 1, T, N), None, None, None
 
 
@@ -300,8 +302,8 @@ class ForwardSumLoss(nn.Module):
     def forward(self, attn_logprob, text_lens, mel_lens):
         """attn_logprob (B,1,T,N) log-attention, text_lens / mel_lens per-utterance phoneme / frame counts -> scalar loss."""
         dev = attn_logprob.device
-        if attn_logprob.shape[-1] > 63:
-            raise ValueError("ForwardSumLoss kernels hold at most 63 phoneme slots")
+        if attn_logprob.shape[-1] > ops.XATTN_MAX_SLOTS:
+            raise ValueError(f"ForwardSumLoss kernels hold at most {ops.XATTN_MAX_SLOTS} phoneme slots")
         tl = torch.as_tensor(text_lens, dtype=torch.int32).to(dev).contiguous()
         ml = torch.as_tensor(mel_lens, dtype=torch.int32).to(dev).contiguous()
         return _FwdSumFn.apply(attn_logprob.float(), tl, ml, float(self.blank_logprob))

@@ -1080,22 +1080,46 @@ def embed_bwd(ids_i32, dout, vocab, p, seed):
     return demb
 
 
+XATTN_MAX_SLOTS = 255                  # the wide softmax pair and the CTC kernels behind the forward-sum loss (MAXV = 256 classes)
+
+
+def fs_row_pitch(N: int) -> int:
+    """Floats per forward-sum row [-1 | att_log[0..N) | zeros]: round_up(N + 1, 64)."""
+    return (int(N) + 64) // 64 * 64
+
+
 def xattn_softmax_fwd(raw, ids_i32, B, T, N, fs_rows=None):
-    """fs_rows (optional [B*T][64] fp32): also writes the forward-sum CTC input rows [-1 | att_log | 0]."""
+    """fs_rows (optional [B*T][fs_row_pitch(N)] fp32, or True to have it allocated and returned as a fifth value): also writes the
+    forward-sum CTC input rows [-1 | att_log | 0].  Up to 63 slots (64 without rows) run the one-slot-per-lane kernel, up to 255
+    the wide one."""
     dev = raw.device
+    if not 0 < N <= XATTN_MAX_SLOTS:
+        raise _lib.AptaiHipError(f"xattn_softmax_fwd: 1..{XATTN_MAX_SLOTS} phoneme slots, got {N}")
+    ld = fs_row_pitch(N)
+    made = fs_rows is True
+    if made:
+        fs_rows = torch.empty((B * T, ld), device=dev, dtype=torch.float32)
+    elif fs_rows is not None and (fs_rows.dtype != torch.float32 or not fs_rows.is_contiguous() or fs_rows.dim() != 2
+                                  or fs_rows.shape[0] < B * T or fs_rows.shape[1] != ld):
+        raise _lib.AptaiHipError(f"xattn_softmax_fwd: fs_rows must be contiguous fp32 [{B * T}][{ld}] for {N} slots, "
+                                 f"got {tuple(fs_rows.shape)} {fs_rows.dtype}")
     energy, att, att_log = (torch.empty((B * T, N), device=dev, dtype=torch.float32) for _ in range(3))
     align = torch.empty((B, T), device=dev, dtype=torch.int64)
-    _lib.call("aptai_xattn_softmax_fwd", raw.data_ptr(), ids_i32.data_ptr(), energy.data_ptr(), att.data_ptr(), att_log.data_ptr(),
-              align.data_ptr(), _ptr(fs_rows), B, T, N, _stream())
-    return energy, att, att_log, align
+    if N <= 63 or (N == 64 and fs_rows is None):
+        _lib.call("aptai_xattn_softmax_fwd", raw.data_ptr(), ids_i32.data_ptr(), energy.data_ptr(), att.data_ptr(), att_log.data_ptr(),
+                  align.data_ptr(), _ptr(fs_rows), B, T, N, _stream())
+    else:
+        _lib.call("aptai_xattn_softmax_fwd_wide", raw.data_ptr(), ids_i32.data_ptr(), energy.data_ptr(), att.data_ptr(),
+                  att_log.data_ptr(), align.data_ptr(), _ptr(fs_rows), ld, B, T, N, _stream())
+    return (energy, att, att_log, align, fs_rows) if made else (energy, att, att_log, align)
 
 
 def xattn_softmax_bwd(att, att_log, d_att, d_attlog, ld_dattlog=0):
-    """d_attlog may be a strided view (e.g. columns 1..N of the 64-float forward-sum gradient rows: pass ld_dattlog=64)."""
+    """d_attlog may be a strided view (e.g. columns 1..N of the forward-sum gradient rows: pass their pitch as ld_dattlog)."""
     rows, N = att.shape
     d_raw = torch.empty_like(att)
-    _lib.call("aptai_xattn_softmax_bwd", att.data_ptr(), att_log.data_ptr(), _ptr(d_att), _ptr(d_attlog), ld_dattlog, d_raw.data_ptr(),
-              rows, N, _stream())
+    _lib.call("aptai_xattn_softmax_bwd" if N <= 64 else "aptai_xattn_softmax_bwd_wide", att.data_ptr(), att_log.data_ptr(), _ptr(d_att),
+              _ptr(d_attlog), ld_dattlog, d_raw.data_ptr(), rows, N, _stream())
     return d_raw
 
 

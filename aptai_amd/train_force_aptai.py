@@ -48,7 +48,9 @@ def collate_raw(batch):
 def load_model_optimizer(args_cfg):
     """train/train_force_aptai.py:328-368: Force_APTAI over a trained recogniser checkpoint, Adam over the parameters that
     require gradients (the heads), LambdaLR with the 10x warm-up schedule."""
-    model = Force_APTAI(args_cfg.pr_model_path, args_cfg.device, args_cfg.vocab).to(args_cfg.device)
+    model = Force_APTAI(args_cfg.pr_model_path, args_cfg.device, args_cfg.vocab,
+                        max_phn_seq_len=getattr(args_cfg, "max_phn_seq_len", 60)).to(args_cfg.device)
+    model.transcript = getattr(args_cfg, "transcript", "decoded")
     optimizer, lr_scheduler = loops.adam_and_schedule([p for p in model.parameters() if p.requires_grad], args_cfg)
     return model, optimizer, lr_scheduler
 
@@ -148,10 +150,11 @@ def default_cfg(**kw):
     vocab = {"(blank)": 0, "(...)": 1}
     vocab.update({f"p{i}": i for i in range(2, 40)})
     return loops.default_cfg(kw, batch_size=5, learning_rate=1e-5, target_metric="val_mean_rmse", exp_dir=None, vocab=vocab,
-                             pr_model_path=None)
+                             pr_model_path=None, max_phn_seq_len=60, transcript="decoded")
 
 
-def main(argv=None):
+def parse_args(argv=None):
+    """The command line of main()."""
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--pr_model_path", required=True, help="directory holding best-model-ckpt/{pytorch_model.bin, model_cfg.pkl}")
     ap.add_argument("--num_epochs", type=int, default=2)
@@ -161,10 +164,18 @@ def main(argv=None):
     ap.add_argument("--seconds", type=float, default=10.0)
     ap.add_argument("--learning_rate", type=float, default=1e-5)
     loops.add_shared_arguments(ap)
+    ap.add_argument("--max_phn_seq_len", type=int, default=60,
+                    help="phoneme slots per utterance, 2..255: a transcript must be shorter than this (the reference's constant: 60)")
+    ap.add_argument("--transcript", choices=("decoded", "labels"), default="decoded",
+                    help="what the aligner aligns to: the frozen recogniser's decode, or the batch's phoneme_labels")
     ap.add_argument("--out", default="force_aptai_ckpt")
-    a = ap.parse_args(argv)
+    return ap.parse_args(argv)
+
+
+def main(argv=None):
+    a = parse_args(argv)
     cfg = default_cfg(num_epochs=a.num_epochs, batch_size=a.batch_size, learning_rate=a.learning_rate, pr_model_path=a.pr_model_path,
-                      **loops.shared_arguments(a))
+                      max_phn_seq_len=a.max_phn_seq_len, transcript=a.transcript, **loops.shared_arguments(a))
     model, optimizer, lr_scheduler = load_model_optimizer(cfg)
     w2v = model.w2v2_pr.wav2vec2.config
     train_ds = SyntheticHPRCWithLabels(a.steps_per_epoch * a.batch_size, a.seconds, seed=1, cfg=w2v, vocab_size=len(cfg.vocab),

@@ -484,6 +484,13 @@ int aptai_xattn_softmax_fwd(const float* raw, const int32_t* phn_ids, float* ene
                             float* fs_rows, int64_t B, int64_t T, int64_t N, void* stream);
 int aptai_xattn_softmax_bwd(const float* att, const float* att_log, const float* d_att, const float* d_attlog, int64_t ld_dattlog,
                             float* d_raw, int64_t rows, int64_t N, void* stream);
+/* The same pair for 64 <= N <= 255 phoneme slots (Force_APTAI(max_phn_seq_len=...)): a lane holds slots l, l + 64, l + 128, l + 192.
+ * fs_rows has pitch ld_fs = round_up(N + 1, 64) floats (64 .. 256) with the same content, -1 | att_log[0..N) | zeros.  Among equal
+ * maxima align is the lowest slot index.  A transcript short enough for the pair above gets that pair's bits in its own columns. */
+int aptai_xattn_softmax_fwd_wide(const float* raw, const int32_t* phn_ids, float* energy, float* att, float* att_log, int64_t* align,
+                                 float* fs_rows, int64_t ld_fs, int64_t B, int64_t T, int64_t N, void* stream);
+int aptai_xattn_softmax_bwd_wide(const float* att, const float* att_log, const float* d_att, const float* d_attlog,
+                                 int64_t ld_dattlog, float* d_raw, int64_t rows, int64_t N, void* stream);
 int aptai_layernorm_f32_fwd(const float* x, const float* gamma, const float* beta, float* y, float* mean, float* rstd, int64_t rows,
                             int64_t cols, float eps, void* stream);
 int aptai_layernorm_f32_bwd(const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma, float* dx,
