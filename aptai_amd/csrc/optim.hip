@@ -221,6 +221,57 @@ __global__ __launch_bounds__(256) void scale_multi_kernel(const int64_t* __restr
     }
 }
 
+// ---------------------------------------------------------------------------------- gradient accumulation (windows of N micro-batches)
+// One micro-step of a window over the Adam job table: job y's accumulator takes this micro-step's gradient, and at the close of the
+// window the mean.  Per-call row {grad, mode}: mode 0 = no contribution in the window so far (the accumulator is neither read nor
+// written), 1 = first contribution (acc = g: an overwrite, nothing was zeroed), 2 = contributed before (acc = acc + g, or untouched
+// when grad is 0).  scale != 1 (the close): every row of mode 1 or 2 is then multiplied by it.  One __fadd_rn per element per
+// micro-step in micro-step order, one __fmul_rn at the close: the bits are those of ((g1 + g2) + ...) * scale in fp32.  The chunking
+// and thread mapping of adam_multi_kernel, every load of a thread before its first store, no atomics.
+__global__ __launch_bounds__(256) void grad_accum_kernel(const int64_t* __restrict__ table, const int64_t* __restrict__ dynt,
+                                                         const int64_t* __restrict__ accp, float scale) {
+    const long n = table[(long)blockIdx.y * 6 + 4];
+    const long base = (long)blockIdx.x * ADAM_CHUNK;
+    const float* g = (const float*)dynt[(long)blockIdx.y * 2];
+    const int64_t mode = dynt[(long)blockIdx.y * 2 + 1];
+    const bool first = mode == 1;
+    const bool scaled = scale != 1.0f;
+    if (base >= n || mode == 0 || (g == nullptr && (first || !scaled))) return;
+    float* acc = (float*)accp[blockIdx.y];
+    if ((n % 4 == 0) && (((int64_t)g | (int64_t)acc) % 16 == 0)) {
+        f32x4 aq[4], gq[4];
+#pragma unroll
+        for (int it = 0; it < 4; ++it) {
+            const long i = base + (long)(it * 256 + threadIdx.x) * 4;
+            if (i < n) {
+                if (!first) aq[it] = *(const f32x4*)(acc + i);
+                if (g) gq[it] = *(const f32x4*)(g + i);
+            }
+        }
+#pragma unroll
+        for (int it = 0; it < 4; ++it) {
+            const long i = base + (long)(it * 256 + threadIdx.x) * 4;
+            if (i >= n) break;
+            f32x4 aa;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                float x = first ? gq[it][r] : (g ? __fadd_rn(aq[it][r], gq[it][r]) : aq[it][r]);
+                if (scaled) x = __fmul_rn(x, scale);
+                aa[r] = x;
+            }
+            *(f32x4*)(acc + i) = aa;
+        }
+    } else {
+        long end = base + ADAM_CHUNK;
+        end = end < n ? end : n;
+        for (long i = base + threadIdx.x; i < end; i += 256) {
+            float x = first ? g[i] : (g ? __fadd_rn(acc[i], g[i]) : acc[i]);
+            if (scaled) x = __fmul_rn(x, scale);
+            acc[i] = x;
+        }
+    }
+}
+
 }  // namespace
 
 static int adam_launch(const char* who, const int64_t* table_dev, const int64_t* dyn_dev, int64_t njobs, int64_t max_n, float lr,
@@ -272,5 +323,15 @@ extern "C" int aptai_scale_multi(const int64_t* table_dev, const int64_t* dyn_de
     APTAI_LAUNCH(scale_multi_kernel, dim3((unsigned)ceil_div(max_n, ADAM_CHUNK), (unsigned)njobs), dim3(256), 0, (hipStream_t)stream,
                  table_dev, dyn_dev, scale_dev);
     APTAI_CHECK_LAUNCH("scale_multi_kernel");
+    return APTAI_OK;
+}
+
+extern "C" int aptai_grad_accum_multi(const int64_t* table_dev, const int64_t* dyn_dev, const int64_t* acc_dev, int64_t njobs,
+                                      int64_t max_n, float scale, void* stream) {
+    APTAI_REQUIRE(table_dev && dyn_dev && acc_dev && njobs > 0 && njobs <= 65535 && max_n > 0, "aptai_grad_accum_multi: bad arguments");
+    APTAI_REQUIRE(scale > 0.f && scale <= 3.402823466e38f, "aptai_grad_accum_multi: scale must be finite and positive (1 / micro-steps)");
+    APTAI_LAUNCH(grad_accum_kernel, dim3((unsigned)ceil_div(max_n, ADAM_CHUNK), (unsigned)njobs), dim3(256), 0, (hipStream_t)stream,
+                 table_dev, dyn_dev, acc_dev, scale);
+    APTAI_CHECK_LAUNCH("grad_accum_kernel");
     return APTAI_OK;
 }

@@ -31,7 +31,8 @@ def adam_and_schedule(params, args_cfg, publish_to=None):
     whose bf16 weight copies the step refreshes in the same pass."""
     from .optim import Adam
     optimizer = Adam(params, lr=args_cfg.learning_rate, betas=(args_cfg.adam_beta1, args_cfg.adam_beta2), eps=args_cfg.adam_epsilon,
-                     weight_decay=args_cfg.adam_weight_decay, max_grad_norm=getattr(args_cfg, "max_grad_norm", None))
+                     weight_decay=args_cfg.adam_weight_decay, max_grad_norm=getattr(args_cfg, "max_grad_norm", None),
+                     gradient_accumulation_steps=getattr(args_cfg, "gradient_accumulation_steps", 1))
     if publish_to is not None:
         optimizer.publish_to(publish_to)
     lr_scheduler = torch.optim.lr_scheduler.LambdaLR(
@@ -51,6 +52,8 @@ def default_cfg(overrides, **own):
 def add_shared_arguments(ap):
     ap.add_argument("--max_grad_norm", type=float, default=None,
                     help="clip the gradients at this global 2-norm inside the optimiser step (off by default)")
+    ap.add_argument("--gradient_accumulation_steps", type=int, default=1,
+                    help="update once per this many batches, with the mean of their gradients (accumulated inside the optimiser; off by default)")
     ap.add_argument("--source_rate", type=int, default=None,
                     help="the corpus' sampling rate: the audio is uploaded at that rate and resampled to 16 kHz on the device")
     ap.add_argument("--normalize_audio", action="store_true", help="zero-mean / unit-variance normalisation on the device")
@@ -58,7 +61,8 @@ def add_shared_arguments(ap):
 
 def shared_arguments(a) -> dict:
     """The parsed flags of add_shared_arguments as default_cfg entries."""
-    return dict(max_grad_norm=a.max_grad_norm, source_rate=a.source_rate, normalize_audio=a.normalize_audio)
+    return dict(max_grad_norm=a.max_grad_norm, gradient_accumulation_steps=a.gradient_accumulation_steps, source_rate=a.source_rate,
+                normalize_audio=a.normalize_audio)
 
 
 def save_checkpoint(model, path):
@@ -95,10 +99,14 @@ class EpochDriver:
         self.runner = None
         self.eval_target = None
         self.history = []
-        self.sum_train_loss, self.steps = 0.0, 0
+        # cfg.gradient_accumulation_steps: every optimizer.step() below is one micro-step of a window (aptai_amd.optim.Adam); the loop
+        # counts the updates, keeps the clip monitor to them and closes an unfinished window at the end of the epoch
+        self.accumulate = getattr(cfg, "gradient_accumulation_steps", 1) > 1
+        self.sum_train_loss, self.steps, self.updates = 0.0, 0, 0
 
     def eager_step(self, forward):
-        """zero_grad -> `forward()` (the loop's model call on its uploaded batch) -> backward -> optimizer.step.  Returns the outputs."""
+        """zero_grad -> `forward()` (the loop's model call on its uploaded batch) -> backward -> optimizer.step.  Returns the outputs.
+        (Under accumulation too: the window's sum lives in the optimiser, not in `.grad`.)"""
         self.optimizer.zero_grad()
         outputs = forward()
         outputs["loss"].backward()
@@ -115,9 +123,15 @@ class EpochDriver:
             self.runner = graphed.BucketedGraphedStep(self.model, self.optimizer)
         return self._trained(self.runner.step(batch))
 
-    def _trained(self, outputs):
+    def _updated(self):
+        """After an optimizer.step() or flush() that moved the parameters (every one, unless accumulation is on)."""
+        self.updates += 1
         if self.clip is not None:
             self.clip.update()
+
+    def _trained(self, outputs):
+        if getattr(self.optimizer, "last_step_updated", True):
+            self._updated()
         self.sum_train_loss += float(outputs["loss"].detach())
         self.steps += 1
         return outputs
@@ -128,6 +142,8 @@ class EpochDriver:
         recogniser's fixed number of steps per epoch; the mean train loss divides by it and the log gains `trained_batches`.
         `extra_checkpoints()`: further files, written after the best checkpoint."""
         cfg, model = self.cfg, self.model
+        if getattr(self.optimizer, "micro_step", 0) and self.optimizer.flush():        # a remainder of the epoch's last window
+            self._updated()
         self.lr_scheduler.step()
         if self.runner is not None:
             self.runner.suspend()        # the eager validation below rebuilds its weight copies; the captured buckets stay
@@ -146,10 +162,12 @@ class EpochDriver:
                          lr=self.optimizer.param_groups[0]["lr"], saved=bool(better))
         if planned_steps is not None:
             epoch_log["trained_batches"] = self.steps
+        if self.accumulate:
+            epoch_log["optimizer_updates"] = self.updates
         if self.clip is not None:
             epoch_log.update(self.clip.epoch_log())
         self.history.append(epoch_log)
-        self.sum_train_loss, self.steps = 0.0, 0
+        self.sum_train_loss, self.steps, self.updates = 0.0, 0, 0
         return epoch_log
 
     def close(self):

@@ -642,6 +642,12 @@ def scale_multi(table_ptr: int, dyn_ptr: int, njobs: int, max_n: int, scale, str
     _lib.call("aptai_scale_multi", table_ptr, dyn_ptr, njobs, max_n, scale.data_ptr(), _stream() if stream is None else stream)
 
 
+def grad_accum_multi(table_ptr: int, dyn_ptr: int, acc_ptr: int, njobs: int, max_n: int, scale: float = 1.0, stream=None) -> None:
+    """One micro-step of gradient accumulation over Adam job tables given by address (aptai_grad_accum_multi): per job acc = grad on
+    the window's first contribution, acc += grad later, then acc *= scale when scale != 1 (the close: scale = 1 / micro-steps)."""
+    _lib.call("aptai_grad_accum_multi", table_ptr, dyn_ptr, acc_ptr, njobs, max_n, float(scale), _stream() if stream is None else stream)
+
+
 def conv_weight_bf16(w: torch.Tensor) -> torch.Tensor:
     """[N][C][Kw] fp32 -> [N][Kw*C] bf16."""
     _dev(w)

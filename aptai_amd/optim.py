@@ -11,10 +11,15 @@ Global-norm gradient clipping (``torch.nn.utils.clip_grad_norm_(params, max_norm
 group with an order-fixed two-stage reduction, leaves the coefficient on the device and the Adam kernel multiplies each gradient by
 it as it reads it.  ``.grad`` is NOT modified in this form: it still holds the unclipped gradient after ``step()``.
 ``clip_grad_norm_`` below is the in-place drop-in for a loop that wants torch's two calls.
+
+Gradient accumulation (the HF Trainer's ``gradient_accumulation_steps``) lives here too: ``Adam(..., gradient_accumulation_steps=N)``
+makes every ``step()`` one micro-step of a window of N.  The first N - 1 add the gradients into fp32 accumulators the optimiser owns
+(one streaming launch, nothing else moves); the N-th multiplies them by 1/N and hands the mean to the norm and Adam kernels above.
 """
 from __future__ import annotations
 
 import math
+import operator
 from typing import Dict, Optional
 
 import torch
@@ -29,13 +34,26 @@ def _check_max_norm(max_norm) -> float:
     return max_norm
 
 
+def _check_accum_steps(steps) -> int:
+    try:
+        steps = operator.index(steps)
+    except TypeError:
+        raise ValueError(f"gradient_accumulation_steps must be an integer >= 1, got {steps!r}") from None
+    if steps < 1:
+        raise ValueError(f"gradient_accumulation_steps must be an integer >= 1, got {steps}")
+    return steps
+
+
 class Adam(torch.optim.Optimizer):
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
-                 max_grad_norm: Optional[float] = None):
+                 max_grad_norm: Optional[float] = None, gradient_accumulation_steps: int = 1):
         if lr < 0 or eps < 0 or not (0 <= betas[0] < 1) or not (0 <= betas[1] < 1) or weight_decay < 0:
             raise ValueError("invalid Adam hyper-parameters")
         # an attribute, not a param_groups key (one norm spans all groups; state_dict() stays interchangeable with torch's)
         self.max_grad_norm = max_grad_norm
+        self._accum = None                          # accumulation: accumulators, pointer tables and the open window (_accum_tables)
+        self.gradient_accumulation_steps = gradient_accumulation_steps      # an attribute as well: one window spans all groups
+        self.last_step_updated = False              # did the last step() / flush() update the parameters (False inside a window)
         super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay))
         self._copies: Dict[int, tuple] = {}         # id(param) -> (destination tensor, kind)
         self._tables: Dict[int, tuple] = {}         # group index -> (key, table tensor, max_n)
@@ -43,6 +61,7 @@ class Adam(torch.optim.Optimizer):
         self._span = None                           # clipping: one job table over every group (_span_tables)
         self._clip_result = None                    # clipping: device fp32 {total norm, coefficient, gradient elements}
         self._pending_clip = None
+        self._pending_accum = None
 
     # ------------------------------------------------------------------ global-norm clipping
     @property
@@ -66,6 +85,38 @@ class Adam(torch.optim.Optimizer):
         """0-dim device view of min(1, max_grad_norm / (norm + 1e-6)) of the last clipped step (see last_grad_norm)."""
         return None if self._clip_result is None else self._clip_result[1]
 
+    # ------------------------------------------------------------------ gradient accumulation
+    @property
+    def gradient_accumulation_steps(self) -> int:
+        """1: every step() updates.  N > 1: every step() is one micro-step of a window of N; the N-th applies the MEAN of the window's
+        gradients (a parameter without a gradient in some micro-steps counts zeros for them; one without any is skipped).  `.grad`
+        is never written.  May be reassigned only while no window is open."""
+        return self._accum_steps
+
+    @gradient_accumulation_steps.setter
+    def gradient_accumulation_steps(self, value) -> None:
+        value = _check_accum_steps(value)
+        if self.micro_step:
+            raise RuntimeError("gradient_accumulation_steps cannot change inside an open window: flush() first")
+        self._accum_steps = value
+
+    @property
+    def micro_step(self) -> int:
+        """Micro-steps the open window holds so far; 0 after an update (and always at gradient_accumulation_steps=1)."""
+        return 0 if self._accum is None else self._accum["k"]
+
+    def accumulated_grad(self, p) -> Optional[torch.Tensor]:
+        """The fp32 accumulator of `p` (a view shaped like `p`, not synchronised): the sum over the open window so far or, with no
+        window open, the mean gradient the last update applied.  None when `p` contributed nothing to that window, or when
+        nothing has been accumulated yet."""
+        acc = self._accum
+        if acc is None:
+            return None
+        row = acc["rows"].get(id(p))
+        if row is None or not (acc["seen"] if acc["k"] else acc["applied"])[row]:
+            return None
+        return acc["views"][row]
+
     # ------------------------------------------------------------------ compute copies
     def publish_to(self, model) -> "Adam":
         """Refresh the wav2vec2 layer compute copies (ops.CastPlan destinations) inside the optimiser kernel."""
@@ -79,6 +130,7 @@ class Adam(torch.optim.Optimizer):
         self._plans.append(plan)
         self._tables.clear()
         self._span = None
+        self._accum = None
         return self
 
     # ------------------------------------------------------------------ step
@@ -111,30 +163,57 @@ class Adam(torch.optim.Optimizer):
         self._tables[gi] = cached
         return cached
 
-    def _span_tables(self, ts):
-        """Clipping: ONE job table over the rows of every group (`ts`: the groups' tables in group order), so that one norm spans
+    def _span_tables(self, ts, clip: bool = True):
+        """Clipping and accumulation: ONE job table over the rows of every group (`ts`: the groups' tables in group order), so that one norm spans
         them and its summation order depends on the tables alone; per-step rows, pinned ring, partial-sum workspace and the result
-        words are allocated here, never inside a step.  The groups' Adam launches read row ranges of this table."""
+        words are allocated here, never inside a step.  The groups' Adam launches read row ranges of this table.  `clip` False (accumulation
+        without clipping): the table alone; the norm's workspace and result words follow when clipping is first asked for."""
         span = self._span
-        if span is not None and len(span["tables"]) == len(ts) and all(a is t["table"] for a, t in zip(span["tables"], ts)):
-            return span
-        devs = {t["table"].device for t in ts}
-        if len(devs) != 1:
-            raise _lib.AptaiHipError("aptai_amd.optim.Adam(max_grad_norm=...): one global norm needs every parameter group on one device")
-        dev = devs.pop()
-        offs, n = {}, 0
-        for t in ts:
-            offs[id(t)] = n
-            n += len(t["params"])
-        numels = [m for t in ts for m in t["numels"]]
-        if self._clip_result is None or self._clip_result.device != dev:
-            self._clip_result = torch.zeros(3, dtype=torch.float32, device=dev)
-        span = dict(tables=[t["table"] for t in ts], table=torch.cat([t["table"] for t in ts]).contiguous(), offs=offs, n=n,
-                    max_n=max(numels), dyn_dev=torch.zeros((n, 2), dtype=torch.int64, device=dev),
-                    partials=torch.zeros(ops.grad_norm_chunks(numels), dtype=torch.float32, device=dev),
-                    ring=[torch.zeros((n, 2), dtype=torch.int64).pin_memory() for _ in range(4)], events=[None] * 4, turn=0)
-        self._span = span
+        if span is None or len(span["tables"]) != len(ts) or not all(a is t["table"] for a, t in zip(span["tables"], ts)):
+            devs = {t["table"].device for t in ts}
+            if len(devs) != 1:
+                raise _lib.AptaiHipError("aptai_amd.optim.Adam(max_grad_norm=... / gradient_accumulation_steps=...): one global norm or "
+                                         "one window needs every parameter group on one device")
+            dev = devs.pop()
+            offs, n = {}, 0
+            for t in ts:
+                offs[id(t)] = n
+                n += len(t["params"])
+            numels = [m for t in ts for m in t["numels"]]
+            span = dict(tables=[t["table"] for t in ts], table=torch.cat([t["table"] for t in ts]).contiguous(), offs=offs, n=n,
+                        max_n=max(numels), numels=numels, dev=dev, dyn_dev=torch.zeros((n, 2), dtype=torch.int64, device=dev),
+                        partials=None, ring=[torch.zeros((n, 2), dtype=torch.int64).pin_memory() for _ in range(4)], events=[None] * 4,
+                        turn=0)
+            self._span = span
+        if clip and span["partials"] is None:
+            if self._clip_result is None or self._clip_result.device != span["dev"]:
+                self._clip_result = torch.zeros(3, dtype=torch.float32, device=span["dev"])
+            span["partials"] = torch.zeros(ops.grad_norm_chunks(span["numels"]), dtype=torch.float32, device=span["dev"])
         return span
+
+    def _accum_tables(self, span, ts):
+        """Accumulation: one fp32 accumulator per row of the span table (slices of ONE buffer, each 16-byte aligned so that the
+        accumulate and Adam kernels take their vector paths), their device pointer table, the per-call rows - plane 0 what the norm
+        and Adam launches of a closing step read {accumulator, step count}, plane 1 what the accumulate launch reads {grad, mode} -
+        and their pinned ring.  Allocated when the first window opens; a rebuilt span (publish_to, load_state_dict) discards the
+        open window with the old accumulators."""
+        acc = self._accum
+        if acc is not None and acc["span"] is span:
+            return acc
+        n, offs, total = span["n"], [], 0
+        for m in span["numels"]:
+            offs.append(total)
+            total += (m + 3) // 4 * 4
+        buf = torch.empty(total, dtype=torch.float32, device=span["dev"])
+        params = [p for t, _ in ts for p in t["params"]]
+        views = [buf[o:o + m].view(p.shape) for o, m, p in zip(offs, span["numels"], params)]
+        ptrs = [v.data_ptr() for v in views]
+        acc = dict(span=span, buf=buf, views=views, ptrs=ptrs, ptrs_dev=torch.tensor(ptrs, dtype=torch.int64).to(span["dev"]),
+                   rows={id(p): r for r, p in enumerate(params)}, dyn_dev=torch.zeros((2, n, 2), dtype=torch.int64, device=span["dev"]),
+                   ring=[torch.zeros((2, n, 2), dtype=torch.int64).pin_memory() for _ in range(4)], events=[None] * 4, turn=0,
+                   seen=[False] * n, applied=[False] * n, k=0)
+        self._accum = acc
+        return acc
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -157,6 +236,10 @@ class Adam(torch.optim.Optimizer):
         early_ids = {id(p) for p in early}
         self._pending = []
         self._pending_clip = None
+        self._pending_accum = None
+        if self._accum_steps > 1:
+            # a window's mean does not exist before its last gradient does: every row goes to finish(), `early` is ignored
+            return self._prepare_accum(stream, True)
         if self._max_grad_norm is not None:
             # the global norm does not exist before the last gradient does: every row goes to finish(), `early` is ignored
             # (launch_early() then finds nothing to do and the step is the one-launch step, bit for bit)
@@ -197,8 +280,8 @@ class Adam(torch.optim.Optimizer):
             t["events"][slot] = ev
             self._pending.append((t, group, any_late))
 
-    def _prepare_clipped(self, stream) -> None:
-        """prepare() with clipping on: the same checks and step counts, the per-step rows of ALL groups in one table, one copy."""
+    def _device_groups(self):
+        """[(table, group)] of the groups with parameters on the device, after prepare()'s checks."""
         ts = []
         for gi, group in enumerate(self.param_groups):
             if not any(p.is_cuda for p in group["params"]):
@@ -209,6 +292,67 @@ class Adam(torch.optim.Optimizer):
             if any(p.grad is not None for p in t["others"]):
                 raise _lib.AptaiHipError("aptai_amd.optim.Adam updates contiguous fp32 parameters on the MI355X only")
             ts.append((t, group))
+        return ts
+
+    def _prepare_accum(self, stream, contribute: bool) -> None:
+        """prepare() with accumulation on: one micro-step (`contribute`) or the early close of flush().  Plane 1 of the per-call rows
+        names this micro-step's gradients for the accumulate launch; a micro-step that closes the window also fills plane 0 with the
+        accumulators as gradient pointers and the step counts of the rows that contributed, which finish() hands to the usual
+        launches.  One pinned buffer, one copy."""
+        ts = self._device_groups()
+        if not ts:
+            return
+        span = self._span_tables([t for t, _ in ts], clip=self._max_grad_norm is not None)
+        acc = self._accum_tables(span, ts)
+        if not contribute and acc["k"] == 0:
+            return
+        slot = acc["turn"]
+        acc["turn"] = (slot + 1) % len(acc["ring"])
+        if acc["events"][slot] is not None:
+            acc["events"][slot].synchronize()          # the copy that last used this pinned buffer has been consumed
+        host = acc["ring"][slot].numpy()               # [2][rows of all groups][2]
+        host[:] = 0
+        seen, any_grad = acc["seen"], False
+        for t, group in ts:
+            off = span["offs"][id(t)]
+            for j, p in enumerate(t["params"]):
+                g = p.grad if contribute else None
+                if g is not None:
+                    if g.dtype != torch.float32 or not g.is_contiguous():
+                        raise _lib.AptaiHipError("aptai_amd.optim.Adam needs contiguous fp32 gradients")
+                    host[1, off + j, 0] = g.data_ptr()
+                    host[1, off + j, 1] = 2 if seen[off + j] else 1
+                    seen[off + j] = any_grad = True
+                elif seen[off + j]:
+                    host[1, off + j, 1] = 2
+        if contribute:
+            if not any_grad and acc["k"] == 0:
+                return                                 # nothing has a gradient and no window is open: nothing to do, as at N = 1
+            acc["k"] += 1
+        close = not contribute or acc["k"] >= self._accum_steps
+        scale = 1.0 / acc["k"] if close else 1.0
+        if close:
+            for t, group in ts:
+                off, any_seen = span["offs"][id(t)], False
+                for j, st in enumerate(t["states"]):
+                    if seen[off + j]:
+                        st["step"] += 1
+                        host[0, off + j, 0] = acc["ptrs"][off + j]
+                        host[0, off + j, 1] = st["step"]
+                        any_seen = True
+                if any_seen:
+                    self._pending.append((t, group, True))
+            acc["applied"], acc["seen"], acc["k"] = seen, [False] * span["n"], 0
+        acc["dyn_dev"].copy_(acc["ring"][slot], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(stream)
+        acc["events"][slot] = ev
+        # scale == 1 without a gradient (a flush() after one micro-step): the accumulators already hold the mean
+        self._pending_accum = (span, acc, scale, close, any_grad or scale != 1.0, self._max_grad_norm)
+
+    def _prepare_clipped(self, stream) -> None:
+        """prepare() with clipping on: the same checks and step counts, the per-step rows of ALL groups in one table, one copy."""
+        ts = self._device_groups()
         if not ts:
             return
         span = self._span_tables([t for t, _ in ts])
@@ -250,7 +394,7 @@ class Adam(torch.optim.Optimizer):
         """Update `params` (named in prepare(early=...)) now, on `stream`: one launch per parameter group over the row range that
         spans them (rows in between that were not named `early` carry no gradient pointer in this plane and are skipped)."""
         stream = stream or torch.cuda.current_stream()
-        if self._pending_clip is not None:
+        if self._pending_clip is not None or self._pending_accum is not None:
             return
         ids = {id(p) for p in params}
         for t, group, _ in self._pending:
@@ -262,7 +406,10 @@ class Adam(torch.optim.Optimizer):
     def finish(self, stream=None) -> None:
         """Update every parameter that has a gradient and was not named `early`."""
         stream = stream or torch.cuda.current_stream()
-        if self._pending_clip is not None:
+        self.last_step_updated = self._accum_steps == 1
+        if self._pending_accum is not None:
+            self._finish_accum(stream)
+        elif self._pending_clip is not None:
             # here, not in prepare(): every gradient is final now (and, under data parallelism, already averaged: the norm is that
             # of the averaged gradient and the same on every rank).  Two norm launches, then the groups' Adam launches read the
             # coefficient from the device on the same stream
@@ -281,7 +428,45 @@ class Adam(torch.optim.Optimizer):
                     self._launch(t, group, 0, 0, len(t["params"]), stream)
         self._pending = []
         for plan in self._plans:                    # the copies of every parameter that had a gradient are fresh now;
-            plan.optimizer_synced = True            # parameters without one did not move
+            plan.optimizer_synced = True            # parameters without one did not move (nor did any inside a window)
+
+    def _finish_accum(self, stream) -> None:
+        """finish() with accumulation on: the accumulate launch and, when the micro-step closes the window, today's launches on the
+        accumulated mean - the groups' Adam launches, behind the norm launches under clipping - over row ranges of the span table."""
+        span, acc, scale, close, launch, max_norm = self._pending_accum
+        self._pending_accum = None
+        tab, dyn = span["table"].data_ptr(), acc["dyn_dev"]
+        if launch:
+            ops.grad_accum_multi(tab, dyn[1].data_ptr(), acc["ptrs_dev"].data_ptr(), span["n"], span["max_n"], scale, stream.cuda_stream)
+        self.last_step_updated = close
+        if not close:
+            return
+        dyn = dyn[0].data_ptr()
+        if max_norm is not None:
+            coef = self._clip_result[1:2]
+            ops.grad_sqnorm_multi(tab, dyn, span["n"], span["max_n"], span["partials"], self._clip_result, max_norm, stream.cuda_stream)
+        for t, group, _ in self._pending:
+            off = span["offs"][id(t)]
+            b1, b2 = group["betas"]
+            if max_norm is not None:
+                ops.adam_multi_scaled(tab + off * 48, dyn + off * 16, len(t["params"]), t["max_n"], group["lr"], b1, b2, group["eps"],
+                                      group["weight_decay"], coef, stream.cuda_stream)
+            else:
+                _lib.call("aptai_adam_multi", tab + off * 48, dyn + off * 16, len(t["params"]), t["max_n"], float(group["lr"]), float(b1),
+                          float(b2), float(group["eps"]), float(group["weight_decay"]), stream.cuda_stream)
+
+    @torch.no_grad()
+    def flush(self) -> bool:
+        """Close the open window now: the update applies the mean over the micro-steps the window holds (a remainder at the end of an
+        epoch).  Returns whether an update happened; with no window open it launches nothing."""
+        if self.micro_step == 0:
+            self.last_step_updated = False
+            return False
+        self._pending = []
+        self._pending_clip = None
+        self._prepare_accum(torch.cuda.current_stream(), False)
+        self.finish()
+        return True
 
     @property
     def publishes_copies(self) -> bool:
@@ -302,6 +487,7 @@ class Adam(torch.optim.Optimizer):
                 st["step"] = int(st["step"].item())
         self._tables.clear()                        # the moment buffers were replaced: rebuild the job tables
         self._span = None
+        self._accum = None                          # an open window is discarded with them
 
 
 def clip_grad_norm_(parameters, max_norm: float, norm_type: float = 2.0, error_if_nonfinite: bool = False, foreach=None) -> torch.Tensor:

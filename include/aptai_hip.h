@@ -284,6 +284,20 @@ int aptai_adam_multi_scaled(const int64_t* table_dev, const int64_t* dyn_dev, in
  * single rounded multiply as aptai_adam_multi_scaled, so scale-then-step equals the fused step bit for bit. */
 int aptai_scale_multi(const int64_t* table_dev, const int64_t* dyn_dev, int64_t njobs, int64_t max_n, const float* scale_dev,
                       void* stream);
+/* Gradient accumulation over a window of N micro-batches (the HF Trainer's gradient_accumulation_steps), one launch per micro-step
+ * over the Adam job table above (only n, column 4, is read).  acc_dev: device int64 [njobs] = one fp32 accumulator of n elements per
+ * job; dyn_dev: device int64 [njobs][2] = {grad or 0 (no gradient in this micro-step), mode}:
+ *   mode 0  the job has had no contribution in this window: its accumulator is neither read nor written;
+ *   mode 1  first contribution of the window: acc = grad (an overwrite - there is no zeroing pass; grad must not be 0);
+ *   mode 2  contributed before: acc = acc + grad, or untouched when grad is 0.
+ * scale != 1 closes the window: every job of mode 1 or 2 is then multiplied by it, also one without a gradient in this call.
+ * Arithmetic contract: one rounded fp32 add (__fadd_rn) per element per micro-step, in micro-step order, and one rounded fp32 multiply
+ * (__fmul_rn) by scale = (float)(1.0 / k) at the close - the bits of ((g1 + g2) + ... + gk) * scale evaluated in fp32 in that order;
+ * no division, no atomics, no dependence on the launch geometry.  16-byte vector path when n % 4 == 0 and both pointers are 16-byte
+ * aligned, scalar path otherwise.  Validates and launches only (no allocation, copy or synchronisation): it runs between graph
+ * replays.  Moves 12 B per parameter (8 B on a first contribution); the Adam launch moves 28 B. */
+int aptai_grad_accum_multi(const int64_t* table_dev, const int64_t* dyn_dev, const int64_t* acc_dev, int64_t njobs, int64_t max_n,
+                           float scale, void* stream);
 /* nn.Conv1d weight [N][C][Kw] (HF:260-266) -> [N][Kw*C] bf16, K index = kw*C + c (channels-last frames) */
 int aptai_conv_weight_to_bf16(const float* src, void* dst, int64_t N, int64_t C, int64_t Kw, void* stream);
 /* positional conv (HF:329-356): weight_norm(dim=2) w = g*v/||v||_(0,1) ; v [H][H/groups][Kw], gain [Kw];
