@@ -47,6 +47,7 @@ ARGTYPES = {
     "aptai_dropout_bf16": [_P, _P, _I64, _F, _U64, _P],
     "aptai_dgelu_bf16": [_P, _P, _P, _I64, _P],
     "aptai_conv0_fwd": [_P, _I64, _I64, _P, _P, _P, _P, _I, _F, _P, _I64, _I64, _I64, _I64, _I64, _P, _P, _P],
+    "aptai_conv0_fwd_lens": [_P, _I64, _I64, _P, _P, _P, _P, _I, _F, _P, _I64, _I64, _I64, _I64, _I64, _P, _P, _P, _P],
     "aptai_conv0_bwd": [_P, _I64, _I64, _P, _P, _P, _P, _I, _F, _P, _I64, _I64, _P, _P, _P, _P, _P, _P, _P],
     "aptai_conv0_bwd_workspace_bytes": [_I64, _I64],
     "aptai_conv0_bwd_data": [_P, _I64, _I64, _P, _P, _P, _P, _I, _F, _P, _I64, _I64, _P, _P, _P, _P],
@@ -55,6 +56,7 @@ ARGTYPES = {
     "aptai_head_act_fwd": [_P, _P, _P, _I64, _F, _F, _U64, _P],
     "aptai_head_act_bwd": [_P, _P, _P, _P, _I64, _F, _F, _U64, _P],
     "aptai_lowpass_fir": [_P, _I64, _I64, _P, _I64, _P, _I64, _I64, _I, _I64, _I64, _I64, _I64, _I64, _P],
+    "aptai_lowpass_fir_lens": [_P, _I64, _I64, _P, _I64, _P, _I64, _I64, _I, _I64, _I64, _I64, _I64, _I64, _P, _P],
     "aptai_aptai_loss_fwd": [_P, _P, _P, _I64, _I64, _P, _I64, _I64, _I64, _I64, _F, _F, _P, _P, _P, _P],
     "aptai_aptai_loss_bwd": [_P, _P, _P, _I64, _I64, _P, _I64, _I64, _I64, _I64, _F, _F, _P, _P, _P, _P, _I64, _P],
     "aptai_aptai_loss_workspace_bytes": [],

@@ -18,9 +18,10 @@ import torch.nn.functional as F
 
 from . import ops
 from .config import W2V2Config
+from . import hostlogic
 from .hostlogic import TV_NAMES
 from .modules import LowPassFilterLayer
-from .wav2vec2 import Wav2Vec2Model, _seed
+from .wav2vec2 import Wav2Vec2Model, _seed, batch_invariant_scope
 
 _PADN = 64      # head Linears run on the MFMA GEMM with N padded to 64
 
@@ -44,7 +45,8 @@ def heads_fwd(h, tv_w, tv_b, ph_w, ph_b, st):
     tv_raw = ops.gemm(a_tv, wtv, M, _PADN, H, bias=btv, out_f32=True)
     logits = ops.gemm(a_ph, wph, M, _PADN, H, bias=bph, out_f32=True)
     tvs = torch.empty((g.B, g.T, n_tv), device=dev, dtype=torch.float32)
-    ops.lowpass_fir(tv_raw, _PADN, g.Tp, st.taps, tvs, n_tv, g.T, g.B, g.T, g.T, n_tv, n_tv)
+    # batch-invariant inference (Wav2Vec2Model.batch_invariant): the filter's zero padding starts at each row's own length
+    ops.lowpass_fir(tv_raw, _PADN, g.Tp, st.taps, tvs, n_tv, g.T, g.B, g.T, g.T, n_tv, n_tv, frame_lens=getattr(g, "fir_lens", None))
     scalars, pred = ops.aptai_loss_fwd(tvs, st.tv_tgt, logits, _PADN, g.Tp, st.phn_tgt, g.B, g.T, n_tv, n_phn, st.w_mse, st.w_ce)
     saved = SimpleNamespace(h=h, a_tv=a_tv, a_ph=a_ph, wtv=wtv, wph=wph, tvs=tvs, logits=logits, scalars=scalars, n_tv=n_tv,
                             n_phn=n_phn)
@@ -89,6 +91,10 @@ class _HeadsFn(torch.autograd.Function):
 
 
 class APTAI(nn.Module):
+    # opt-in: eval-mode calls return for every row what the utterance gets at batch size 1 (Wav2Vec2Model.batch_invariant for the
+    # encoder, the low-pass filter padded at each row's own length); training-mode calls are what they were
+    batch_invariant = False
+
     def __init__(self, device, vocab, huggingface_model_id, pretrain_cfg, cache_dir, phn_drop=0.1, tv_drop=0.1,
                  freeze_feature_encoder=True, n_tv=9, n_phn=46):
         super().__init__()
@@ -135,8 +141,9 @@ class APTAI(nn.Module):
         if len(tracks) != self.n_tv:
             raise ValueError(f"expected {self.n_tv} TV tracks, got {len(tracks)}")
         tv_targets = torch.stack(tracks, dim=-1).float()                       # models/aptai.py:67-70
-        w2v2_out = self.wav2vec2(audio_inputs, attention_mask=audio_lengths[:, None], return_dict=True,
-                                 output_hidden_states=True)
+        with batch_invariant_scope(self.wav2vec2, self.batch_invariant and not self.training):
+            w2v2_out = self.wav2vec2(audio_inputs, attention_mask=audio_lengths[:, None], return_dict=True,
+                                     output_hidden_states=True)
         loss, mse, ce, tvs, pred, _ = self._heads(w2v2_out, tv_targets, phn_frames_49hz)
         return {'loss': loss, 'mse_loss': mse, 'ce_loss': ce, 'tvs_pred': tvs, 'phn_fc_pred': pred}
 
@@ -153,7 +160,8 @@ class APTAI(nn.Module):
                 wav = wav[0]
             wav_input = torch.unsqueeze(torch.Tensor(wav), dim=0).to(device)
             wav_len = torch.unsqueeze(torch.LongTensor([len(wav)]), dim=0).to(device)
-            w2v2_out = self.wav2vec2(wav_input, attention_mask=wav_len[:, None], return_dict=True, output_hidden_states=True)
+            with batch_invariant_scope(self.wav2vec2, self.batch_invariant):
+                w2v2_out = self.wav2vec2(wav_input, attention_mask=wav_len[:, None], return_dict=True, output_hidden_states=True)
             _, _, _, tvs, pred, logits = self._heads(w2v2_out, None, None)
             g = w2v2_out._geom
             phn_logits = logits.view(g.B, g.Tp, -1)[:, :g.T, :self.n_phn]
@@ -167,3 +175,40 @@ class APTAI(nn.Module):
                 'phn_fc_pred': pred.squeeze(dim=0).cpu().numpy(),
                 'tvs_pred': tvs_pred_dict,
             }
+
+    def get_aptai_outputs(self, wavs):
+        """Batched sibling of `get_aptai_output`: a list of 1-D waveforms -> a list of dicts with the same keys and per-utterance
+        shapes, from ONE batch-invariant forward (the waveforms zero-padded to the longest; `batch_invariant` is switched on for
+        the call and put back), so every entry is what `get_aptai_output` returns for that waveform up to what the batch size
+        does to the GEMM plans ("Batch-invariant inference")."""
+        self.eval()
+        device = next(self.parameters()).device
+        wavs = [torch.as_tensor(np.asarray(w), dtype=torch.float32).reshape(-1) for w in wavs]
+        if not wavs:
+            return []
+        lens = [int(w.numel()) for w in wavs]
+        cfg = self.wav2vec2.config
+        frames = [hostlogic.conv_layer_lengths(n, cfg.conv_kernel, cfg.conv_stride)[-1] for n in lens]
+        if min(frames) < 1:
+            raise ValueError(f"a waveform of {min(lens)} samples is shorter than the receptive field of the feature encoder")
+        audio = torch.zeros((len(wavs), max(lens)), dtype=torch.float32)
+        for b, w in enumerate(wavs):
+            audio[b, :lens[b]] = w
+        names = TV_NAMES if self.n_tv == 9 else tuple(f"TV{i}" for i in range(self.n_tv))
+        with torch.no_grad(), batch_invariant_scope(self.wav2vec2, True):
+            wav_len = torch.tensor(lens, dtype=torch.long, device=device)
+            w2v2_out = self.wav2vec2(audio.to(device), attention_mask=wav_len[:, None], return_dict=True, output_hidden_states=True)
+            _, _, _, tvs, pred, logits = self._heads(w2v2_out, None, None)
+            g = w2v2_out._geom
+            phn_logits = logits.view(g.B, g.Tp, -1)[:, :g.T, :self.n_phn]
+            probs, phn_logits = F.softmax(phn_logits, dim=-1).cpu().numpy(), phn_logits.cpu().numpy()
+            tvs, pred = tvs.cpu().numpy(), pred.cpu().numpy()
+        out = []
+        for b, T in enumerate(frames):
+            out.append({
+                'phn_fc_probs': probs[b:b + 1, :T].transpose(2, 1, 0),                                  # (C, T, 1) as get_aptai_output
+                'phn_fc_logits': phn_logits[b, :T],
+                'phn_fc_pred': pred[b, :T],
+                'tvs_pred': {n: [row[i] for row in tvs[b, :T]] for i, n in enumerate(names)},
+            })
+        return out

@@ -37,6 +37,16 @@ __device__ __forceinline__ int frames_collated(const int* __restrict__ bounds, i
     return tb < 1 ? 1 : (tb < T_real ? tb : T_real);
 }
 
+// aptai_conv0_fwd_lens (batch-invariant inference): the frames utterance b has ON ITS OWN, (len_b - 10) / 5 + 1 as the caller counted
+// them, never more than the launch's static count or a bucketed graph's bound.  Everything the <true> kernels sum, normalise or write
+// is decided by this count and the frame index alone, so row b of a batch gets the bits it gets at batch size 1.
+__device__ __forceinline__ int frames_own(const int* __restrict__ lens, int b, const int* __restrict__ bounds, int T_real) {
+    int n = lens[b];
+    n = n < T_real ? n : T_real;
+    if (bounds != nullptr) { const int tb = bounds[0]; n = tb < n ? tb : n; }
+    return n < 1 ? 1 : n;
+}
+
 __device__ __forceinline__ void load_weights(const Conv0Args& a, int lane, float (&w)[8][KW], float (&bias)[8]) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
@@ -66,9 +76,13 @@ __device__ __forceinline__ void store8(bf16_t* dst, const float (&o)[8]) {
 }
 
 // ---- mode 1: conv + bias -> LayerNorm(512) -> GELU, one pass.  grid (blocks, B)
-__global__ __launch_bounds__(256) void conv0_layer_kernel(Conv0Args a) {
+// LENS (here and below; `lens` = [B] own first-layer frames, read by the <true> instances only): frames at or beyond the utterance's
+// own count are written as zeros (frames_own), else the static T_real
+template <bool LENS>
+__global__ __launch_bounds__(256) void conv0_layer_kernel(Conv0Args a, const int* __restrict__ lens) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int b = blockIdx.y;
+    const int T_real = LENS ? frames_own(lens, b, a.bounds, a.T_real) : a.T_real;
     float w[8][KW], bias[8], gm[8], bt[8];
     load_weights(a, lane, w, bias);
 #pragma unroll
@@ -81,18 +95,18 @@ __global__ __launch_bounds__(256) void conv0_layer_kernel(Conv0Args a) {
     float xs[KW];
 #pragma unroll
     for (int k = 0; k < KW; ++k) xs[k] = 0.f;
-    if (t < a.T_real) {
+    if (t < T_real) {
 #pragma unroll
         for (int k = 0; k < KW; ++k) xs[k] = xb[(long)t * STRIDE + k];
     }
     for (; t < a.T_alloc; t += tstep) {
         float xn[KW];
         const int tn = t + tstep;
-        const float* xp = xb + (long)(tn < a.T_real ? tn : 0) * STRIDE;      // clamped: always in bounds
+        const float* xp = xb + (long)(tn < T_real ? tn : 0) * STRIDE;      // clamped: always in bounds
 #pragma unroll
         for (int k = 0; k < KW; ++k) xn[k] = xp[k];
         float o[8];
-        if (t < a.T_real) {
+        if (t < T_real) {
             float v[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
@@ -129,12 +143,18 @@ __global__ __launch_bounds__(256) void conv0_layer_kernel(Conv0Args a) {
 constexpr int AC_TERMS = KW + KW * (KW + 1) / 2;        // 65
 constexpr int AC_FRAMES_PER_BLOCK = 1024;
 
+// LENS: the sums stop at the utterance's own frame count.  Chunks are cut by the frame index (AC_FRAMES_PER_BLOCK) and a thread's frames
+// by t mod 256, whatever the batch looks like; a chunk wholly beyond the count leaves at once and conv0_moments_final_kernel<true> never
+// reads its slot.  No sample at or beyond the utterance's length is loaded.
+template <bool LENS>
 __global__ __launch_bounds__(256) void conv0_moments_kernel(const float* __restrict__ audio, long S, int T_static,
-                                                            float* __restrict__ partials, int nch, const int* __restrict__ bounds) {
-    const int T_real = frames_collated(bounds, T_static);
+                                                            float* __restrict__ partials, int nch, const int* __restrict__ bounds,
+                                                            const int* __restrict__ lens) {
+    const int b = blockIdx.y, chunk = blockIdx.x;
+    const int T_real = LENS ? frames_own(lens, b, bounds, T_static) : frames_collated(bounds, T_static);
+    if (LENS && chunk * AC_FRAMES_PER_BLOCK >= T_real) return;
     __shared__ float red[4][AC_TERMS];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int b = blockIdx.y, chunk = blockIdx.x;
     const float* xb = audio + (long)b * S;
     float acc[AC_TERMS];
 #pragma unroll
@@ -166,16 +186,20 @@ __global__ __launch_bounds__(256) void conv0_moments_kernel(const float* __restr
 }
 
 // mean / rstd per (b, c) from the window moments, in double.  grid (B), 512 threads
+template <bool LENS>
 __global__ void conv0_moments_final_kernel(const float* __restrict__ partials, const float* __restrict__ w,
                                            const float* __restrict__ bias, float* __restrict__ stats, int nch, int T_real,
-                                           float eps, const int* __restrict__ bounds) {
+                                           float eps, const int* __restrict__ bounds, const int* __restrict__ lens) {
     __shared__ double mom[AC_TERMS];
     const int b = blockIdx.x, c = threadIdx.x;
+    // bucketed hipGraphs: sums (conv0_moments_kernel) and frame count both follow the batch as collated; LENS: the utterance's own
+    // frames, its chunks summed in ascending order (the chunks the utterance alone would have, no others)
+    const int frames = LENS ? frames_own(lens, b, bounds, T_real) : frames_collated(bounds, T_real);
+    const int nsum = LENS ? (frames + AC_FRAMES_PER_BLOCK - 1) / AC_FRAMES_PER_BLOCK : nch;
     if (c < AC_TERMS) {
         double s = 0.0;
-        for (int k = 0; k < nch; ++k) s += (double)partials[((long)b * nch + k) * AC_TERMS + c];
-        // bucketed hipGraphs: sums (conv0_moments_kernel) and frame count both follow the batch as collated
-        mom[c] = s / frames_collated(bounds, T_real);
+        for (int k = 0; k < nsum; ++k) s += (double)partials[((long)b * nch + k) * AC_TERMS + c];
+        mom[c] = s / frames;
     }
     __syncthreads();
     double wk[KW];
@@ -215,9 +239,11 @@ __device__ __forceinline__ f32x2 gelu_fast2(f32x2 x) {
     return x * (f32x2){__builtin_amdgcn_rcpf(e.x), __builtin_amdgcn_rcpf(e.y)};
 }
 
-__global__ __launch_bounds__(256) void conv0_group_kernel(Conv0Args a) {
+template <bool LENS>
+__global__ __launch_bounds__(256) void conv0_group_kernel(Conv0Args a, const int* __restrict__ lens) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int b = blockIdx.y;
+    const int T_real = LENS ? frames_own(lens, b, a.bounds, a.T_real) : a.T_real;
     f32x2 w2[4][KW], b2[4];
     {
         float w[8][KW], bias[8];
@@ -242,19 +268,19 @@ __global__ __launch_bounds__(256) void conv0_group_kernel(Conv0Args a) {
     float xs[KW];
 #pragma unroll
     for (int k = 0; k < KW; ++k) xs[k] = 0.f;
-    if (t < a.T_real) {
+    if (t < T_real) {
 #pragma unroll
         for (int k = 0; k < KW; ++k) xs[k] = xb[(long)t * STRIDE + k];
     }
     for (; t < a.T_alloc; t += tstep) {
         float xn[KW];
         const int tn = t + tstep;
-        const bool has_next = tn < a.T_real;
+        const bool has_next = tn < T_real;
         const float* xp = xb + (long)(has_next ? tn : 0) * STRIDE;       // clamped: the load is always in bounds
 #pragma unroll
         for (int k = 0; k < KW; ++k) xn[k] = xp[k];
         float o[8];
-        if (t < a.T_real) {
+        if (t < T_real) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 f32x2 acc = b2[j];
@@ -283,10 +309,14 @@ __global__ __launch_bounds__(256) void conv0_group_kernel(Conv0Args a) {
 // Channel map ch(g, 4q + r) = 32 (g / 2) + 8 q + 4 (g % 2) + r: the lane's outputs of a PAIR of groups are 8 consecutive
 // channels = one 16-byte store (a store instruction writes 16 rows x 64 B; the next pair completes the 128-byte lines).
 // One wave per 16 frames; the 96 tap registers stay resident, two groups' accumulators are live at a time.
-__global__ __launch_bounds__(256) void conv0_group_mfma_kernel(Conv0Args a) {
+// LENS: a frame's column of D depends on its own column of B alone, so the other frames of its 16-frame block (zeros beyond the count)
+// and the grid that dealt the block to this wave do not reach it.
+template <bool LENS>
+__global__ __launch_bounds__(256) void conv0_group_mfma_kernel(Conv0Args a, const int* __restrict__ lens) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int q = lane >> 4, f = lane & 15;
     const int b = blockIdx.y;
+    const int T_real = LENS ? frames_own(lens, b, a.bounds, a.T_real) : a.T_real;
     float wa[32][3];                                     // A operand: row i = f, k = 4 s + q
 #pragma unroll
     for (int g = 0; g < 32; ++g) {
@@ -307,7 +337,7 @@ __global__ __launch_bounds__(256) void conv0_group_mfma_kernel(Conv0Args a) {
     const int step = gridDim.x * 4;
     auto load_x = [&](int blk, float (&x)[3]) {
         const int t = blk * 16 + f;
-        const bool real = t < a.T_real;
+        const bool real = t < T_real;
 #pragma unroll
         for (int s = 0; s < 3; ++s) {
             const int k = 4 * s + q;
@@ -921,39 +951,44 @@ extern "C" int64_t aptai_conv0_workspace_bytes(int64_t B, int64_t T_real) {
     return (B * nchunks * 2 * C0 + B * 2 * C0) * 4;
 }
 
-extern "C" int aptai_conv0_fwd(const float* audio, int64_t B, int64_t S, const float* weight, const float* bias,
-                               const float* gamma, const float* beta, int mode, float eps, void* out, int64_t T_real,
-                               int64_t T_alloc, int64_t C, int64_t Kw, int64_t stride, void* workspace, float* stats_out,
-                               void* stream_) {
+// aptai_conv0_fwd (LENS = false, `lens` null: the launches it has always made) and aptai_conv0_fwd_lens (LENS = true) share one body
+template <bool LENS>
+static int conv0_fwd_impl(const char* who, const float* audio, int64_t B, int64_t S, const float* weight, const float* bias,
+                          const float* gamma, const float* beta, int mode, float eps, void* out, int64_t T_real, int64_t T_alloc,
+                          int64_t C, int64_t Kw, int64_t stride, void* workspace, float* stats_out, const int32_t* lens,
+                          void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    APTAI_REQUIRE(audio && weight && gamma && beta && out, "aptai_conv0_fwd: null pointer");
-    APTAI_REQUIRE(C == C0 && Kw == KW && stride == STRIDE, "aptai_conv0_fwd: built for C=512, k=10, s=5 (got %ld,%ld,%ld)",
+    APTAI_REQUIRE(audio && weight && gamma && beta && out, "%s: null pointer", who);
+    APTAI_REQUIRE(!LENS || lens, "%s: null frame_lens0", who);
+    APTAI_REQUIRE(C == C0 && Kw == KW && stride == STRIDE, "%s: built for C=512, k=10, s=5 (got %ld,%ld,%ld)", who,
                   (long)C, (long)Kw, (long)stride);
-    APTAI_REQUIRE(B > 0 && T_real > 0 && T_alloc >= T_real, "aptai_conv0_fwd: bad frame counts");
-    APTAI_REQUIRE((T_real - 1) * STRIDE + KW <= S, "aptai_conv0_fwd: T_real=%ld frames need more than S=%ld samples", (long)T_real, (long)S);
-    APTAI_REQUIRE(mode == 0 || mode == 1, "aptai_conv0_fwd: mode must be 0 (group) or 1 (layer)");
+    APTAI_REQUIRE(B > 0 && T_real > 0 && T_alloc >= T_real, "%s: bad frame counts", who);
+    APTAI_REQUIRE((T_real - 1) * STRIDE + KW <= S, "%s: T_real=%ld frames need more than S=%ld samples", who, (long)T_real, (long)S);
+    APTAI_REQUIRE(mode == 0 || mode == 1, "%s: mode must be 0 (group) or 1 (layer)", who);
+    const int* bounds = (const int*)aptai_frame_bounds(stream_);
     Conv0Args a;
     memset(&a, 0, sizeof(a));
     a.audio = audio; a.S = S; a.w = weight; a.bias = bias; a.gamma = gamma; a.beta = beta;
     a.out = (bf16_t*)out; a.B = (int)B; a.T_real = (int)T_real; a.T_alloc = (int)T_alloc; a.eps = eps;
+    if (LENS) a.bounds = bounds;          // the <true> write passes honour a bucketed graph's bound as well
     long blocks = ceil_div(T_alloc, 4 * 8);           // 8 frames per wave
     if (blocks > 1024) blocks = 1024;
     if (mode == 1) {
-        APTAI_LAUNCH(conv0_layer_kernel, dim3((unsigned)blocks, (unsigned)B), dim3(256), 0, stream, a);
+        APTAI_LAUNCH(conv0_layer_kernel<LENS>, dim3((unsigned)blocks, (unsigned)B), dim3(256), 0, stream, a, (const int*)lens);
         APTAI_CHECK_LAUNCH("conv0_layer_kernel");
         return APTAI_OK;
     }
-    APTAI_REQUIRE(workspace != nullptr, "aptai_conv0_fwd: group mode needs a workspace");
+    APTAI_REQUIRE(workspace != nullptr, "%s: group mode needs a workspace", who);
     a.nchunks = (int)ceil_div(T_real, FRAMES_PER_BLOCK_STATS);
     a.partials = (float*)workspace;
     float* stats = stats_out ? stats_out : (float*)workspace + (long)B * a.nchunks * 2 * C0;
     a.stats = stats;
     const int nch = (int)ceil_div(T_real, AC_FRAMES_PER_BLOCK);   // [B][nch][65] floats: fits the conv-pass workspace
-    APTAI_LAUNCH(conv0_moments_kernel, dim3((unsigned)nch, (unsigned)B), dim3(256), 0, stream, audio, (long)S, (int)T_real,
-                 a.partials, nch, (const int*)aptai_frame_bounds(stream_));
+    APTAI_LAUNCH(conv0_moments_kernel<LENS>, dim3((unsigned)nch, (unsigned)B), dim3(256), 0, stream, audio, (long)S, (int)T_real,
+                 a.partials, nch, bounds, (const int*)lens);
     APTAI_CHECK_LAUNCH("conv0_moments_kernel");
-    APTAI_LAUNCH(conv0_moments_final_kernel, dim3((unsigned)B), dim3(C0), 0, stream, (const float*)a.partials, weight, bias,
-                 stats, nch, (int)T_real, eps, (const int*)aptai_frame_bounds(stream_));
+    APTAI_LAUNCH(conv0_moments_final_kernel<LENS>, dim3((unsigned)B), dim3(C0), 0, stream, (const float*)a.partials, weight, bias,
+                 stats, nch, (int)T_real, eps, bounds, (const int*)lens);
     APTAI_CHECK_LAUNCH("conv0_moments_final_kernel");
     // the conv on the fp32 matrix pipe beside the vector pipe's GELU (APTAI_CONV0_MFMA=0: the all-vector kernel, A/B)
     static int use_mfma = -1;
@@ -967,13 +1002,31 @@ extern "C" int aptai_conv0_fwd(const float* audio, int64_t B, int64_t S, const f
         long mb = ceil_div(1536, B);
         const long mb_max = ceil_div(T_alloc / 16, 4);
         if (mb > mb_max) mb = mb_max;
-        APTAI_LAUNCH(conv0_group_mfma_kernel, dim3((unsigned)mb, (unsigned)B), dim3(256), 0, stream, a);
+        APTAI_LAUNCH(conv0_group_mfma_kernel<LENS>, dim3((unsigned)mb, (unsigned)B), dim3(256), 0, stream, a, (const int*)lens);
         APTAI_CHECK_LAUNCH("conv0_group_mfma_kernel");
         return APTAI_OK;
     }
-    APTAI_LAUNCH(conv0_group_kernel, dim3((unsigned)blocks, (unsigned)B), dim3(256), 0, stream, a);
+    APTAI_LAUNCH(conv0_group_kernel<LENS>, dim3((unsigned)blocks, (unsigned)B), dim3(256), 0, stream, a, (const int*)lens);
     APTAI_CHECK_LAUNCH("conv0_group_kernel");
     return APTAI_OK;
+}
+
+extern "C" int aptai_conv0_fwd(const float* audio, int64_t B, int64_t S, const float* weight, const float* bias,
+                               const float* gamma, const float* beta, int mode, float eps, void* out, int64_t T_real,
+                               int64_t T_alloc, int64_t C, int64_t Kw, int64_t stride, void* workspace, float* stats_out,
+                               void* stream_) {
+    return conv0_fwd_impl<false>("aptai_conv0_fwd", audio, B, S, weight, bias, gamma, beta, mode, eps, out, T_real, T_alloc, C, Kw, stride,
+                                 workspace, stats_out, nullptr, stream_);
+}
+
+/* Batch-invariant form (include/aptai_hip.h): frame_lens0 int32 [B] on the device, each utterance's own first-layer frame count.  Both
+   forms of the group-mode write pass (APTAI_CONV0_MFMA = 1, the default, and 0) are covered. */
+extern "C" int aptai_conv0_fwd_lens(const float* audio, int64_t B, int64_t S, const float* weight, const float* bias,
+                                    const float* gamma, const float* beta, int mode, float eps, void* out, int64_t T_real,
+                                    int64_t T_alloc, int64_t C, int64_t Kw, int64_t stride, void* workspace, float* stats_out,
+                                    const int32_t* frame_lens0, void* stream_) {
+    return conv0_fwd_impl<true>("aptai_conv0_fwd_lens", audio, B, S, weight, bias, gamma, beta, mode, eps, out, T_real, T_alloc, C, Kw,
+                                stride, workspace, stats_out, frame_lens0, stream_);
 }
 
 extern "C" int64_t aptai_conv0_bwd_workspace_bytes(int64_t B, int64_t T_real) {

@@ -9,15 +9,17 @@ constexpr int MAXTAPS = 64;
 
 // y[b][t][c] = sum_j taps[j] * x[b][t + j - N/2][c]   ('same' zero padding over t in [0,T)), fp64 accumulate.
 // in:  fp32 with row stride ldx (rows b*Tp_in + t);  out: fp32 (ldy) or bf16 (ldy) with zero fill of cols >= C.
-template <bool OUT_BF16>
+// LENS (aptai_lowpass_fir_lens, batch-invariant inference): the zero padding of utterance b starts at its OWN frame count lens[b]
+// (never beyond T or the bound); same taps in the same order, so a row is what the utterance gets alone at T = lens[b].
+template <bool OUT_BF16, bool LENS>
 __global__ void fir_kernel(const float* __restrict__ x, long ldx, long rows_per_b_in, const double* __restrict__ taps, int ntaps,
                            void* __restrict__ y, long ldy, long rows_per_b_out, int B, int T_static, int T_out, int C, int C_out,
-                           const int* __restrict__ bounds) {
+                           const int* __restrict__ bounds, const int* __restrict__ lens) {
     __shared__ double tp[MAXTAPS];
     // frames at or beyond the bound do not exist for the filter (zero padding starts there) and are written as zeros: a graph
     // captured for a bucket length then equals the eager run on the batch's own padded length (runtime.hip, aptai_set_frame_bounds)
-    int T = T_static;
-    if (bounds != nullptr) { const int tb = bounds[1]; T = tb < 1 ? 1 : (tb < T_static ? tb : T_static); }
+    int T_batch = T_static;
+    if (bounds != nullptr) { const int tb = bounds[1]; T_batch = tb < 1 ? 1 : (tb < T_static ? tb : T_static); }
     if ((int)threadIdx.x < ntaps) tp[threadIdx.x] = taps[threadIdx.x];
     __syncthreads();
     const long n = (long)B * T_out * C_out;
@@ -27,6 +29,8 @@ __global__ void fir_kernel(const float* __restrict__ x, long ldx, long rows_per_
         const int c = (int)(i % C_out);
         const int t = (int)((i / C_out) % T_out);
         const int b = (int)(i / ((long)C_out * T_out));
+        int T = T_batch;
+        if (LENS) { const int tl = lens[b]; T = tl < 1 ? 1 : (tl < T_batch ? tl : T_batch); }
         double acc = 0.0;
         if (c < C && t < T) {
             const float* xb = x + (long)b * rows_per_b_in * ldx + c;
@@ -185,24 +189,40 @@ constexpr int LOSS_BLOCKS = 128;
 
 }  // namespace
 
-extern "C" int aptai_lowpass_fir(const float* x, int64_t ldx, int64_t rows_per_b_in, const double* taps, int64_t ntaps,
-                                 void* y, int64_t ldy, int64_t rows_per_b_out, int out_bf16, int64_t B, int64_t T,
-                                 int64_t T_out, int64_t C, int64_t C_out, void* stream) {
-    APTAI_REQUIRE(x && taps && y, "aptai_lowpass_fir: null pointer");
-    APTAI_REQUIRE(ntaps > 0 && ntaps <= MAXTAPS && (ntaps & 1), "aptai_lowpass_fir: ntaps=%ld (odd, <= %d)", (long)ntaps, MAXTAPS);
-    APTAI_REQUIRE(B > 0 && T > 0 && T_out >= T && C > 0 && C_out >= C, "aptai_lowpass_fir: bad sizes");
+template <bool LENS>
+static int lowpass_fir_impl(const char* who, const float* x, int64_t ldx, int64_t rows_per_b_in, const double* taps, int64_t ntaps,
+                            void* y, int64_t ldy, int64_t rows_per_b_out, int out_bf16, int64_t B, int64_t T, int64_t T_out, int64_t C,
+                            int64_t C_out, const int32_t* lens, void* stream) {
+    APTAI_REQUIRE(x && taps && y, "%s: null pointer", who);
+    APTAI_REQUIRE(!LENS || lens, "%s: null frame_lens", who);
+    APTAI_REQUIRE(ntaps > 0 && ntaps <= MAXTAPS && (ntaps & 1), "%s: ntaps=%ld (odd, <= %d)", who, (long)ntaps, MAXTAPS);
+    APTAI_REQUIRE(B > 0 && T > 0 && T_out >= T && C > 0 && C_out >= C, "%s: bad sizes", who);
     const long n = B * T_out * C_out;
     unsigned blocks = (unsigned)(ceil_div(n, 256) > 2048 ? 2048 : ceil_div(n, 256));
     if (out_bf16)
-        APTAI_LAUNCH(fir_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, (long)ldx, (long)rows_per_b_in,
+        APTAI_LAUNCH((fir_kernel<true, LENS>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, (long)ldx, (long)rows_per_b_in,
                            taps, (int)ntaps, y, (long)ldy, (long)rows_per_b_out, (int)B, (int)T, (int)T_out, (int)C, (int)C_out,
-                           (const int*)aptai_frame_bounds(stream));
+                           (const int*)aptai_frame_bounds(stream), (const int*)lens);
     else
-        APTAI_LAUNCH(fir_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, (long)ldx, (long)rows_per_b_in,
+        APTAI_LAUNCH((fir_kernel<false, LENS>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, (long)ldx, (long)rows_per_b_in,
                            taps, (int)ntaps, y, (long)ldy, (long)rows_per_b_out, (int)B, (int)T, (int)T_out, (int)C, (int)C_out,
-                           (const int*)aptai_frame_bounds(stream));
+                           (const int*)aptai_frame_bounds(stream), (const int*)lens);
     APTAI_CHECK_LAUNCH("fir_kernel");
     return APTAI_OK;
+}
+
+extern "C" int aptai_lowpass_fir(const float* x, int64_t ldx, int64_t rows_per_b_in, const double* taps, int64_t ntaps,
+                                 void* y, int64_t ldy, int64_t rows_per_b_out, int out_bf16, int64_t B, int64_t T,
+                                 int64_t T_out, int64_t C, int64_t C_out, void* stream) {
+    return lowpass_fir_impl<false>("aptai_lowpass_fir", x, ldx, rows_per_b_in, taps, ntaps, y, ldy, rows_per_b_out, out_bf16, B, T, T_out,
+                                   C, C_out, nullptr, stream);
+}
+
+extern "C" int aptai_lowpass_fir_lens(const float* x, int64_t ldx, int64_t rows_per_b_in, const double* taps, int64_t ntaps,
+                                      void* y, int64_t ldy, int64_t rows_per_b_out, int out_bf16, int64_t B, int64_t T,
+                                      int64_t T_out, int64_t C, int64_t C_out, const int32_t* frame_lens, void* stream) {
+    return lowpass_fir_impl<true>("aptai_lowpass_fir_lens", x, ldx, rows_per_b_in, taps, ntaps, y, ldy, rows_per_b_out, out_bf16, B, T,
+                                  T_out, C, C_out, frame_lens, stream);
 }
 
 extern "C" int64_t aptai_aptai_loss_workspace_bytes(void) { return LOSS_BLOCKS * 4 * 4; }

@@ -24,7 +24,7 @@ from .config import W2V2Config, load_model_cfg
 from .hostlogic import TV_NAMES
 from .modules import CrossAttention, ForwardSumLoss, LowPassFilterLayer, PositionalEncoding, RNN
 from .w2v2_pr import Wav2Vec2_PR
-from .wav2vec2 import _seed
+from .wav2vec2 import _seed, batch_invariant_scope
 
 _NPHN = 60                              # the reference's max_phn_seq_len (models/force_aptai.py:36): the default slot count
 MAX_PHN_SLOTS = ops.XATTN_MAX_SLOTS     # 255: what the wide softmax pair and the CTC kernels (256 classes, 511 states) hold
@@ -78,7 +78,8 @@ def force_heads_fwd(ac, st, P):
     tv_raw = ops.linear_f32(s.h1a, l3_w, l3_b)                                                             # [M][9]
     n_tv = l3_w.shape[0]
     s.tvs = torch.empty((B, T, n_tv), device=dev, dtype=torch.float32)
-    ops.lowpass_fir(tv_raw, n_tv, Tp, st.taps, s.tvs, n_tv, T, B, T, T, n_tv, n_tv)
+    # batch-invariant inference (Wav2Vec2Model.batch_invariant): the filter's zero padding starts at each row's own length
+    ops.lowpass_fir(tv_raw, n_tv, Tp, st.taps, s.tvs, n_tv, T, B, T, T, n_tv, n_tv, frame_lens=getattr(g, "fir_lens", None))
     s.dummy_logits = torch.zeros((M, 1), device=dev, dtype=torch.float32)
     s.dummy_phn = torch.zeros((B, T), device=dev, dtype=torch.int64)
     s.sc, _ = ops.aptai_loss_fwd(s.tvs, st.tv_tgt, s.dummy_logits, 1, Tp, s.dummy_phn, B, T, n_tv, 1, 1.0, 0.0, want_pred=False)
@@ -235,6 +236,11 @@ class Force_APTAI(nn.Module):
     # read-out that belongs to the forward-sum loss; aptai_ctc_viterbi topology 1).  Losses, tvs_pred and gradients do not depend on it.
     alignment_readout = "argmax"
 
+    # opt-in: in eval mode every row of a batch gets what the utterance gets at batch size 1 (the frozen recogniser runs with
+    # Wav2Vec2_PR.batch_invariant, the low-pass filter pads at each row's own length).  Training steps - the recogniser's pass
+    # inside them and the prefetch graph included - are what they were.
+    batch_invariant = False
+
     # where the phoneme sequence comes from: "decoded" (the reference: the frozen recogniser's best path) or "labels" (opt-in: the
     # batch's `phoneme_labels`, the known transcript - labels_to_slots; no decode error can reach the aligner).  get_alignment and
     # get_faptai_output take a waveform alone and always decode.
@@ -261,7 +267,8 @@ class Force_APTAI(nn.Module):
         `labels` (transcript = "labels"): the phoneme slots come from them and nothing is decoded."""
         pr = self.w2v2_pr
         pr.eval()                                                      # models/w2v2_pr.py:125: the recogniser always runs in eval mode
-        with torch.no_grad():
+        # the recogniser is in eval mode while the heads train too: batch invariance reaches it only when this module evaluates
+        with torch.no_grad(), batch_invariant_scope(pr, self.batch_invariant and not self.training):
             lens1d = audio_lengths.reshape(-1)
             out, _ = pr._logits_eval(audio_inputs, lens1d[:, None])
             dev = out._flat_last.device
@@ -304,6 +311,8 @@ class Force_APTAI(nn.Module):
         key = (tuple(audio_inputs.shape), tuple(audio_lengths.shape), audio_inputs.dtype, audio_lengths.dtype,
                getattr(self.w2v2_pr.wav2vec2, "_encoder_precision", "bf16"))
         use_graph = os.environ.get("APTAI_FORCE_ENC_GRAPH", "1") != "0"
+        if self.batch_invariant and not self.training:
+            use_graph = False                                          # the captured pass is a training device: batch-invariant evaluation encodes eagerly
         with torch.cuda.stream(self._enc_stream):
             ge = self._enc_graphs.get(key) if use_graph else None
             if ge is None and use_graph and self._enc_seen.get(key, 0) >= 1:

@@ -59,6 +59,14 @@ def conv_layer_lengths(n_samples: int, conv_kernel: Sequence[int], conv_stride: 
     return out
 
 
+def conv0_frame_lengths(sample_lengths: torch.Tensor, kernel: int = 10, stride: int = 5) -> torch.Tensor:
+    """First-layer frame count of every utterance, ``(len - kernel) // stride + 1`` as int32 (``conv_layer_lengths(len)[0]``),
+    for the batch-invariant kernels (aptai_conv0_fwd_lens).  Pure tensor arithmetic on the lengths' device: no read-back.
+    Utterances shorter than one window give values < 1; the model refuses those from the padded shape."""
+    n = sample_lengths.reshape(-1).long()
+    return (torch.div(n - kernel, stride, rounding_mode="floor") + 1).to(torch.int32).contiguous()
+
+
 def frame_attention_mask(n_frames: int, frame_lengths: torch.Tensor) -> torch.Tensor:
     """(B, T) bool mask of valid frames — same result as HF:1018-1036's flip/cumsum construction."""
     ar = torch.arange(n_frames, device=frame_lengths.device)

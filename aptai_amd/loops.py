@@ -6,6 +6,7 @@ is called and what gets printed stay in each loop's own module.
 """
 from __future__ import annotations
 
+import functools
 import pickle
 from pathlib import Path
 from types import SimpleNamespace
@@ -44,7 +45,7 @@ def default_cfg(overrides, **own):
     """The hyper-parameters all three loops take at the reference's argparse defaults, the loop's `own` ones, then `overrides`."""
     cfg = SimpleNamespace(device="cuda", num_epochs=2, adam_beta1=0.9, adam_beta2=0.999, adam_epsilon=1e-8, adam_weight_decay=0.0,
                           num_warmup_epochs=10, num_static_epochs=30, lr_decay=0.96, target_metric_bigger_better=False,
-                          device_metrics=False, source_rate=None, normalize_audio=False, **own)
+                          device_metrics=False, batch_invariant_eval=False, source_rate=None, normalize_audio=False, **own)
     cfg.__dict__.update(overrides)
     return cfg
 
@@ -57,12 +58,33 @@ def add_shared_arguments(ap):
     ap.add_argument("--source_rate", type=int, default=None,
                     help="the corpus' sampling rate: the audio is uploaded at that rate and resampled to 16 kHz on the device")
     ap.add_argument("--normalize_audio", action="store_true", help="zero-mean / unit-variance normalisation on the device")
+    ap.add_argument("--batch_invariant_eval", action="store_true",
+                    help="validate() / test() with the model's batch_invariant switch on: every utterance of a batch scored as if it "
+                         "ran alone, so evaluation may run at any batch size (off by default)")
 
 
 def shared_arguments(a) -> dict:
     """The parsed flags of add_shared_arguments as default_cfg entries."""
     return dict(max_grad_norm=a.max_grad_norm, gradient_accumulation_steps=a.gradient_accumulation_steps, source_rate=a.source_rate,
-                normalize_audio=a.normalize_audio)
+                normalize_audio=a.normalize_audio, batch_invariant_eval=a.batch_invariant_eval)
+
+
+def batch_invariant_eval(fn):
+    """Gives a loop's validate() / test() the keyword `batch_invariant=False` (cfg.batch_invariant_eval in train()): the model's
+    `batch_invariant` attribute is set for the duration of the pass, on the host-metrics and the device-metrics path alike, and put
+    back afterwards.  Every utterance of a batch then gets its batch-1 predictions, so the per-utterance metrics do not depend on
+    the loader's batch size; `val_mean_loss` stays a mean over BATCHES of the model's batch loss."""
+    @functools.wraps(fn)
+    def run(model, *args, batch_invariant=False, **kw):
+        if not batch_invariant:
+            return fn(model, *args, **kw)
+        prev = model.batch_invariant
+        model.batch_invariant = True
+        try:
+            return fn(model, *args, **kw)
+        finally:
+            model.batch_invariant = prev
+    return run
 
 
 def save_checkpoint(model, path):

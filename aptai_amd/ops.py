@@ -759,13 +759,28 @@ def dgelu(dy, u):
 
 
 # ----------------------------------------------------------------------------- conv layer 0
-def conv0_fwd(audio, weight, bias, gamma, beta, mode, out, T_real, T_alloc, eps=1e-5, want_stats=False):
-    """Returns the (mean, rstd) block [B][2][512] in group mode when ``want_stats`` (needed by conv0_bwd)."""
+def _lens_vec(lens, B, what):
+    """A per-utterance length vector of the batch-invariant entries: int32 [B], contiguous, on the device."""
+    _dev(lens)
+    if lens.dtype != torch.int32 or lens.shape != (B,) or not lens.is_contiguous():
+        raise ValueError(f"{what} must be a contiguous int32 tensor of shape ({B},), got {lens.dtype} {tuple(lens.shape)}")
+    return lens
+
+
+def conv0_fwd(audio, weight, bias, gamma, beta, mode, out, T_real, T_alloc, eps=1e-5, want_stats=False, frame_lens0=None):
+    """Returns the (mean, rstd) block [B][2][512] in group mode when ``want_stats`` (needed by conv0_bwd).  ``frame_lens0`` (int32
+    [B] on the device, hostlogic.conv0_frame_lengths): the batch-invariant entry aptai_conv0_fwd_lens - every row normalised
+    over its own frames and zero beyond them, bit for bit what it gets alone; None is the plain call."""
     _dev(audio, weight, bias, gamma, beta, out)
     B, S = audio.shape
     C, _, Kw = weight.shape
     ws = _ws(_lib.lib().aptai_conv0_workspace_bytes(B, T_real), audio.device) if mode == 0 else None
     stats = torch.empty((B, 2, C), device=audio.device, dtype=torch.float32) if (want_stats and mode == 0) else None
+    if frame_lens0 is not None:
+        _lib.call("aptai_conv0_fwd_lens", audio.data_ptr(), B, S, weight.data_ptr(), _ptr(bias), gamma.data_ptr(), beta.data_ptr(),
+                  mode, eps, out.data_ptr(), T_real, T_alloc, C, Kw, 5, _ptr(ws), _ptr(stats),
+                  _lens_vec(frame_lens0, B, "frame_lens0").data_ptr(), _stream())
+        return stats
     _lib.call("aptai_conv0_fwd", audio.data_ptr(), B, S, weight.data_ptr(), _ptr(bias), gamma.data_ptr(), beta.data_ptr(), mode,
               eps, out.data_ptr(), T_real, T_alloc, C, Kw, 5, _ptr(ws), _ptr(stats), _stream())
     return stats
@@ -815,8 +830,15 @@ def head_act_bwd(h, d_tv, d_ph, p_tv, p_ph, seed):
     return dh
 
 
-def lowpass_fir(x, ldx, rows_per_b_in, taps_f64, y, ldy, rows_per_b_out, B, T, T_out, C, C_out):
+def lowpass_fir(x, ldx, rows_per_b_in, taps_f64, y, ldy, rows_per_b_out, B, T, T_out, C, C_out, frame_lens=None):
+    """``frame_lens`` (int32 [B] on the device): aptai_lowpass_fir_lens - the zero padding of each row starts at its own frame
+    count, zeros beyond; None is the plain call (one T for the batch)."""
     _dev(x, taps_f64, y)
+    if frame_lens is not None:
+        _lib.call("aptai_lowpass_fir_lens", x.data_ptr(), ldx, rows_per_b_in, taps_f64.data_ptr(), taps_f64.numel(), y.data_ptr(), ldy,
+                  rows_per_b_out, int(y.dtype == torch.bfloat16), B, T, T_out, C, C_out,
+                  _lens_vec(frame_lens, B, "frame_lens").data_ptr(), _stream())
+        return y
     _lib.call("aptai_lowpass_fir", x.data_ptr(), ldx, rows_per_b_in, taps_f64.data_ptr(), taps_f64.numel(), y.data_ptr(), ldy,
               rows_per_b_out, int(y.dtype == torch.bfloat16), B, T, T_out, C, C_out, _stream())
     return y

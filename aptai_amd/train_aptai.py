@@ -81,6 +81,7 @@ def train(cfg, model, optimizer, lr_scheduler, train_dataloader, valid_dataloade
                 f"lr: {optimizer.param_groups[0]['lr']:.6f}")
         epoch_log = run.end_epoch(epoch, lambda: validate(model, cfg.device, cfg.vocab, epoch, getattr(cfg, "exp_dir", None), test_spk,
                                                           valid_dataloader, device_metrics=getattr(cfg, "device_metrics", False),
+                                                          batch_invariant=getattr(cfg, "batch_invariant_eval", False),
                                                           frontend=frontend))
         log(loops.epoch_line(cfg, epoch_log))
     return run.close()
@@ -104,6 +105,7 @@ def _device_eval(model, device, epoch, dl, acc, frontend=None):
     return acc.result()
 
 
+@loops.batch_invariant_eval
 def validate(model, device, vocab, epoch, exp_dir, test_spk, val_dl, log_step=100, device_metrics=False, frontend=None) -> Dict[str, float]:
     """train/train_aptai.py:533-652, batch size 1.  Reproduces the reference as written, including its two quirks: the ground
     truth stack lists TTCD in the TMCD slot (:557-560) and `get_stats` receives frame label sequences, not boundary times.
@@ -161,6 +163,7 @@ def _score_file(s, model, device, epoch, batch_x, frontend, pred_frames=lambda o
     return outputs, batch_x, y, yhat
 
 
+@loops.batch_invariant_eval
 def test(model, device, vocab, exp_dir, test_spk, test_dl, rate, log_step=100, num_epochs=0, device_metrics=False,
          frontend=None) -> Dict[str, float]:
     """train/train_aptai.py:655-850, batch size 1: per-track RMSE / PCC means, FER, frame-grouped PER, overlap, boundary scores,

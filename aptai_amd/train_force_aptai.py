@@ -79,6 +79,7 @@ def train(cfg, model, optimizer, lr_scheduler, train_dataloader, valid_dataloade
                 f"lr: {optimizer.param_groups[0]['lr']:.6f}")
         epoch_log = run.end_epoch(epoch, lambda: validate(model, cfg.device, cfg.vocab, epoch, getattr(cfg, "exp_dir", None), test_spk,
                                                           valid_dataloader, device_metrics=getattr(cfg, "device_metrics", False),
+                                                          batch_invariant=getattr(cfg, "batch_invariant_eval", False),
                                                           frontend=frontend))
         log(loops.epoch_line(cfg, epoch_log))
     return run.close()
@@ -118,6 +119,7 @@ def _device_eval(model, device, epoch, dl, acc, frontend=None):
     return acc.result()
 
 
+@loops.batch_invariant_eval
 def validate(model, device, vocab, epoch, exp_dir, test_spk, val_dl, log_step=100, device_metrics=False, frontend=None) -> Dict[str, float]:
     """train/train_force_aptai.py:533-652, batch size 1 (incl. the TTCD-twice ground-truth stack).  `device_metrics=True`
     (opt-in): the same entries from aptai_amd.device_metrics, one device->host transfer per call."""
@@ -130,6 +132,7 @@ def validate(model, device, vocab, epoch, exp_dir, test_spk, val_dl, log_step=10
     return metrics.eval_summary("val", **s)
 
 
+@loops.batch_invariant_eval
 def test(model, device, vocab, exp_dir, test_spk, test_dl, rate, log_step=100, num_epochs=0, device_metrics=False,
          frontend=None) -> Dict[str, float]:
     """train/train_force_aptai.py:655-838: as train_aptai.test plus the std entries and the CTC-based PER."""

@@ -115,7 +115,8 @@ def train(cfg, model, optimizer, lr_scheduler, vocab, train_dataloader, valid_da
                 outputs = run.eager_step(lambda: model(**batch_x))
             log(f"\tepoch {epoch + 1} ~ batch {run.steps}/{epoch_train_steps}, train_loss: {float(outputs['loss'].detach()):.4f}")
         epoch_log = run.end_epoch(epoch, lambda: validate(model, cfg.device, vocab, epoch, valid_dataloader,
-                                                          device_metrics=getattr(cfg, "device_metrics", False), frontend=frontend),
+                                                          device_metrics=getattr(cfg, "device_metrics", False),
+                                                          batch_invariant=getattr(cfg, "batch_invariant_eval", False), frontend=frontend),
                                   planned_steps=epoch_train_steps, extra_checkpoints=lambda: save_epoch_and_last(epoch))
         log(f"Epoch {epoch + 1}/{cfg.num_epochs} -> lr: {epoch_log['lr']}| mean_train_loss: {epoch_log['mean_train_loss']}| "
             f"mean_val_loss: {epoch_log['mean_val_loss']}| val_per: {epoch_log['mean_val_per']}")
@@ -152,6 +153,7 @@ def _device_eval(model, device, dl, acc, with_loss, laptop=False, frontend=None)
     return acc.result()
 
 
+@loops.batch_invariant_eval
 def validate(model, device, vocab, epoch, validate_dataloader, log_step=100, device_metrics=False, frontend=None) -> Dict[str, float]:
     """train/train_phoneme_recognizer.py:509-561, batch size 1.  `device_metrics=True` (opt-in): the edit distances stay on the
     device (aptai_amd.device_metrics), one device->host transfer per call."""
@@ -170,6 +172,7 @@ def validate(model, device, vocab, epoch, validate_dataloader, log_step=100, dev
     return metrics.eval_summary("pr_val", edit_d, n_phn, losses=val_losses)
 
 
+@loops.batch_invariant_eval
 def test(model, device, vocab, test_dl, dataset_name, log_step=100, laptop=False, device_metrics=False, frontend=None) -> Dict[str, float]:
     """train/train_phoneme_recognizer.py:566-617."""
     edit_d, n_phn = [], []

@@ -21,7 +21,7 @@ import torch.nn as nn
 
 from . import hostlogic, ops
 from .modules import _LinearFn
-from .wav2vec2 import Wav2Vec2Model, _round_up, _seed
+from .wav2vec2 import Wav2Vec2Model, _round_up, _seed, batch_invariant_scope
 
 
 def pr_head_fwd(h, w, b, st):
@@ -76,6 +76,11 @@ class _CtcHeadFn(torch.autograd.Function):
 class Wav2Vec2_PR(nn.Module):
     """Wav2Vec2 model used as a phoneme recognizer."""
 
+    # opt-in: eval-mode calls (forward in eval mode, force_align, get_embeddings, get_ctc_logits, ...) return for every row what the
+    # utterance gets at batch size 1 - Wav2Vec2Model.batch_invariant for the encoder, and the best-path decode stops at each row's
+    # own last frame.  Training-mode forwards are what they were.
+    batch_invariant = False
+
     def __init__(self, pretrain_cfg, cache_dir, huggingface_model_id, vocab):
         super().__init__()
         self.cache_dir = cache_dir
@@ -91,7 +96,8 @@ class Wav2Vec2_PR(nn.Module):
     # ------------------------------------------------------------------ training forward (models/w2v2_pr.py:40-88)
     def forward(self, input_values, input_lengths, phoneme_labels):
         cfg = self.wav2vec2.config
-        outputs = self.wav2vec2(input_values, attention_mask=input_lengths[:, None], return_dict=True, output_hidden_states=True)
+        with batch_invariant_scope(self.wav2vec2, self.batch_invariant and not self.training):
+            outputs = self.wav2vec2(input_values, attention_mask=input_lengths[:, None], return_dict=True, output_hidden_states=True)
         g = outputs._geom
         dev = outputs._flat_last.device
         state_lens = self.wav2vec2._get_feat_extract_output_lengths(input_lengths)
@@ -110,7 +116,8 @@ class Wav2Vec2_PR(nn.Module):
     # ------------------------------------------------------------------ inference helpers
     def _logits_eval(self, audio_inputs, lengths_2d):
         """eval-mode encoder + pr_head (fp32 logits (B,T,V)); shared by every helper below."""
-        out = self.wav2vec2(audio_inputs, attention_mask=lengths_2d, return_dict=True, output_hidden_states=True)
+        with batch_invariant_scope(self.wav2vec2, self.batch_invariant and not self.training):
+            out = self.wav2vec2(audio_inputs, attention_mask=lengths_2d, return_dict=True, output_hidden_states=True)
         g, h = out._geom, out._flat_last
         V, H = self.pr_head.weight.shape
         Np = _round_up(V, 64)
@@ -162,11 +169,26 @@ class Wav2Vec2_PR(nn.Module):
         (hostlogic.ctc_bracketed_best_path: prepended / appended unless the first / last frame's own token is the silence)."""
         g, full = out._geom, out._logits_full
         V = self.pr_head.weight.shape[0]
+        own = getattr(g, "fir_lens", None)
+        last = None
+        if own is not None:
+            # batch-invariant: the frames past a row's own length do not exist at batch size 1, so they decode as blank here (a
+            # copy of the small logit block with those frames' rows put on the blank; `_logits_full` itself stays as computed)
+            rows = full.view(g.B, g.Tp, -1)
+            pad = torch.arange(g.Tp, device=full.device)[None, :, None] >= own[:, None, None]
+            blank_row = torch.zeros(rows.shape[-1], device=full.device, dtype=full.dtype)
+            blank_row[self._blank()] = 1.0
+            full = torch.where(pad, blank_row, rows).view(full.shape).contiguous()
+            last = (own.long() - 1).clamp(min=0)
         ids, n = ops.ctc_greedy_decode(full, full.shape[1], g.Tp, g.B, g.T, V, self._blank(), max_n)
         sil = self._sil()
         if sil is None:
             return ids, n
-        ends = full.view(g.B, g.Tp, -1)[:, [0, g.T - 1], :V].argmax(dim=-1)
+        if last is None:
+            ends = full.view(g.B, g.Tp, -1)[:, [0, g.T - 1], :V].argmax(dim=-1)
+        else:
+            rows = full.view(g.B, g.Tp, -1)[:, :, :V]
+            ends = torch.stack([rows[:, 0].argmax(dim=-1), rows[torch.arange(g.B, device=full.device), last].argmax(dim=-1)], dim=1)
         front, back = (ends[:, :1] != sil).to(torch.int32), (ends[:, 1:] != sil).to(torch.int32)          # [B][1]
         pos = torch.arange(max_n, device=ids.device, dtype=torch.int32)[None]
         n1 = n[:, None]

@@ -10,6 +10,7 @@ compute copies are cached per parameter version.  "HF:n" cites modeling_wav2vec2
 """
 from __future__ import annotations
 
+import contextlib
 import json
 import math
 import os
@@ -433,8 +434,30 @@ class _FinalLNImpl:
 
 
 # =================================================================================== the model
+# encoder precisions whose first conv layer reads the statistics block of aptai_conv0_fwd(_lens): all five that exist
+_BATCH_INVARIANT_PRECISIONS = ("bf16", "bf16_f32res", "f32x3", "f32x6", "mxfp8")
+
+
+@contextlib.contextmanager
+def batch_invariant_scope(encoder, on: bool):
+    """Sets ``encoder.batch_invariant`` for the duration of one call of a model built on it and puts the old value back."""
+    prev = encoder.batch_invariant
+    encoder.batch_invariant = bool(on)
+    try:
+        yield
+    finally:
+        encoder.batch_invariant = prev
+
+
 class Wav2Vec2Model(nn.Module):
     """Drop-in for ``transformers.Wav2Vec2Model`` on the reference's call pattern."""
+
+    # Opt-in, eval-mode forwards only (every encoder precision): what a row returns on its valid frames depends on that utterance's
+    # samples, its length and the weights alone - not on the batch size, the padded length, the other rows or the padding samples.
+    # wav2vec2-base takes its first layer's GroupNorm statistics over the row's own frames (aptai_conv0_fwd_lens) instead of the
+    # collated length (HF:317-323 on a padded batch), so at batch > 1 it deliberately differs from the reference and equals the
+    # reference's batch-1 result.  Train-mode forwards ignore it; gradients through it are refused.
+    batch_invariant = False
 
     def __init__(self, config):
         super().__init__()
@@ -732,8 +755,11 @@ class Wav2Vec2Model(nn.Module):
             return self._scratch(("conv", i, rows), rows * C, dev).view(rows, C)
         buf = new_buf(0, g.B * g.alloc[0] + 8)
         l0 = cl[0]
+        # batch-invariant inference (forward): the first layer normalises every row over its own frames; never on the saving path
+        lens0 = None if save else getattr(g, "lens0", None)
         stats0 = ops.conv0_fwd(audio, l0.conv.weight, l0.conv.bias if cfg.conv_bias else None, l0.layer_norm.weight,
-                               l0.layer_norm.bias, 1 if layer_mode else 0, buf, g.Tl[0], g.alloc[0], want_stats=save)
+                               l0.layer_norm.bias, 1 if layer_mode else 0, buf, g.Tl[0], g.alloc[0], want_stats=save,
+                               frame_lens0=lens0)
         if save:
             sv.bufs.append(buf)
             sv.stats0 = stats0
@@ -826,6 +852,9 @@ class Wav2Vec2Model(nn.Module):
         params = self._conv_params()
         # autograd path when a conv parameter OR the waveform requires grad (input gradients: saliency, attribution)
         trainable = torch.is_grad_enabled() and (audio.requires_grad or any(p.requires_grad for p in params))
+        if trainable and getattr(g, "lens0", None) is not None:
+            raise NotImplementedError("batch_invariant: the per-utterance GroupNorm has no backward - run the eval-mode forward "
+                                      "under torch.no_grad() or freeze the feature encoder")
         if not trainable:
             with torch.no_grad():
                 return self._conv_forward(audio, g, save=False)[0]
@@ -904,7 +933,8 @@ class Wav2Vec2Model(nn.Module):
         if not layer_mode:                                   # GroupNorm statistics (double-precision window moments, csrc/conv.hip)
             scratch = self._scratch(("conv", 0, g.B * g.alloc[0] + 8), (g.B * g.alloc[0] + 8) * C, dev).view(-1, C)
             stats = ops.conv0_fwd(audio, l0.conv.weight, l0.conv.bias if cfg.conv_bias else None, l0.layer_norm.weight,
-                                  l0.layer_norm.bias, 0, scratch, g.Tl[0], g.alloc[0], want_stats=True)
+                                  l0.layer_norm.bias, 0, scratch, g.Tl[0], g.alloc[0], want_stats=True,
+                                  frame_lens0=getattr(g, "lens0", None))
         if layer_mode:
             # wav2vec2-large: a LayerNorm sits between the conv layers, so every layer's fp32 output is stored, normalised and split
             buf = torch.empty((g.B * g.alloc[0] + 8, C), device=dev, dtype=torch.float32)
@@ -1013,6 +1043,16 @@ class Wav2Vec2Model(nn.Module):
         if want_attn and getattr(self, "_encoder_precision", "bf16") not in ("bf16", "bf16_f32res"):
             raise NotImplementedError(f"output_attentions is not available with encoder precision {self._encoder_precision!r}: "
                                       "the attention maps come from the bf16 attention kernels ('bf16', 'bf16_f32res')")
+        # batch-invariant inference (opt-in, eval mode only): refusals first, before anything is launched
+        batch_invariant = bool(self.batch_invariant) and not self.training
+        if batch_invariant:
+            prec = getattr(self, "_encoder_precision", "bf16")
+            if prec not in _BATCH_INVARIANT_PRECISIONS:
+                raise NotImplementedError(f"batch_invariant is not available with encoder precision {prec!r}: its first conv layer "
+                                          "does not take the per-utterance statistics")
+            if torch.is_grad_enabled() and input_values.requires_grad:
+                raise NotImplementedError("batch_invariant: no gradient w.r.t. the waveform (the per-utterance GroupNorm backward is "
+                                          "not built); switch it off for input gradients")
         audio = input_values.float().contiguous()
         B, S = audio.shape
         g = self._geometry(B, S)
@@ -1024,6 +1064,15 @@ class Wav2Vec2Model(nn.Module):
         else:
             frame_lens = torch.full((B,), g.T, device=dev, dtype=torch.long)
         lens_i32 = frame_lens.to(torch.int32).contiguous()
+        # ---- batch-invariant inference (opt-in, eval mode only): each row as if it ran alone - the first conv layer's statistics over
+        # the row's own frames (g.lens0) and, in the heads that follow, the FIR's zero padding at the row's own length (g.fir_lens)
+        g.lens0 = g.fir_lens = None
+        if batch_invariant:
+            if attention_mask is not None:
+                g.lens0 = hostlogic.conv0_frame_lengths(sample_lens, cfg.conv_kernel[0], cfg.conv_stride[0]).clamp(min=1, max=g.Tl[0])
+            else:
+                g.lens0 = torch.full((B,), g.Tl[0], device=dev, dtype=torch.int32)
+            g.fir_lens = lens_i32
         self._step += 1
         seed = _seed(self.base_seed, self._step)
         training = self.training

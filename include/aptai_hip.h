@@ -357,6 +357,21 @@ int aptai_conv0_fwd(const float* audio, int64_t B, int64_t S, const float* weigh
                     const float* beta, int mode, float eps, void* out, int64_t T_real, int64_t T_alloc, int64_t C,
                     int64_t Kw, int64_t stride, void* workspace, float* stats_out, void* stream);
 int64_t aptai_conv0_workspace_bytes(int64_t B, int64_t T_real);
+/* Batch-invariant form of aptai_conv0_fwd (inference; Wav2Vec2Model.batch_invariant): the same operands plus frame_lens0, int32 [B] on
+ * the device, utterance b's OWN first-layer frame count (len_b - 10) / 5 + 1 >= 1.  The effective count of a row is
+ * n_b = max(1, min(frame_lens0[b], T_real, bounds[0] of aptai_set_frame_bounds when one is bound to the stream)).
+ *   mode 0: the GroupNorm moments run over frames t < n_b only and are divided by n_b; out[b][t] = 0 for n_b <= t < T_alloc;
+ *           stats_out [B][2][512] as in aptai_conv0_fwd (aptai_conv0_fwd_f32 / _split, which read it, follow unchanged).
+ *   mode 1: the arithmetic of aptai_conv0_fwd, zeros for n_b <= t < T_alloc.
+ * Row b - its valid frames and its stats_out row - is bit for bit what the utterance gets from this entry at B = 1, S = len_b: the moment
+ * chunks (1024 frames) and a thread's frames within a chunk follow the frame index alone, the chunks of a row are summed in ascending
+ * order and those wholly beyond n_b are neither computed nor read.  Frames are masked by selection: no sample at or beyond
+ * 5 (n_b - 1) + 10 <= len_b reaches a result, whatever it holds (NaN included).  Both forms of the group-mode write pass are covered
+ * (APTAI_CONV0_MFMA=1, the default, and 0).  Runs on `stream`, never synchronises, no atomics, capturable; workspace as
+ * aptai_conv0_workspace_bytes(B, T_real).  The backward entries below do not know this form (inference only). */
+int aptai_conv0_fwd_lens(const float* audio, int64_t B, int64_t S, const float* weight, const float* bias, const float* gamma,
+                         const float* beta, int mode, float eps, void* out, int64_t T_real, int64_t T_alloc, int64_t C,
+                         int64_t Kw, int64_t stride, void* workspace, float* stats_out, const int32_t* frame_lens0, void* stream);
 /* backward of the same fused layer: recomputes the conv from the waveform, folds GELU' and the GroupNorm / LayerNorm
  * backward, and reduces dweight [512][10] (+ dbias, dgamma, dbeta) deterministically.  dy bf16 [B][T_alloc][512];
  * fwd_stats fp32 [B][2][512] = (mean, rstd) written by the forward (`stats_out`), group mode only. */
@@ -385,6 +400,13 @@ int aptai_head_act_bwd(const void* h, const void* d_tv, const void* d_ph, void* 
 int aptai_lowpass_fir(const float* x, int64_t ldx, int64_t rows_per_b_in, const double* taps, int64_t ntaps, void* y,
                       int64_t ldy, int64_t rows_per_b_out, int out_bf16, int64_t B, int64_t T, int64_t T_out, int64_t C,
                       int64_t C_out, void* stream);
+/* Batch-invariant form: frame_lens int32 [B] on the device.  For row b the zero padding starts at
+ * n_b = max(1, min(frame_lens[b], T, bounds[1] of aptai_set_frame_bounds when bound)): taps outside [0, n_b) weigh 0 and frames
+ * n_b <= t < T_out are written as 0.  Tap order and the fp64 accumulate are those of aptai_lowpass_fir, so a row equals, bit for bit,
+ * aptai_lowpass_fir on that utterance alone at T = n_b.  Same stream / no-sync / no-atomics / capture properties. */
+int aptai_lowpass_fir_lens(const float* x, int64_t ldx, int64_t rows_per_b_in, const double* taps, int64_t ntaps, void* y,
+                           int64_t ldy, int64_t rows_per_b_out, int out_bf16, int64_t B, int64_t T, int64_t T_out, int64_t C,
+                           int64_t C_out, const int32_t* frame_lens, void* stream);
 /* loss = w_mse * MSE(tv_pred[mask], tv_tgt[mask]) + w_ce * CE(logits[phn!=0], phn) and argmax (models/aptai.py:89-106;
  * models/force_aptai.py:137-141 with w_ce = 0).  scalars fp32[5] = loss, mse, ce, #valid tv elements, #valid frames. */
 int aptai_aptai_loss_fwd(const float* tv_pred, const float* tv_tgt, const float* logits, int64_t ldl, int64_t rows_per_b,
