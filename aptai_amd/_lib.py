@@ -74,6 +74,8 @@ ARGTYPES = {
     "aptai_adam_multi_scaled": [_P, _P, _I64, _I64, _F, _F, _F, _F, _F, _P, _P],
     "aptai_scale_multi": [_P, _P, _I64, _I64, _P, _P],
     "aptai_grad_accum_multi": [_P, _P, _P, _I64, _I64, _F, _P],
+    "aptai_ema_multi": [_P, _P, _I64, _I64, _F, _P],
+    "aptai_swap_multi": [_P, _P, _I64, _I64, _P],
     "aptai_sgemm_f32": [_P, _I, _I64, _I64, _P, _I64, _I64, _P, _I64, _P, _F, _I, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P],
     "aptai_sgemm_workspace_bytes": [_I64, _I64, _I64, _I64],
     "aptai_colsum_f32_workspace_bytes": [_I64],

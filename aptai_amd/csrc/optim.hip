@@ -272,6 +272,87 @@ __global__ __launch_bounds__(256) void grad_accum_kernel(const int64_t* __restri
     }
 }
 
+// ---------------------------------------------------------------------------------- exponential moving average of the weights
+// Behind the Adam launches of an update: job y's average moves towards its parameter, ema = ema + weight * (p - ema), as three
+// rounded fp32 operations (__fsub_rn, __fmul_rn, __fadd_rn: no fused multiply-add, so the bits are those of torch's
+// e + w * (p - e) on CPU tensors).  Only the parameter pointer (column 0) and n (column 4) of the Adam job table are read; there is
+// no per-step row: a job without a gradient in this update (LayerDrop) still averages.  The chunking and thread mapping of
+// adam_multi_kernel, every load of a thread before its first store, no atomics.
+// (the build runs with -ffp-contract=fast, under which the back end fuses a * b + c whatever the source says, and the __f*_rn
+// spellings are plain operators here: the empty asm makes the rounded product opaque, so the add cannot absorb the multiply)
+__device__ __forceinline__ float ema_one(float e, float p, float weight) {
+    float s = __fmul_rn(weight, __fsub_rn(p, e));
+    asm volatile("" : "+v"(s));
+    return __fadd_rn(e, s);
+}
+
+__global__ __launch_bounds__(256) void ema_multi_kernel(const int64_t* __restrict__ table, const int64_t* __restrict__ emap,
+                                                        float weight) {
+    const int64_t* job = table + (long)blockIdx.y * 6;
+    const long n = job[4];
+    const long base = (long)blockIdx.x * ADAM_CHUNK;
+    if (base >= n) return;
+    const float* p = (const float*)job[0];
+    float* e = (float*)emap[blockIdx.y];
+    if ((n % 4 == 0) && ((job[0] | (int64_t)e) % 16 == 0)) {
+        f32x4 pq[4], eq[4];
+#pragma unroll
+        for (int it = 0; it < 4; ++it) {
+            const long i = base + (long)(it * 256 + threadIdx.x) * 4;
+            if (i < n) { pq[it] = *(const f32x4*)(p + i); eq[it] = *(const f32x4*)(e + i); }
+        }
+#pragma unroll
+        for (int it = 0; it < 4; ++it) {
+            const long i = base + (long)(it * 256 + threadIdx.x) * 4;
+            if (i >= n) break;
+            f32x4 ee = eq[it];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) ee[r] = ema_one(ee[r], pq[it][r], weight);
+            *(f32x4*)(e + i) = ee;
+        }
+    } else {
+        long end = base + ADAM_CHUNK;
+        end = end < n ? end : n;
+        for (long i = base + threadIdx.x; i < end; i += 256) {
+            e[i] = ema_one(e[i], p[i], weight);
+        }
+    }
+}
+
+// Exchanges job y's parameter and its average element for element (evaluation on the averaged weights and back: the pointers stay,
+// so job tables and captured graphs remain valid).  Same table columns, chunking, paths and load-before-store order as above.
+__global__ __launch_bounds__(256) void swap_multi_kernel(const int64_t* __restrict__ table, const int64_t* __restrict__ emap) {
+    const int64_t* job = table + (long)blockIdx.y * 6;
+    const long n = job[4];
+    const long base = (long)blockIdx.x * ADAM_CHUNK;
+    if (base >= n) return;
+    float* p = (float*)job[0];
+    float* e = (float*)emap[blockIdx.y];
+    if ((n % 4 == 0) && ((job[0] | (int64_t)e) % 16 == 0)) {
+        f32x4 pq[4], eq[4];
+#pragma unroll
+        for (int it = 0; it < 4; ++it) {
+            const long i = base + (long)(it * 256 + threadIdx.x) * 4;
+            if (i < n) { pq[it] = *(const f32x4*)(p + i); eq[it] = *(const f32x4*)(e + i); }
+        }
+#pragma unroll
+        for (int it = 0; it < 4; ++it) {
+            const long i = base + (long)(it * 256 + threadIdx.x) * 4;
+            if (i >= n) break;
+            *(f32x4*)(p + i) = eq[it];
+            *(f32x4*)(e + i) = pq[it];
+        }
+    } else {
+        long end = base + ADAM_CHUNK;
+        end = end < n ? end : n;
+        for (long i = base + threadIdx.x; i < end; i += 256) {
+            const float pp = p[i], ee = e[i];
+            p[i] = ee;
+            e[i] = pp;
+        }
+    }
+}
+
 }  // namespace
 
 static int adam_launch(const char* who, const int64_t* table_dev, const int64_t* dyn_dev, int64_t njobs, int64_t max_n, float lr,
@@ -333,5 +414,23 @@ extern "C" int aptai_grad_accum_multi(const int64_t* table_dev, const int64_t* d
     APTAI_LAUNCH(grad_accum_kernel, dim3((unsigned)ceil_div(max_n, ADAM_CHUNK), (unsigned)njobs), dim3(256), 0, (hipStream_t)stream,
                  table_dev, dyn_dev, acc_dev, scale);
     APTAI_CHECK_LAUNCH("grad_accum_kernel");
+    return APTAI_OK;
+}
+
+extern "C" int aptai_ema_multi(const int64_t* table_dev, const int64_t* ema_dev, int64_t njobs, int64_t max_n, float weight,
+                               void* stream) {
+    APTAI_REQUIRE(table_dev && ema_dev && njobs > 0 && njobs <= 65535 && max_n > 0, "aptai_ema_multi: bad arguments");
+    APTAI_REQUIRE(weight > 0.f && weight <= 1.f, "aptai_ema_multi: weight must lie in (0, 1] (1 - decay of this update)");
+    APTAI_LAUNCH(ema_multi_kernel, dim3((unsigned)ceil_div(max_n, ADAM_CHUNK), (unsigned)njobs), dim3(256), 0, (hipStream_t)stream,
+                 table_dev, ema_dev, weight);
+    APTAI_CHECK_LAUNCH("ema_multi_kernel");
+    return APTAI_OK;
+}
+
+extern "C" int aptai_swap_multi(const int64_t* table_dev, const int64_t* ema_dev, int64_t njobs, int64_t max_n, void* stream) {
+    APTAI_REQUIRE(table_dev && ema_dev && njobs > 0 && njobs <= 65535 && max_n > 0, "aptai_swap_multi: bad arguments");
+    APTAI_LAUNCH(swap_multi_kernel, dim3((unsigned)ceil_div(max_n, ADAM_CHUNK), (unsigned)njobs), dim3(256), 0, (hipStream_t)stream,
+                 table_dev, ema_dev);
+    APTAI_CHECK_LAUNCH("swap_multi_kernel");
     return APTAI_OK;
 }

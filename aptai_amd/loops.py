@@ -6,6 +6,7 @@ is called and what gets printed stay in each loop's own module.
 """
 from __future__ import annotations
 
+import contextlib
 import functools
 import pickle
 from pathlib import Path
@@ -33,7 +34,8 @@ def adam_and_schedule(params, args_cfg, publish_to=None):
     from .optim import Adam
     optimizer = Adam(params, lr=args_cfg.learning_rate, betas=(args_cfg.adam_beta1, args_cfg.adam_beta2), eps=args_cfg.adam_epsilon,
                      weight_decay=args_cfg.adam_weight_decay, max_grad_norm=getattr(args_cfg, "max_grad_norm", None),
-                     gradient_accumulation_steps=getattr(args_cfg, "gradient_accumulation_steps", 1))
+                     gradient_accumulation_steps=getattr(args_cfg, "gradient_accumulation_steps", 1),
+                     ema_decay=getattr(args_cfg, "ema_decay", None), ema_warmup=getattr(args_cfg, "ema_warmup", False))
     if publish_to is not None:
         optimizer.publish_to(publish_to)
     lr_scheduler = torch.optim.lr_scheduler.LambdaLR(
@@ -45,7 +47,8 @@ def default_cfg(overrides, **own):
     """The hyper-parameters all three loops take at the reference's argparse defaults, the loop's `own` ones, then `overrides`."""
     cfg = SimpleNamespace(device="cuda", num_epochs=2, adam_beta1=0.9, adam_beta2=0.999, adam_epsilon=1e-8, adam_weight_decay=0.0,
                           num_warmup_epochs=10, num_static_epochs=30, lr_decay=0.96, target_metric_bigger_better=False,
-                          device_metrics=False, batch_invariant_eval=False, source_rate=None, normalize_audio=False, **own)
+                          device_metrics=False, batch_invariant_eval=False, source_rate=None, normalize_audio=False, ema_decay=None,
+                          ema_warmup=False, **own)
     cfg.__dict__.update(overrides)
     return cfg
 
@@ -55,6 +58,11 @@ def add_shared_arguments(ap):
                     help="clip the gradients at this global 2-norm inside the optimiser step (off by default)")
     ap.add_argument("--gradient_accumulation_steps", type=int, default=1,
                     help="update once per this many batches, with the mean of their gradients (accumulated inside the optimiser; off by default)")
+    ap.add_argument("--ema_decay", type=float, default=None,
+                    help="keep an exponential moving average of the weights inside the optimiser step with this decay; validation and "
+                         "the best checkpoint then use the averaged weights (off by default)")
+    ap.add_argument("--ema_warmup", action="store_true",
+                    help="with --ema_decay: the k-th update uses min(ema_decay, (1 + k) / (10 + k))")
     ap.add_argument("--source_rate", type=int, default=None,
                     help="the corpus' sampling rate: the audio is uploaded at that rate and resampled to 16 kHz on the device")
     ap.add_argument("--normalize_audio", action="store_true", help="zero-mean / unit-variance normalisation on the device")
@@ -66,7 +74,8 @@ def add_shared_arguments(ap):
 def shared_arguments(a) -> dict:
     """The parsed flags of add_shared_arguments as default_cfg entries."""
     return dict(max_grad_norm=a.max_grad_norm, gradient_accumulation_steps=a.gradient_accumulation_steps, source_rate=a.source_rate,
-                normalize_audio=a.normalize_audio, batch_invariant_eval=a.batch_invariant_eval)
+                normalize_audio=a.normalize_audio, batch_invariant_eval=a.batch_invariant_eval, ema_decay=a.ema_decay,
+                ema_warmup=a.ema_warmup)
 
 
 def batch_invariant_eval(fn):
@@ -124,6 +133,8 @@ class EpochDriver:
         # cfg.gradient_accumulation_steps: every optimizer.step() below is one micro-step of a window (aptai_amd.optim.Adam); the loop
         # counts the updates, keeps the clip monitor to them and closes an unfinished window at the end of the epoch
         self.accumulate = getattr(cfg, "gradient_accumulation_steps", 1) > 1
+        # cfg.ema_decay: the optimiser averages the weights inside step(); validation and the best checkpoint see the averages
+        self.ema = getattr(cfg, "ema_decay", None) is not None and hasattr(optimizer, "ema_weights")
         self.sum_train_loss, self.steps, self.updates = 0.0, 0, 0
 
     def eager_step(self, forward):
@@ -162,7 +173,8 @@ class EpochDriver:
         """Schedule step, validation (`validate()` -> its dictionary), best checkpoint, the epoch's log dictionary (also appended
         to `history`).  A tie on cfg.target_metric counts as better and writes the checkpoint again.  `planned_steps`: the
         recogniser's fixed number of steps per epoch; the mean train loss divides by it and the log gains `trained_batches`.
-        `extra_checkpoints()`: further files, written after the best checkpoint."""
+        `extra_checkpoints()`: further files, written after the best checkpoint.  With cfg.ema_decay, validation and the best
+        checkpoint run on the AVERAGED weights (optimizer.ema_weights); `extra_checkpoints()` and the next epoch see the raw ones."""
         cfg, model = self.cfg, self.model
         if getattr(self.optimizer, "micro_step", 0) and self.optimizer.flush():        # a remainder of the epoch's last window
             self._updated()
@@ -170,13 +182,14 @@ class EpochDriver:
         if self.runner is not None:
             self.runner.suspend()        # the eager validation below rebuilds its weight copies; the captured buckets stay
         model.eval()
-        val_logs = validate()
-        better = (self.eval_target is None
-                  or (cfg.target_metric_bigger_better and self.eval_target <= val_logs[cfg.target_metric])
-                  or (not cfg.target_metric_bigger_better and self.eval_target >= val_logs[cfg.target_metric]))
-        if better:
-            self.eval_target = val_logs[cfg.target_metric]
-            save_checkpoint(model, self.best_ckpt_path)
+        with self.optimizer.ema_weights(model) if self.ema else contextlib.nullcontext():
+            val_logs = validate()
+            better = (self.eval_target is None
+                      or (cfg.target_metric_bigger_better and self.eval_target <= val_logs[cfg.target_metric])
+                      or (not cfg.target_metric_bigger_better and self.eval_target >= val_logs[cfg.target_metric]))
+            if better:
+                self.eval_target = val_logs[cfg.target_metric]
+                save_checkpoint(model, self.best_ckpt_path)
         if extra_checkpoints is not None:
             extra_checkpoints()
         divisor = self.steps if planned_steps is None else planned_steps
@@ -188,6 +201,8 @@ class EpochDriver:
             epoch_log["optimizer_updates"] = self.updates
         if self.clip is not None:
             epoch_log.update(self.clip.epoch_log())
+        if self.ema:
+            epoch_log["ema_updates"] = getattr(self.optimizer, "ema_updates", 0)
         self.history.append(epoch_log)
         self.sum_train_loss, self.steps, self.updates = 0.0, 0, 0
         return epoch_log

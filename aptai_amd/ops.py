@@ -648,6 +648,17 @@ def grad_accum_multi(table_ptr: int, dyn_ptr: int, acc_ptr: int, njobs: int, max
     _lib.call("aptai_grad_accum_multi", table_ptr, dyn_ptr, acc_ptr, njobs, max_n, float(scale), _stream() if stream is None else stream)
 
 
+def ema_multi(table_ptr: int, ema_ptr: int, njobs: int, max_n: int, weight: float, stream=None) -> None:
+    """Averages of the jobs += weight * (parameter - average) over Adam job tables given by address (aptai_ema_multi): three
+    rounded fp32 operations per element, the bits of torch's e + w * (p - e) on CPU tensors."""
+    _lib.call("aptai_ema_multi", table_ptr, ema_ptr, njobs, max_n, float(weight), _stream() if stream is None else stream)
+
+
+def swap_multi(table_ptr: int, ema_ptr: int, njobs: int, max_n: int, stream=None) -> None:
+    """Parameters and averages of the jobs exchanged in place (aptai_swap_multi); two calls are the identity."""
+    _lib.call("aptai_swap_multi", table_ptr, ema_ptr, njobs, max_n, _stream() if stream is None else stream)
+
+
 def conv_weight_bf16(w: torch.Tensor) -> torch.Tensor:
     """[N][C][Kw] fp32 -> [N][Kw*C] bf16."""
     _dev(w)

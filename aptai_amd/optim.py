@@ -15,9 +15,15 @@ it as it reads it.  ``.grad`` is NOT modified in this form: it still holds the u
 Gradient accumulation (the HF Trainer's ``gradient_accumulation_steps``) lives here too: ``Adam(..., gradient_accumulation_steps=N)``
 makes every ``step()`` one micro-step of a window of N.  The first N - 1 add the gradients into fp32 accumulators the optimiser owns
 (one streaming launch, nothing else moves); the N-th multiplies them by 1/N and hands the mean to the norm and Adam kernels above.
+
+An exponential moving average of the weights (``torch._foreach_lerp_(ema, params, 1 - decay)`` after every ``optimizer.step()``) is
+the last launch of an update: ``Adam(..., ema_decay=0.999)`` keeps one fp32 average per parameter, moves it once per update (not per
+micro-step of a window) and exchanges parameters and averages in place for evaluation (``with opt.ema_weights(model): ...``), telling
+the model that its derived weight copies are stale.
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import operator
 from typing import Dict, Optional
@@ -44,9 +50,23 @@ def _check_accum_steps(steps) -> int:
     return steps
 
 
+def _check_ema_decay(decay) -> float:
+    if isinstance(decay, bool) or not isinstance(decay, (int, float)) or not 0 <= decay < 1:       # also NaN
+        raise ValueError(f"ema_decay must be None or a float with 0 <= ema_decay < 1, got {decay!r}")
+    return float(decay)
+
+
+def ema_decay_at(k: int, decay: float, warmup: bool = False) -> float:
+    """Decay of the k-th averaged update, k = 1, 2, ...: `decay`, or with warm-up min(decay, (1 + k) / (10 + k)) - 2/11, 3/12, ...
+    until it reaches `decay` - so that the first updates are not averaged with the initial weights at full weight.  The kernel's
+    weight is (float)(1.0 - ema_decay_at(k, ...)), evaluated in double here."""
+    return min(decay, (1.0 + k) / (10.0 + k)) if warmup else decay
+
+
 class Adam(torch.optim.Optimizer):
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
-                 max_grad_norm: Optional[float] = None, gradient_accumulation_steps: int = 1):
+                 max_grad_norm: Optional[float] = None, gradient_accumulation_steps: int = 1, ema_decay: Optional[float] = None,
+                 ema_warmup: bool = False):
         if lr < 0 or eps < 0 or not (0 <= betas[0] < 1) or not (0 <= betas[1] < 1) or weight_decay < 0:
             raise ValueError("invalid Adam hyper-parameters")
         # an attribute, not a param_groups key (one norm spans all groups; state_dict() stays interchangeable with torch's)
@@ -54,6 +74,13 @@ class Adam(torch.optim.Optimizer):
         self._accum = None                          # accumulation: accumulators, pointer tables and the open window (_accum_tables)
         self.gradient_accumulation_steps = gradient_accumulation_steps      # an attribute as well: one window spans all groups
         self.last_step_updated = False              # did the last step() / flush() update the parameters (False inside a window)
+        self.ema_decay = ema_decay                  # attributes as well: one average spans all groups
+        self.ema_warmup = bool(ema_warmup)
+        self._ema = None                            # averaging: the averages by parameter and their pointer table (_ema_tables)
+        self._ema_updates = 0
+        self._ema_swapped = False                   # swap_ema(): the parameters hold the averages right now
+        self._pending_ema = None
+        self._models = []                           # publish_to(): the encoders whose weight copies follow these parameters
         super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay))
         self._copies: Dict[int, tuple] = {}         # id(param) -> (destination tensor, kind)
         self._tables: Dict[int, tuple] = {}         # group index -> (key, table tensor, max_n)
@@ -117,6 +144,118 @@ class Adam(torch.optim.Optimizer):
             return None
         return acc["views"][row]
 
+    # ------------------------------------------------------------------ exponential moving average of the weights
+    @property
+    def ema_decay(self) -> Optional[float]:
+        """None: no averaging, nothing is allocated or launched.  A value d in [0, 1): every step() / flush() that updates the
+        parameters ends with ONE launch that moves an fp32 average of every parameter of every group, ema += (1 - d_k) * (p - ema),
+        d_k = ema_decay_at(k, d, ema_warmup) for the k-th such update.  The averages start as a copy of the parameters at the first
+        step with averaging on; a parameter without a gradient in an update still averages.  May be reassigned between steps."""
+        return self._ema_decay
+
+    @ema_decay.setter
+    def ema_decay(self, value) -> None:
+        self._ema_decay = None if value is None else _check_ema_decay(value)
+
+    @property
+    def ema_updates(self) -> int:
+        """k: how many updates the averages have taken."""
+        return self._ema_updates
+
+    def ema_parameter(self, p) -> Optional[torch.Tensor]:
+        """The average of `p` (a view shaped like `p`, not synchronised); None when averaging is off, has not started, or `p` is not
+        updated on the device."""
+        if self._ema_decay is None or self._ema is None:
+            return None
+        return self._ema["views"].get(id(p))
+
+    def _ema_tables(self, span, ts):
+        """Averaging: one fp32 average per row of the span table (slices of ONE buffer, each 16-byte aligned so that the kernels take
+        their vector paths) and their device pointer table.  The averages are kept BY PARAMETER: a rebuilt span (publish_to,
+        load_state_dict) only rebuilds the pointer table; a parameter seen for the first time starts as a copy of itself."""
+        ema = self._ema
+        if ema is not None and ema["span"] is span:
+            return ema
+        views, bufs = ({}, []) if ema is None else (ema["views"], ema["bufs"])
+        params = [p for t, _ in ts for p in t["params"]]
+        fresh = [p for p in params if id(p) not in views]
+        if fresh:
+            offs, total = [], 0
+            for p in fresh:
+                offs.append(total)
+                total += (p.numel() + 3) // 4 * 4
+            buf = torch.empty(total, dtype=torch.float32, device=span["dev"])
+            for o, p in zip(offs, fresh):
+                views[id(p)] = buf[o:o + p.numel()].view(p.shape)
+                views[id(p)].copy_(p.detach())
+            bufs.append(buf)
+        ptrs = [views[id(p)].data_ptr() for p in params]
+        self._ema = dict(span=span, views=views, bufs=bufs, ptrs_dev=torch.tensor(ptrs, dtype=torch.int64).to(span["dev"]))
+        return self._ema
+
+    @torch.no_grad()
+    def _ema_ready(self):
+        """The averages and their pointer table over the current job tables (allocated and filled on first use), or None without
+        parameters on the device."""
+        ts = [(self._group_tables(gi, g), g) for gi, g in enumerate(self.param_groups) if any(p.is_cuda for p in g["params"])]
+        if not ts:
+            return None
+        return self._ema_tables(self._span_tables([t for t, _ in ts], clip=False), ts)
+
+    def ema_state_dict(self) -> dict:
+        """What a resumed run needs beside state_dict() (whose keys stay torch's): the settings, k and a copy of every average in
+        `param_groups` order (None for a parameter that has none)."""
+        ema = self._ema_ready() if self._ema_decay is not None else self._ema
+        views = {} if ema is None else ema["views"]
+        return dict(decay=self._ema_decay, warmup=self.ema_warmup, updates=self._ema_updates,
+                    ema=[views[id(p)].clone() if id(p) in views else None for g in self.param_groups for p in g["params"]])
+
+    @torch.no_grad()
+    def load_ema_state_dict(self, sd: dict) -> None:
+        params = [p for g in self.param_groups for p in g["params"]]
+        if len(sd["ema"]) != len(params):
+            raise ValueError(f"load_ema_state_dict: {len(sd['ema'])} averages for {len(params)} parameters")
+        self.ema_decay, self.ema_warmup, self._ema_updates = sd["decay"], bool(sd["warmup"]), int(sd["updates"])
+        ema = self._ema_ready() if self._ema_decay is not None else None
+        for p, t in zip(params, sd["ema"]):
+            if t is not None and ema is not None and id(p) in ema["views"]:
+                ema["views"][id(p)].copy_(t)
+
+    @torch.no_grad()
+    def swap_ema(self, model=None) -> None:
+        """Exchanges parameters and averages in place, one launch: pointers do not move, so job tables, captured graphs and
+        data-parallel buckets stay valid.  `model` (default: the models of publish_to()) is told that its weights moved
+        (Wav2Vec2Model.weights_moved): its eval-mode weight copies miss and the published bf16 copies are re-cast.  A second call
+        puts everything back, bit for bit.  Not while a window is open; step() refuses to run on the averages."""
+        if self._ema_decay is None:
+            raise RuntimeError("swap_ema() needs ema_decay: this optimiser keeps no averages")
+        if self.micro_step:
+            raise RuntimeError("swap_ema() inside an open accumulation window: flush() first")
+        ema = self._ema_ready()
+        if ema is not None:
+            span = ema["span"]
+            ops.swap_multi(span["table"].data_ptr(), ema["ptrs_dev"].data_ptr(), span["n"], span["max_n"])
+        self._ema_swapped = not self._ema_swapped
+        if model is None:
+            moved = self._models
+        else:
+            moved = [getattr(model, "wav2vec2", None) or getattr(getattr(model, "w2v2_pr", None), "wav2vec2", None) or model]
+        for w2v in moved:
+            if hasattr(w2v, "weights_moved"):       # a module without derived weight copies has nothing to be told
+                w2v.weights_moved()
+
+    @contextlib.contextmanager
+    def ema_weights(self, model=None):
+        """`with opt.ema_weights(model):` the model's parameters ARE the averages inside the block (validation, checkpoints) and the
+        training weights again behind it, also when the block raises.  Does not nest."""
+        if self._ema_swapped:
+            raise RuntimeError("ema_weights() does not nest: the parameters already hold the averages")
+        self.swap_ema(model)
+        try:
+            yield self
+        finally:
+            self.swap_ema(model)
+
     # ------------------------------------------------------------------ compute copies
     def publish_to(self, model) -> "Adam":
         """Refresh the wav2vec2 layer compute copies (ops.CastPlan destinations) inside the optimiser kernel."""
@@ -128,6 +267,7 @@ class Adam(torch.optim.Optimizer):
             if p is not None and p.numel() == dst.numel():
                 self._copies[id(p)] = (dst, 0 if dst.dtype == torch.bfloat16 else 1)
         self._plans.append(plan)
+        self._models.append(w2v)
         self._tables.clear()
         self._span = None
         self._accum = None
@@ -233,10 +373,12 @@ class Adam(torch.optim.Optimizer):
         final, on any stream ordered behind this call) before finish() updates the rest.  Every parameter's `.grad` must already
         be the tensor its gradient WILL be in (static gradient buffers): the kernel reads it only when it is launched."""
         stream = torch.cuda.current_stream()
-        early_ids = {id(p) for p in early}
         self._pending = []
         self._pending_clip = None
         self._pending_accum = None
+        self._prepare_ema()
+        # the averaging launch follows EVERY update of the step: with it on, every row goes to finish() and `early` is ignored, too
+        early_ids = set() if self._pending_ema is not None else {id(p) for p in early}
         if self._accum_steps > 1:
             # a window's mean does not exist before its last gradient does: every row goes to finish(), `early` is ignored
             return self._prepare_accum(stream, True)
@@ -279,6 +421,13 @@ class Adam(torch.optim.Optimizer):
             ev.record(stream)
             t["events"][slot] = ev
             self._pending.append((t, group, any_late))
+
+    def _prepare_ema(self) -> None:
+        """Averaging on: the averages exist (a copy of the parameters as they are BEFORE the first averaged update) and their pointer
+        table matches the job tables before finish() launches anything."""
+        if self._ema_swapped:
+            raise RuntimeError("the parameters hold their averages (swap_ema() / ema_weights()): swap back before the next step")
+        self._pending_ema = None if self._ema_decay is None else self._ema_ready()
 
     def _device_groups(self):
         """[(table, group)] of the groups with parameters on the device, after prepare()'s checks."""
@@ -394,7 +543,7 @@ class Adam(torch.optim.Optimizer):
         """Update `params` (named in prepare(early=...)) now, on `stream`: one launch per parameter group over the row range that
         spans them (rows in between that were not named `early` carry no gradient pointer in this plane and are skipped)."""
         stream = stream or torch.cuda.current_stream()
-        if self._pending_clip is not None or self._pending_accum is not None:
+        if self._pending_clip is not None or self._pending_accum is not None or self._pending_ema is not None:
             return
         ids = {id(p) for p in params}
         for t, group, _ in self._pending:
@@ -407,6 +556,7 @@ class Adam(torch.optim.Optimizer):
         """Update every parameter that has a gradient and was not named `early`."""
         stream = stream or torch.cuda.current_stream()
         self.last_step_updated = self._accum_steps == 1
+        applied = bool(self._pending)               # some parameter is updated by this call (inside a window: none)
         if self._pending_accum is not None:
             self._finish_accum(stream)
         elif self._pending_clip is not None:
@@ -429,6 +579,13 @@ class Adam(torch.optim.Optimizer):
         self._pending = []
         for plan in self._plans:                    # the copies of every parameter that had a gradient are fresh now;
             plan.optimizer_synced = True            # parameters without one did not move (nor did any inside a window)
+        ema, self._pending_ema = self._pending_ema, None
+        if ema is not None and applied and self._ema_decay is not None:
+            # ONE launch over the rows of all groups, behind every Adam launch of this call on the same stream
+            self._ema_updates += 1
+            span = ema["span"]
+            ops.ema_multi(span["table"].data_ptr(), ema["ptrs_dev"].data_ptr(), span["n"], span["max_n"],
+                          1.0 - ema_decay_at(self._ema_updates, self._ema_decay, self.ema_warmup), stream.cuda_stream)
 
     def _finish_accum(self, stream) -> None:
         """finish() with accumulation on: the accumulate launch and, when the micro-step closes the window, today's launches on the
@@ -464,6 +621,7 @@ class Adam(torch.optim.Optimizer):
             return False
         self._pending = []
         self._pending_clip = None
+        self._prepare_ema()
         self._prepare_accum(torch.cuda.current_stream(), False)
         self.finish()
         return True

@@ -96,6 +96,8 @@ def train(cfg, model, optimizer, lr_scheduler, vocab, train_dataloader, valid_da
             if not (all_ckpt_path / "model_cfg.pkl").exists():
                 pickle.dump(model.get_config(), open(all_ckpt_path / "model_cfg.pkl", "wb"))
         torch.save(optimizer.state_dict(), last_ckpt_path / "optimizer.pt")
+        if run.ema:                              # cfg.ema_decay: the averages a resumed run continues from
+            torch.save(optimizer.ema_state_dict(), last_ckpt_path / "ema.pt")
         torch.save({"last_epoch": cfg.num_epochs}, last_ckpt_path / "scheduler.pt")          # as written (:484)
         loops.save_checkpoint(model, last_ckpt_path)
 

@@ -689,6 +689,21 @@ class Wav2Vec2Model(nn.Module):
             plan.version = ver
             plan.after_training = bool(trainable) and not synced
 
+    def weights_moved(self) -> None:
+        """Something other than a training step rewrote the parameters in place (aptai_amd.optim.Adam.swap_ema: averaged weights
+        in, training weights back).  Every `_cached` copy misses in eval mode from here on, and the layer copies are re-cast NOW,
+        also when the optimiser publishes them (`optimizer_synced`) and when a graph runner froze the cache: a replayed step reads
+        them without asking."""
+        self._train_marker = getattr(self, "_train_marker", 0) + 1
+        if getattr(self, "_cache_mode", None) == "frozen":       # as BucketedGraphedStep.suspend(): the graphs keep their own copies
+            self._cache_mode = None
+            self._cache.clear()
+        plan = getattr(self, "_lplan", None)
+        if plan is not None and not plan.stale():
+            with torch.no_grad():
+                plan.run()
+            plan.version = None
+
     def _layer_weights(self, i: int):
         return self._layer_plan().entries[i], self._layer_params(i)
 

@@ -298,6 +298,18 @@ int aptai_scale_multi(const int64_t* table_dev, const int64_t* dyn_dev, int64_t 
  * replays.  Moves 12 B per parameter (8 B on a first contribution); the Adam launch moves 28 B. */
 int aptai_grad_accum_multi(const int64_t* table_dev, const int64_t* dyn_dev, const int64_t* acc_dev, int64_t njobs, int64_t max_n,
                            float scale, void* stream);
+/* Exponential moving average of the weights, one launch behind the Adam launches of an update, over the Adam job table above (only
+ * the parameter pointer, column 0, and n, column 4, are read; there is no per-step row, so a job without a gradient in this update
+ * still averages).  ema_dev: device int64 [njobs] = one fp32 average of n elements per job.  Per element
+ *   ema = __fadd_rn(ema, __fmul_rn(weight, __fsub_rn(p, ema)))
+ * - three rounded fp32 operations, no fused multiply-add: the bits of e + w * (p - e) evaluated with separate fp32 operations.
+ * weight = (float)(1 - decay of this update), in (0, 1] (NaN is refused).  The chunking of aptai_adam_multi, every load of a thread
+ * before its first store, no atomics; 16-byte vector path when n % 4 == 0 and both pointers are 16-byte aligned, scalar path
+ * otherwise.  Validates and launches only (no allocation, copy or synchronisation).  Moves 12 B per parameter. */
+int aptai_ema_multi(const int64_t* table_dev, const int64_t* ema_dev, int64_t njobs, int64_t max_n, float weight, void* stream);
+/* Exchanges every job's parameter and its average element for element (same tables, chunking and paths): evaluation on the averaged
+ * weights without moving a pointer.  Two calls are the identity, bit for bit.  Moves 16 B per parameter. */
+int aptai_swap_multi(const int64_t* table_dev, const int64_t* ema_dev, int64_t njobs, int64_t max_n, void* stream);
 /* nn.Conv1d weight [N][C][Kw] (HF:260-266) -> [N][Kw*C] bf16, K index = kw*C + c (channels-last frames) */
 int aptai_conv_weight_to_bf16(const float* src, void* dst, int64_t N, int64_t C, int64_t Kw, void* stream);
 /* positional conv (HF:329-356): weight_norm(dim=2) w = g*v/||v||_(0,1) ; v [H][H/groups][Kw], gain [Kw];
