@@ -42,6 +42,8 @@ ARGTYPES = {
     "aptai_frame_mask_fwd": [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _P],
     "aptai_frame_mask_bwd": [_P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _P],
     "aptai_frame_mask_bwd_workspace_bytes": [_I64, _I64, _I64],
+    "aptai_frame_feature_mask_fwd": [_P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _P],
+    "aptai_frame_feature_mask_bwd": [_P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _P],
     "aptai_colsum_bf16": [_P, _I64, _P, _P, _I64, _I64, _I, _P],
     "aptai_colsum_workspace_bytes": [_I64, _I64],
     "aptai_dropout_bf16": [_P, _P, _I64, _F, _U64, _P],

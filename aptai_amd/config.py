@@ -107,6 +107,15 @@ class W2V2Config:
             raise ValueError("conv_dim / conv_stride / conv_kernel must have equal length")
         if self.hidden_act != "gelu" or self.feat_extract_activation != "gelu":
             raise ValueError("only the exact-erf 'gelu' activation of the reference configs is built")
+        if not 0 <= self.mask_feature_prob <= 1:
+            raise ValueError(f"mask_feature_prob={self.mask_feature_prob} must lie in [0, 1]")
+        if self.mask_feature_prob > 0:
+            # HF `_compute_mask_indices` raises these on the first training forward; here they surface when the config is read
+            if self.mask_feature_length < 1:
+                raise ValueError("`mask_length` has to be bigger than 0.")
+            if self.mask_feature_length > self.hidden_size:
+                raise ValueError(f"`mask_length` has to be smaller than `sequence_length`, but got `mask_length`: "
+                                 f"{self.mask_feature_length} and `sequence_length`: {self.hidden_size}`")
 
     # canonical shapes -------------------------------------------------------
     @classmethod

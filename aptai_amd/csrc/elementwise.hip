@@ -264,9 +264,18 @@ __global__ __launch_bounds__(64) void spec_mask_kernel(const int* __restrict__ l
     }
 }
 
-// ---- frame masking: out = pad ? 0 : (spec ? embed : h)   (in place)
+// ---- frame masking: out = pad ? 0 : (feat ? 0 : (spec ? embed : h))   (in place)
+// FEAT: SpecAugment along the hidden axis (HF `_mask_hidden_states`, second half): feat [B][H] uint8, channels zeroed on every valid
+// frame of the row, applied after the time fill.  A thread's four mask bytes are one aligned 32-bit load (H % 4 == 0); the masks
+// below keep (0xffff) or clear (0) each bf16 half of the two packed words.  FEAT = false is the kernel as it was.
+__device__ __forceinline__ u32x2 feat_keep(uint32_t fm) {
+    return (u32x2){((fm & 0x000000ffu) ? 0u : 0x0000ffffu) | ((fm & 0x0000ff00u) ? 0u : 0xffff0000u),
+                   ((fm & 0x00ff0000u) ? 0u : 0x0000ffffu) | ((fm & 0xff000000u) ? 0u : 0xffff0000u)};
+}
+
+template <bool FEAT>
 __global__ void frame_mask_kernel(bf16_t* __restrict__ h, const int* __restrict__ lens, const uint8_t* __restrict__ spec,
-                                  const float* __restrict__ embed, int B, int Tp, int T, int H) {
+                                  const float* __restrict__ embed, const uint8_t* __restrict__ feat, int B, int Tp, int T, int H) {
     const long n4 = (long)B * Tp * H / 4;
     const long stride = (long)gridDim.x * blockDim.x;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
@@ -278,6 +287,20 @@ __global__ void frame_mask_kernel(bf16_t* __restrict__ h, const int* __restrict_
         len = len < T ? len : T;
         if (t >= len) {
             *(u32x2*)(h + e) = (u32x2){0u, 0u};
+        } else if (FEAT) {
+            const uint32_t fm = *(const uint32_t*)(feat + (long)b * H + col);
+            const bool sp = spec && spec[(long)b * T + t];
+            if (sp || fm) {
+                u32x2 p;
+                if (sp) {
+                    const f32x4 m = *(const f32x4*)(embed + col);
+                    p = (u32x2){pack2bf(m[0], m[1]), pack2bf(m[2], m[3])};
+                } else {
+                    p = *(const u32x2*)(h + e);
+                }
+                const u32x2 keep = feat_keep(fm);
+                *(u32x2*)(h + e) = (u32x2){p[0] & keep[0], p[1] & keep[1]};
+            }
         } else if (spec && spec[(long)b * T + t]) {
             const f32x4 m = *(const f32x4*)(embed + col);
             *(u32x2*)(h + e) = (u32x2){pack2bf(m[0], m[1]), pack2bf(m[2], m[3])};
@@ -285,10 +308,11 @@ __global__ void frame_mask_kernel(bf16_t* __restrict__ h, const int* __restrict_
     }
 }
 
-// backward: dh = (pad | spec) ? 0 : dy (in place); dembed partials over spec & !pad rows
+// backward: dh = (pad | spec | feat) ? 0 : dy (in place); dembed partials over spec & !pad rows, without the feat channels
+template <bool FEAT>
 __global__ void frame_mask_bwd_kernel(bf16_t* __restrict__ dy, const int* __restrict__ lens,
-                                      const uint8_t* __restrict__ spec, float* __restrict__ partials, int B, int Tp, int T,
-                                      int H, int rows_per_block) {
+                                      const uint8_t* __restrict__ spec, const uint8_t* __restrict__ feat,
+                                      float* __restrict__ partials, int B, int Tp, int T, int H, int rows_per_block) {
     // block handles rows [blockIdx.x*rpb, +rpb); thread handles 4 columns per pass
     const long rows = (long)B * Tp;
     const long r0 = (long)blockIdx.x * rows_per_block;
@@ -304,9 +328,20 @@ __global__ void frame_mask_bwd_kernel(bf16_t* __restrict__ dy, const int* __rest
             if (t >= len) {
                 *(u32x2*)(dy + e) = (u32x2){0u, 0u};
             } else if (spec && spec[(long)b * T + t]) {
-                const u32x2 p = *(const u32x2*)(dy + e);
+                u32x2 p = *(const u32x2*)(dy + e);
+                if (FEAT) {                                 // a feature-masked channel never saw the embed: no term, not a zero term
+                    const u32x2 keep = feat_keep(*(const uint32_t*)(feat + (long)b * H + c4 * 4));
+                    p = (u32x2){p[0] & keep[0], p[1] & keep[1]};
+                }
                 acc[0] += lo_bf(p[0]); acc[1] += hi_bf(p[0]); acc[2] += lo_bf(p[1]); acc[3] += hi_bf(p[1]);
                 *(u32x2*)(dy + e) = (u32x2){0u, 0u};
+            } else if (FEAT) {
+                const uint32_t fm = *(const uint32_t*)(feat + (long)b * H + c4 * 4);
+                if (fm) {
+                    const u32x2 keep = feat_keep(fm);
+                    const u32x2 p = *(const u32x2*)(dy + e);
+                    *(u32x2*)(dy + e) = (u32x2){p[0] & keep[0], p[1] & keep[1]};
+                }
             }
         }
         if (partials) *(f32x4*)(partials + (long)blockIdx.x * H + c4 * 4) = (f32x4){acc[0], acc[1], acc[2], acc[3]};
@@ -584,28 +619,48 @@ extern "C" int aptai_posconv_pack(const void* x, const void* u, void* xg, void* 
     return APTAI_OK;
 }
 
-extern "C" int aptai_frame_mask_fwd(void* h, const int32_t* lens, const uint8_t* spec_mask, const float* embed, int64_t B,
-                                    int64_t Tp, int64_t T, int64_t H, void* stream) {
-    APTAI_REQUIRE(h && lens && H % 4 == 0, "aptai_frame_mask_fwd: bad arguments");
-    APTAI_REQUIRE(!spec_mask || embed, "aptai_frame_mask_fwd: spec mask without masked_spec_embed");
-    APTAI_LAUNCH(frame_mask_kernel, dim3(grid_for(B * Tp * H / 4)), dim3(256), 0, (hipStream_t)stream, (bf16_t*)h, lens,
-                       spec_mask, embed, (int)B, (int)Tp, (int)T, (int)H);
+static int frame_mask_fwd_impl(const char* who, void* h, const int32_t* lens, const uint8_t* spec_mask, const float* embed,
+                               const uint8_t* feat_mask, int64_t B, int64_t Tp, int64_t T, int64_t H, void* stream) {
+    APTAI_REQUIRE(h && lens && H % 4 == 0, "%s: bad arguments", who);
+    APTAI_REQUIRE(!spec_mask || embed, "%s: spec mask without masked_spec_embed", who);
+    APTAI_REQUIRE((uintptr_t)feat_mask % 4 == 0, "%s: feat_mask must be 4-byte aligned", who);
+    const dim3 grid(grid_for(B * Tp * H / 4));
+    if (feat_mask)
+        APTAI_LAUNCH(frame_mask_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, (bf16_t*)h, lens, spec_mask, embed, feat_mask,
+                     (int)B, (int)Tp, (int)T, (int)H);
+    else
+        APTAI_LAUNCH(frame_mask_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, (bf16_t*)h, lens, spec_mask, embed, feat_mask,
+                     (int)B, (int)Tp, (int)T, (int)H);
     APTAI_CHECK_LAUNCH("frame_mask_kernel");
     return APTAI_OK;
+}
+extern "C" int aptai_frame_mask_fwd(void* h, const int32_t* lens, const uint8_t* spec_mask, const float* embed, int64_t B,
+                                    int64_t Tp, int64_t T, int64_t H, void* stream) {
+    return frame_mask_fwd_impl("aptai_frame_mask_fwd", h, lens, spec_mask, embed, nullptr, B, Tp, T, H, stream);
+}
+extern "C" int aptai_frame_feature_mask_fwd(void* h, const int32_t* lens, const uint8_t* spec_mask, const float* embed,
+                                            const uint8_t* feat_mask, int64_t B, int64_t Tp, int64_t T, int64_t H, void* stream) {
+    return frame_mask_fwd_impl("aptai_frame_feature_mask_fwd", h, lens, spec_mask, embed, feat_mask, B, Tp, T, H, stream);
 }
 
 static const int MASK_BWD_RPB = 32;
 extern "C" int64_t aptai_frame_mask_bwd_workspace_bytes(int64_t B, int64_t Tp, int64_t H) {
     return ceil_div(B * Tp, MASK_BWD_RPB) * H * 4;
 }
-extern "C" int aptai_frame_mask_bwd(void* dy, const int32_t* lens, const uint8_t* spec_mask, float* dembed, void* workspace,
-                                    int64_t B, int64_t Tp, int64_t T, int64_t H, void* stream) {
-    APTAI_REQUIRE(dy && lens && H % 4 == 0, "aptai_frame_mask_bwd: bad arguments");
+static int frame_mask_bwd_impl(const char* who, void* dy, const int32_t* lens, const uint8_t* spec_mask, const uint8_t* feat_mask,
+                               float* dembed, void* workspace, int64_t B, int64_t Tp, int64_t T, int64_t H, void* stream) {
+    APTAI_REQUIRE(dy && lens && H % 4 == 0, "%s: bad arguments", who);
+    APTAI_REQUIRE((uintptr_t)feat_mask % 4 == 0, "%s: feat_mask must be 4-byte aligned", who);
     const long blocks = ceil_div(B * Tp, MASK_BWD_RPB);
     const bool want = spec_mask && dembed;
-    APTAI_REQUIRE(!want || workspace, "aptai_frame_mask_bwd: workspace needed for dembed");
-    APTAI_LAUNCH(frame_mask_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (bf16_t*)dy, lens,
-                       spec_mask, want ? (float*)workspace : nullptr, (int)B, (int)Tp, (int)T, (int)H, MASK_BWD_RPB);
+    APTAI_REQUIRE(!want || workspace, "%s: workspace needed for dembed", who);
+    float* partials = want ? (float*)workspace : nullptr;
+    if (feat_mask)
+        APTAI_LAUNCH(frame_mask_bwd_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (bf16_t*)dy, lens,
+                     spec_mask, feat_mask, partials, (int)B, (int)Tp, (int)T, (int)H, MASK_BWD_RPB);
+    else
+        APTAI_LAUNCH(frame_mask_bwd_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (bf16_t*)dy, lens,
+                     spec_mask, feat_mask, partials, (int)B, (int)Tp, (int)T, (int)H, MASK_BWD_RPB);
     APTAI_CHECK_LAUNCH("frame_mask_bwd_kernel");
     if (want) {
         APTAI_LAUNCH(reduce_partials_kernel, dim3((unsigned)ceil_div(H, 64)), dim3(256), 0, (hipStream_t)stream,
@@ -613,6 +668,16 @@ extern "C" int aptai_frame_mask_bwd(void* dy, const int32_t* lens, const uint8_t
         APTAI_CHECK_LAUNCH("reduce_partials_kernel");
     }
     return APTAI_OK;
+}
+extern "C" int aptai_frame_mask_bwd(void* dy, const int32_t* lens, const uint8_t* spec_mask, float* dembed, void* workspace,
+                                    int64_t B, int64_t Tp, int64_t T, int64_t H, void* stream) {
+    return frame_mask_bwd_impl("aptai_frame_mask_bwd", dy, lens, spec_mask, nullptr, dembed, workspace, B, Tp, T, H, stream);
+}
+/* same workspace as aptai_frame_mask_bwd (aptai_frame_mask_bwd_workspace_bytes): the partial sums keep their layout and order */
+extern "C" int aptai_frame_feature_mask_bwd(void* dy, const int32_t* lens, const uint8_t* spec_mask, const uint8_t* feat_mask,
+                                            float* dembed, void* workspace, int64_t B, int64_t Tp, int64_t T, int64_t H,
+                                            void* stream) {
+    return frame_mask_bwd_impl("aptai_frame_feature_mask_bwd", dy, lens, spec_mask, feat_mask, dembed, workspace, B, Tp, T, H, stream);
 }
 
 static const int COLSUM_RPB = 128;

@@ -11,7 +11,8 @@ and replays them (~30 ``hipGraphLaunch`` per step).  Host-side randomness keeps 
  * LayerDrop (HF:701-703 / 774-776): a dropped layer's two graphs are simply not replayed (its activations / gradients are
    forwarded by one device copy) and its parameters get ``grad = None`` that step, exactly like eager;
  * SpecAugment (HF:101-217): the span mask is sampled by a kernel at the head of the front segment (ops.spec_augment_mask:
-   HF's span-count rule, fresh spans on every replay through the salted seed) - no host copy, no synchronisation;
+   HF's span-count rule, fresh spans on every replay through the salted seed) - no host copy, no synchronisation; with
+   ``mask_feature_prob > 0`` a second launch of the same sampler draws the mask along the hidden axis into ``runner.feat``;
  * dropout: kernels XOR a per-step device salt into their counter-RNG seeds (``aptai_set_seed_salt``), so every replay
    draws fresh masks while the forward and backward of one step regenerate identical ones.
 The optimiser step is issued eagerly after the last segment (aptai_amd.optim.Adam: one launch per parameter group; or any
@@ -31,7 +32,7 @@ import torch
 from . import _lib, hostlogic, ops
 from .aptai import APTAI, heads_bwd, heads_fwd
 from .w2v2_pr import Wav2Vec2_PR, pr_head_bwd, pr_head_fwd
-from .wav2vec2 import _FinalLNImpl, _FrontImpl, _LayerImpl, _seed
+from .wav2vec2 import _FEATURE_MASK_STREAM, _TIME_MASK_STREAM, _FinalLNImpl, _FrontImpl, _LayerImpl, _seed
 
 
 # thread-local capture: under data parallelism the process group's watchdog thread polls its events while this thread captures,
@@ -163,6 +164,13 @@ class GraphedAPTAIStep(_CapturingRunner):
         g = self.g
         self.lens_i32 = torch.zeros(B, device=dev, dtype=torch.int32)
         self.spec = torch.zeros((B, g.T), device=dev, dtype=torch.uint8)
+        # SpecAugment along the hidden axis (mask_feature_prob): a static [B][H] mask and the sampler's constant row lengths (= H);
+        # None, and nothing more captured, when it is off
+        self.feat = self.feat_lens = None
+        if cfg.apply_spec_augment and cfg.mask_feature_prob > 0:
+            ops.feature_mask_span_check(cfg.hidden_size, cfg.mask_feature_prob, cfg.mask_feature_length, cfg.mask_feature_min_masks)
+            self.feat = torch.zeros((B, cfg.hidden_size), device=dev, dtype=torch.uint8)
+            self.feat_lens = torch.full((B,), cfg.hidden_size, device=dev, dtype=torch.int32)
         if self.kind == "pr":
             self.labels = torch.full(tuple(batch["phoneme_labels"].shape), -100, device=dev, dtype=torch.int32)
             self.state_lens = torch.zeros(B, device=dev, dtype=torch.int32)
@@ -303,7 +311,8 @@ class GraphedAPTAIStep(_CapturingRunner):
 
         # -- front: conv stack (frozen) + projection + masking + positional conv (+ LN)
         embed = getattr(w, "masked_spec_embed", None)
-        self.front = _FrontImpl(cfg, g, self.lens_i32, self.spec if embed is not None else None, True, _seed(seed, 1), w)
+        self.front = _FrontImpl(cfg, g, self.lens_i32, self.spec if embed is not None else None, True, _seed(seed, 1), w,
+                                feat=self.feat)
         fp, pc = w.feature_projection, w.encoder.pos_conv_embed.conv
         self.fparams = [fp.layer_norm.weight, fp.layer_norm.bias, fp.projection.weight, fp.projection.bias, embed,
                         pc.parametrizations.weight.original0, pc.parametrizations.weight.original1, pc.bias,
@@ -312,7 +321,10 @@ class GraphedAPTAIStep(_CapturingRunner):
         with torch.cuda.graph(self.g_front, pool=pool, stream=self._cap_stream, capture_error_mode=_CAPTURE_MODE):
             if embed is not None and cfg.apply_spec_augment and cfg.mask_time_prob > 0:
                 ops.spec_augment_mask(self.lens_i32, g.B, g.T, cfg.mask_time_prob, cfg.mask_time_length, cfg.mask_time_min_masks,
-                                      _seed(seed, 77), out=self.spec)        # fresh spans on every replay (salted seed)
+                                      _seed(seed, _TIME_MASK_STREAM), out=self.spec)        # fresh spans on every replay (salted seed)
+            if self.feat is not None:                                        # a seed stream of its own: independent of the time mask
+                ops.spec_augment_mask(self.feat_lens, g.B, cfg.hidden_size, cfg.mask_feature_prob, cfg.mask_feature_length,
+                                      cfg.mask_feature_min_masks, _seed(seed, _FEATURE_MASK_STREAM), out=self.feat)
             feats, self.sv_conv = w._conv_forward(self.audio, g, save=self.train_conv)
             (h,), self.s_front = self.front.fwd(feats, self.fparams, True)
         self.X = [h]

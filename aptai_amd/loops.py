@@ -48,7 +48,7 @@ def default_cfg(overrides, **own):
     cfg = SimpleNamespace(device="cuda", num_epochs=2, adam_beta1=0.9, adam_beta2=0.999, adam_epsilon=1e-8, adam_weight_decay=0.0,
                           num_warmup_epochs=10, num_static_epochs=30, lr_decay=0.96, target_metric_bigger_better=False,
                           device_metrics=False, batch_invariant_eval=False, source_rate=None, normalize_audio=False, ema_decay=None,
-                          ema_warmup=False, **own)
+                          ema_warmup=False, mask_feature_prob=None, mask_feature_length=None, **own)
     cfg.__dict__.update(overrides)
     return cfg
 
@@ -63,6 +63,11 @@ def add_shared_arguments(ap):
                          "the best checkpoint then use the averaged weights (off by default)")
     ap.add_argument("--ema_warmup", action="store_true",
                     help="with --ema_decay: the k-th update uses min(ema_decay, (1 + k) / (10 + k))")
+    ap.add_argument("--mask_feature_prob", type=float, default=None,
+                    help="SpecAugment along the hidden axis: the share of channels that starts a masked span, per utterance and "
+                         "train step (default: the checkpoint's config value)")
+    ap.add_argument("--mask_feature_length", type=int, default=None,
+                    help="channels per span of --mask_feature_prob (default: the checkpoint's config value)")
     ap.add_argument("--source_rate", type=int, default=None,
                     help="the corpus' sampling rate: the audio is uploaded at that rate and resampled to 16 kHz on the device")
     ap.add_argument("--normalize_audio", action="store_true", help="zero-mean / unit-variance normalisation on the device")
@@ -75,7 +80,19 @@ def shared_arguments(a) -> dict:
     """The parsed flags of add_shared_arguments as default_cfg entries."""
     return dict(max_grad_norm=a.max_grad_norm, gradient_accumulation_steps=a.gradient_accumulation_steps, source_rate=a.source_rate,
                 normalize_audio=a.normalize_audio, batch_invariant_eval=a.batch_invariant_eval, ema_decay=a.ema_decay,
-                ema_warmup=a.ema_warmup)
+                ema_warmup=a.ema_warmup, mask_feature_prob=a.mask_feature_prob, mask_feature_length=a.mask_feature_length)
+
+
+def apply_mask_feature_arguments(w2v_cfg, a):
+    """--mask_feature_prob / --mask_feature_length onto a W2V2Config, in place: a flag that was not given (None) leaves the
+    checkpoint's value alone.  `a` is the parsed command line or a loop cfg.  The result is validated, so a length the hidden
+    axis cannot hold is refused before a model is built."""
+    for name in ("mask_feature_prob", "mask_feature_length"):
+        v = getattr(a, name, None)
+        if v is not None:
+            setattr(w2v_cfg, name, v)
+    w2v_cfg.validate()
+    return w2v_cfg
 
 
 def batch_invariant_eval(fn):

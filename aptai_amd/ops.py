@@ -745,6 +745,38 @@ def frame_mask_bwd(dy, lens_i32, spec_mask_u8, B, Tp, T, H, want_dembed):
     return dembed
 
 
+SPEC_MAX_SPANS = 256                         # csrc/elementwise.hip: spans per row of aptai_spec_augment_mask
+
+
+def feature_mask_span_check(H, mask_prob, mask_length, min_masks):
+    """The span sampler caps a row at SPEC_MAX_SPANS spans without a word; on the feature axis the count is known on the host
+    (every row has length H), so a setting it cannot honour is refused before anything is launched."""
+    most = max(int(mask_prob * H / mask_length + 1), int(min_masks))
+    if most > SPEC_MAX_SPANS:
+        raise ValueError(f"mask_feature_prob={mask_prob}, mask_feature_length={mask_length}, mask_feature_min_masks={min_masks} "
+                         f"ask for up to {most} spans over {H} channels; the device sampler draws at most {SPEC_MAX_SPANS} per row")
+
+
+def frame_feature_mask_fwd(h, lens_i32, spec_mask_u8, embed, feat_mask_u8, B, Tp, T, H):
+    """frame_mask_fwd plus SpecAugment along the hidden axis: feat_mask_u8 [B][H] uint8 (None = none), channels zeroed on every
+    valid frame after the time fill.  In place, one pass."""
+    _dev(h, lens_i32, spec_mask_u8, embed, feat_mask_u8)
+    _lib.call("aptai_frame_feature_mask_fwd", h.data_ptr(), lens_i32.data_ptr(), _ptr(spec_mask_u8), _ptr(embed), _ptr(feat_mask_u8),
+              B, Tp, T, H, _stream())
+
+
+def frame_feature_mask_bwd(dy, lens_i32, spec_mask_u8, feat_mask_u8, B, Tp, T, H, want_dembed):
+    """Backward of frame_feature_mask_fwd, in place on dy; returns dembed (None without a time mask or when not wanted)."""
+    _dev(dy, lens_i32, spec_mask_u8, feat_mask_u8)
+    dembed = ws = None
+    if want_dembed and spec_mask_u8 is not None:
+        dembed = torch.empty(H, device=dy.device, dtype=torch.float32)
+        ws = _ws(_lib.lib().aptai_frame_mask_bwd_workspace_bytes(B, Tp, H), dy.device)
+    _lib.call("aptai_frame_feature_mask_bwd", dy.data_ptr(), lens_i32.data_ptr(), _ptr(spec_mask_u8), _ptr(feat_mask_u8), _ptr(dembed),
+              _ptr(ws), B, Tp, T, H, _stream())
+    return dembed
+
+
 def colsum(x, rows, N, *, ld=None, out=None, accumulate=False):
     _dev(x, out)
     if out is None:

@@ -204,6 +204,7 @@ def main(argv=None):
     ap.add_argument("--out", default="aptai_ckpt")
     a = ap.parse_args(argv)
     w2v = W2V2Config.base(vocab_size=VOCAB_SIZE) if a.random_init == "base" else W2V2Config.large(vocab_size=VOCAB_SIZE)
+    loops.apply_mask_feature_arguments(w2v, a)
     with tempfile.TemporaryDirectory() as tmp:
         model_dir = a.model_dir
         if model_dir is None:

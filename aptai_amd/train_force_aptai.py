@@ -51,6 +51,9 @@ def load_model_optimizer(args_cfg):
     model = Force_APTAI(args_cfg.pr_model_path, args_cfg.device, args_cfg.vocab,
                         max_phn_seq_len=getattr(args_cfg, "max_phn_seq_len", 60)).to(args_cfg.device)
     model.transcript = getattr(args_cfg, "transcript", "decoded")
+    # --mask_feature_prob / --mask_feature_length land on the recogniser's config once its checkpoint is loaded (its parameter set
+    # follows the pickled config).  They are recorded, not used: the frozen recogniser runs in eval mode, so it is never masked.
+    loops.apply_mask_feature_arguments(model.w2v2_pr.wav2vec2.config, args_cfg)
     optimizer, lr_scheduler = loops.adam_and_schedule([p for p in model.parameters() if p.requires_grad], args_cfg)
     return model, optimizer, lr_scheduler
 

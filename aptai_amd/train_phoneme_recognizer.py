@@ -217,6 +217,7 @@ def main(argv=None):
     a = ap.parse_args(argv)
     vocab = default_vocab()
     w2v = W2V2Config.base() if a.random_init == "base" else W2V2Config.large()
+    loops.apply_mask_feature_arguments(w2v, a)
     with tempfile.TemporaryDirectory() as tmp:
         model_dir = a.model_dir
         if model_dir is None:

@@ -305,15 +305,35 @@ class _LayerImpl:
 
 
 _SPEC_ON_DEVICE = os.environ.get("APTAI_SPEC_ON_DEVICE", "1") != "0"      # =0: numpy sampler with HF's RNG order (host round trip)
+# seed streams of the device sampler, as ids of _seed(step seed, id): the two masks are drawn independently of each other
+_TIME_MASK_STREAM, _FEATURE_MASK_STREAM = 77, 78
+
+
+def _host_spec_masks(cfg, B, T, frame_lens, want_time, want_feat):
+    """The numpy sampler path (_SPEC_ON_DEVICE off): the time mask [B][T] over each row's valid frames (`frame_lens`, a host tensor, or
+    None for full rows), then the feature mask [B][H] with every row of length H - HF's order in `_mask_hidden_states`, so one
+    `np.random.seed` gives the reference's two masks.  Returns (time or None, feature or None), bool arrays."""
+    m_time = m_feat = None
+    if want_time:
+        am = None if frame_lens is None else (torch.arange(T)[None, :] < frame_lens[:, None])
+        m_time = hostlogic.compute_mask_indices((B, T), cfg.mask_time_prob, cfg.mask_time_length, attention_mask=am,
+                                                min_masks=cfg.mask_time_min_masks)
+    if want_feat:
+        m_feat = hostlogic.compute_mask_indices((B, cfg.hidden_size), cfg.mask_feature_prob, cfg.mask_feature_length,
+                                                min_masks=cfg.mask_feature_min_masks)
+    return m_time, m_feat
 
 
 # =================================================================================== front end of the encoder
 class _FrontImpl:
     """Feature projection (HF:422-434) -> SpecAugment fill + padded-frame zeroing (HF:1292-1295, 678-681) ->
-    h + GELU(grouped positional conv(h)) (HF:326-379, 689-692) -> [LayerNorm for post-LN models] -> dropout."""
+    h + GELU(grouped positional conv(h)) (HF:326-379, 689-692) -> [LayerNorm for post-LN models] -> dropout.
+    ``feat`` is the SpecAugment mask along the hidden axis ([B][H] uint8, HF `_mask_hidden_states`: `mask_feature_prob`), applied
+    in the same pass as the time fill; None launches the kernels of the time-only path."""
 
-    def __init__(self, cfg, geom, lens_i32, spec, training, seed, model):
+    def __init__(self, cfg, geom, lens_i32, spec, training, seed, model, feat=None):
         self.cfg, self.g, self.lens, self.spec, self.training, self.seed, self.model = cfg, geom, lens_i32, spec, training, seed, model
+        self.feat = feat
 
     def _packed(self, key, dev):
         cfg, g = self.cfg, self.g
@@ -341,7 +361,10 @@ class _FrontImpl:
         wp = self.model._cached(("proj",), [pw], lambda: ops.cast_bf16(pw))
         s.p_fp = cfg.feat_proj_dropout if tr else 0.0
         h0 = ops.gemm(s.n0, wp, M, H, C, bias=pb, dropout_p=s.p_fp, seed=_seed(self.seed, 11))
-        ops.frame_mask_fwd(h0, self.lens, self.spec, embed, g.B, g.Tp, g.T, H)
+        if self.feat is None:
+            ops.frame_mask_fwd(h0, self.lens, self.spec, embed, g.B, g.Tp, g.T, H)
+        else:
+            ops.frame_feature_mask_fwd(h0, self.lens, self.spec, embed, self.feat, g.B, g.Tp, g.T, H)
         s.h0 = h0
         # positional conv as ONE batched implicit GEMM over (utterance, group) on a zero-gapped group-major copy
         G, Kw = cfg.num_conv_pos_embedding_groups, cfg.num_conv_pos_embeddings
@@ -406,7 +429,10 @@ class _FrontImpl:
         dpcv, dgain = ops.posconv_weight_bwd(dwf, pcv.detach().contiguous(), pcg.detach().reshape(-1).contiguous(), s.norm, G)
         dpcg = dgain.reshape(pcg.shape)
         # ---- mask + projection + LN
-        dembed = ops.frame_mask_bwd(dh0, self.lens, self.spec, g.B, g.Tp, g.T, H, want_dembed=embed is not None)
+        if self.feat is None:
+            dembed = ops.frame_mask_bwd(dh0, self.lens, self.spec, g.B, g.Tp, g.T, H, want_dembed=embed is not None)
+        else:
+            dembed = ops.frame_feature_mask_bwd(dh0, self.lens, self.spec, self.feat, g.B, g.Tp, g.T, H, want_dembed=embed is not None)
         if s.p_fp > 0:
             dh0 = ops.dropout(dh0, s.p_fp, _seed(self.seed, 11))
         sk = max(1, min(8, M // 2048))
@@ -721,6 +747,13 @@ class Wav2Vec2Model(nn.Module):
         return cur
 
     # ------------------------------------------------------------------ geometry of one batch
+    def _feature_axis_lens(self, B: int, dev) -> torch.Tensor:
+        """[B] int32 filled with hidden_size: the row lengths of the span sampler on the feature axis (a cached constant)."""
+        c = getattr(self, "_feat_lens", None)
+        if c is None or c.shape[0] != B or c.device != dev:
+            c = self._feat_lens = torch.full((B,), self.config.hidden_size, device=dev, dtype=torch.int32)
+        return c
+
     def _geometry(self, B: int, S: int) -> SimpleNamespace:
         cfg = self.config
         Tl = hostlogic.conv_layer_lengths(S, cfg.conv_kernel, cfg.conv_stride)
@@ -1048,9 +1081,16 @@ class Wav2Vec2Model(nn.Module):
 
     # ------------------------------------------------------------------ forward
     def forward(self, input_values, attention_mask=None, mask_time_indices=None, output_attentions=None,
-                output_hidden_states=None, return_dict=None, **kw):
+                output_hidden_states=None, return_dict=None, mask_feature_indices=None, **kw):
         """HF:1319-1375.  ``attention_mask`` follows the reference's convention: the (B,1) tensor of sample
-        counts (models/aptai.py:77), or a regular (B,S) 0/1 mask; both reduce to lengths via a row sum (HF:1023)."""
+        counts (models/aptai.py:77), or a regular (B,S) 0/1 mask; both reduce to lengths via a row sum (HF:1023).
+
+        ``mask_feature_indices`` (bool / uint8 ``[B, hidden_size]``) is an explicit SpecAugment mask along the hidden axis, the
+        counterpart of ``mask_time_indices``: those channels are zeroed on every frame of the row, in train and eval mode alike
+        (and, like ``mask_time_indices``, not at all under ``apply_spec_augment = False``).  HF has no
+        such argument (it only samples the mask, in train mode, when ``mask_feature_prob > 0``, which this forward does as well);
+        it exists so that a run can be reproduced and tested.  The mask that was applied, sampled or given, is
+        ``out._feature_mask`` (a device uint8 ``[B, hidden_size]``, or None)."""
         cfg = self.config
         if not input_values.is_cuda:
             raise ops._lib.AptaiHipError("Wav2Vec2Model runs on the MI355X only (no CPU fallback)")
@@ -1070,6 +1110,20 @@ class Wav2Vec2Model(nn.Module):
                                           "not built); switch it off for input gradients")
         audio = input_values.float().contiguous()
         B, S = audio.shape
+        # SpecAugment along the hidden axis: refusals first, before anything is launched
+        feat = None
+        sample_feat = (mask_feature_indices is None and self.training and getattr(cfg, "apply_spec_augment", True)
+                       and cfg.mask_feature_prob > 0)
+        if mask_feature_indices is not None:
+            feat = torch.as_tensor(mask_feature_indices)
+            if feat.dim() != 2 or tuple(feat.shape) != (B, cfg.hidden_size):
+                raise ValueError(f"mask_feature_indices has shape {tuple(feat.shape)}, expected (batch, hidden_size) = "
+                                 f"{(B, cfg.hidden_size)}")
+        elif sample_feat:
+            if cfg.mask_feature_length < 1 or cfg.mask_feature_length > cfg.hidden_size:
+                raise ValueError(f"mask_feature_length={cfg.mask_feature_length} must lie in [1, hidden_size={cfg.hidden_size}]")
+            if _SPEC_ON_DEVICE:
+                ops.feature_mask_span_check(cfg.hidden_size, cfg.mask_feature_prob, cfg.mask_feature_length, cfg.mask_feature_min_masks)
         g = self._geometry(B, S)
         dev = audio.device
         if attention_mask is not None:
@@ -1096,7 +1150,7 @@ class Wav2Vec2Model(nn.Module):
 
         prec = getattr(self, "_encoder_precision", "bf16")
         if prec in ("f32x3", "f32x6") and not training and not torch.is_grad_enabled():
-            if mask_time_indices is not None:
+            if mask_time_indices is not None or mask_feature_indices is not None:
                 raise NotImplementedError("the exact inference pass takes no SpecAugment mask (eval mode never samples one)")
             h32, hidden32 = self._forward_exact(audio, g, lens_i32, 3 if prec == "f32x3" else 6, output_hidden_states)
             hb = h32.to(torch.bfloat16)
@@ -1104,10 +1158,12 @@ class Wav2Vec2Model(nn.Module):
                                           hidden_states=tuple(t.view(B, g.Tp, -1)[:, :g.T] for t in hidden32) if output_hidden_states else None,
                                           attentions=None)
             out._geom, out._frame_lens, out._flat_last, out._flat_last_f32, out._features = g, frame_lens, hb, h32, None
+            out._feature_mask = None
             return out
         feats = self._feature_encoder(audio, g)                                         # [M][512] bf16
         # ---- feature projection + SpecAugment + padded-frame zeroing (HF:429-434, 1272-1316, 678-681)
         spec = None
+        host_time = False
         if getattr(cfg, "apply_spec_augment", True):
             if mask_time_indices is not None:
                 spec = torch.as_tensor(mask_time_indices).to(dev).to(torch.uint8).contiguous()
@@ -1116,17 +1172,32 @@ class Wav2Vec2Model(nn.Module):
                     # sampled by a kernel from the device-resident lengths: no device->host copy (a 2.3 ms stall of the eager
                     # loop per step).  Same rule as HF `_compute_mask_indices`, counter-hash draws instead of numpy's.
                     spec = ops.spec_augment_mask(lens_i32, B, g.T, cfg.mask_time_prob, cfg.mask_time_length, cfg.mask_time_min_masks,
-                                                 _seed(seed, 77))
+                                                 _seed(seed, _TIME_MASK_STREAM))
                 else:
-                    am = None
-                    if attention_mask is not None:
-                        am = (torch.arange(g.T)[None, :] < frame_lens.cpu()[:, None])
-                    m = hostlogic.compute_mask_indices((B, g.T), cfg.mask_time_prob, cfg.mask_time_length, attention_mask=am,
-                                                       min_masks=cfg.mask_time_min_masks)
-                    spec = torch.from_numpy(m.astype(np.uint8)).to(dev)
+                    host_time = True
+        # along the hidden axis (HF `_mask_hidden_states`, second half): spans over the H channels of each row, every row of length H,
+        # drawn after the time mask (HF's RNG order on the host path) from a seed stream of its own on the device
+        H = cfg.hidden_size
+        if feat is not None and not getattr(cfg, "apply_spec_augment", True):
+            feat = None                                  # as mask_time_indices: HF `_mask_hidden_states` returns early
+        if feat is not None:
+            feat = feat.to(dev).to(torch.uint8).contiguous()
+            if feat.data_ptr() % 4:
+                feat = feat.clone()
+        elif sample_feat and _SPEC_ON_DEVICE:
+            feat = ops.spec_augment_mask(self._feature_axis_lens(B, dev), B, H, cfg.mask_feature_prob, cfg.mask_feature_length,
+                                         cfg.mask_feature_min_masks, _seed(seed, _FEATURE_MASK_STREAM))
+        host_feat = sample_feat and not _SPEC_ON_DEVICE
+        if host_time or host_feat:
+            m_time, m_feat = _host_spec_masks(cfg, B, g.T, frame_lens.cpu() if attention_mask is not None else None, host_time,
+                                              host_feat)
+            if host_time:
+                spec = torch.from_numpy(m_time.astype(np.uint8)).to(dev)
+            if host_feat:
+                feat = torch.from_numpy(m_feat.astype(np.uint8)).to(dev)
         fp = self.feature_projection
         embed = getattr(self, "masked_spec_embed", None)
-        front = _FrontImpl(cfg, g, lens_i32, spec, training, seed, self)
+        front = _FrontImpl(cfg, g, lens_i32, spec, training, seed, self, feat=feat)
         pc = self.encoder.pos_conv_embed.conv
         fparams = [fp.layer_norm.weight, fp.layer_norm.bias, fp.projection.weight, fp.projection.bias,
                    embed if (embed is not None and spec is not None) else None,
@@ -1157,6 +1228,7 @@ class Wav2Vec2Model(nn.Module):
                                           hidden_states=tuple(t.view(B, g.Tp, -1)[:, :g.T] for t in hidden) if output_hidden_states else None,
                                           attentions=tuple(attn) if want_attn else None)
             out._geom, out._frame_lens, out._flat_last, out._flat_last_f32 = g, frame_lens, h, h32
+            out._feature_mask = feat
             return out
         for i, layer in enumerate(self.encoder.layers):
             hidden.append(h)
@@ -1190,6 +1262,7 @@ class Wav2Vec2Model(nn.Module):
             hidden_states=tuple(view(t) for t in hidden) if output_hidden_states else None,
             attentions=tuple(attn) if want_attn else None)
         out._geom = g
+        out._feature_mask = feat
         out._frame_lens = frame_lens
         out._flat_last = h
         out._features = feats

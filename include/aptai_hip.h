@@ -351,6 +351,16 @@ int aptai_frame_mask_fwd(void* h, const int32_t* lens, const uint8_t* spec_mask,
 int aptai_frame_mask_bwd(void* dy, const int32_t* lens, const uint8_t* spec_mask, float* dembed, void* workspace, int64_t B,
                          int64_t Tp, int64_t T, int64_t H, void* stream);
 int64_t aptai_frame_mask_bwd_workspace_bytes(int64_t B, int64_t Tp, int64_t H);
+/* The same pass with SpecAugment along the hidden axis (HF `_mask_hidden_states`, `mask_feature_prob`): feat_mask uint8 [B][H],
+ * 4-byte aligned, null = none.  Forward, after the time fill: h[b][t][c] = 0 on every valid frame t where feat_mask[b][c] != 0, so
+ * a masked channel is zero on time-masked frames too.  Backward: dy is zeroed on padding, on time-masked frames and on
+ * feature-masked channels; dembed[c] sums dy over the valid, time-masked rows whose feat_mask[b][c] is 0 (fixed order, no
+ * atomics; workspace as aptai_frame_mask_bwd_workspace_bytes).  A feature mask without a time mask is legal (embed / dembed
+ * null); a spec_mask without embed, a null h or lens and H % 4 != 0 are refused before any launch.  One pass over h / dy. */
+int aptai_frame_feature_mask_fwd(void* h, const int32_t* lens, const uint8_t* spec_mask, const float* embed,
+                                 const uint8_t* feat_mask, int64_t B, int64_t Tp, int64_t T, int64_t H, void* stream);
+int aptai_frame_feature_mask_bwd(void* dy, const int32_t* lens, const uint8_t* spec_mask, const uint8_t* feat_mask, float* dembed,
+                                 void* workspace, int64_t B, int64_t Tp, int64_t T, int64_t H, void* stream);
 
 /* out[n] (+)= sum_rows x[row][n]  — bias gradients */
 int aptai_colsum_bf16(const void* x, int64_t ld, float* out, void* workspace, int64_t rows, int64_t N, int accumulate,
