@@ -17,7 +17,7 @@ and replays them (~30 ``hipGraphLaunch`` per step).  Host-side randomness keeps 
    draws fresh masks while the forward and backward of one step regenerate identical ones.
 The optimiser step is issued eagerly after the last segment (aptai_amd.optim.Adam: one launch per parameter group; or any
 torch optimiser).  Nothing in a step synchronises host and device: the host words a step sends (salt, frame bounds, a host
-batch) travel through ``_PinnedRing``.  ``_CapturingRunner`` holds what this runner shares with ``GraphedForceStep``: capture
+batch) travel through ``ops.PinnedRing``.  ``_CapturingRunner`` holds what this runner shares with ``GraphedForceStep``: capture
 stream, salt and its binding, and the way back to the eager loop.
 """
 from __future__ import annotations
@@ -65,36 +65,6 @@ def _bind_bounds(stream_handle: int, bounds: torch.Tensor) -> None:
     _lib.call("aptai_set_frame_bounds", stream_handle, bounds.data_ptr())
 
 
-class _PinnedRing:
-    """`slots` sets of pinned host buffers, one buffer per device tensor in `dst`, that take turns carrying a value to the device:
-    a pageable host-to-device copy would block the host until the GPU has drained, and one pinned buffer could be refilled while
-    its copy is still in flight.  The only wait is for the copy that last read the slot being handed out."""
-
-    def __init__(self, dst, slots: int):
-        self.dst = tuple(dst)
-        self.host = [tuple(torch.empty(t.shape, dtype=t.dtype).pin_memory() for t in self.dst) for _ in range(slots)]
-        self.views = [tuple(t.numpy() for t in bufs) for bufs in self.host]       # numpy views of the pinned buffers
-        self.events: List[Optional[torch.cuda.Event]] = [None] * slots
-        self.turn = 0
-
-    def next(self):
-        """The numpy views of the next slot, to be filled and then sent with send()."""
-        ev = self.events[self.turn]
-        if ev is not None:
-            ev.synchronize()                                    # the copies that last read this slot have finished
-        return self.views[self.turn]
-
-    def send(self) -> None:
-        """Asynchronous copies of the slot next() handed out into the device tensors, on the current stream."""
-        slot = self.turn
-        self.turn = (slot + 1) % len(self.host)
-        for d, h in zip(self.dst, self.host[slot]):
-            d.copy_(h, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        self.events[slot] = ev
-
-
 class _CapturingRunner:
     """What the two capturing runners share: the capture stream, the per-step dropout salt bound to it, and the way back."""
 
@@ -103,7 +73,7 @@ class _CapturingRunner:
         # (include/aptai_hip.h: no process-global state); the module-level registry keeps the two words alive until the binding
         # is cleared, whatever happens to the runner object
         self.salt = torch.zeros(2, device=dev, dtype=torch.int32)
-        self._salt_ring = _PinnedRing((self.salt,), 4)
+        self._salt_ring = ops.PinnedRing((self.salt,), 4)
         self._salt_gen = np.random.RandomState(salt_seed)
         self._cap_stream = torch.cuda.Stream(device=dev)
         _bind_salt(self._cap_stream.cuda_stream, self.salt)
@@ -181,7 +151,7 @@ class GraphedAPTAIStep(_CapturingRunner):
         self._init_capture(dev, 0xC0FFEE + w.base_seed)
         # frame bounds of the batch inside the captured shape (BucketedGraphedStep feeds shorter batches): by default the shape itself
         self.bounds = torch.tensor([g.Tl[0], g.T], device=dev, dtype=torch.int32)
-        self._bounds_ring = _PinnedRing((self.bounds,), 4)
+        self._bounds_ring = ops.PinnedRing((self.bounds,), 4)
         self._bounds_host = (g.Tl[0], g.T)
         self._stage_ring = None                                  # pinned staging of host batches: made on the first one (set_batch)
         _bind_bounds(self._cap_stream.cuda_stream, self.bounds)
@@ -215,7 +185,7 @@ class GraphedAPTAIStep(_CapturingRunner):
             # staging copies through numpy: single-threaded memcpy / cast.  torch's copy_ goes parallel above 32 K elements
             # and the OpenMP workers then spin on the cores the launching thread needs (host time per step 8 -> 19 ms).
             if self._stage_ring is None:
-                self._stage_ring = _PinnedRing((self.audio, self.lens_i32, self.tv_tgt, self.phn_tgt), 2)
+                self._stage_ring = ops.PinnedRing((self.audio, self.lens_i32, self.tv_tgt, self.phn_tgt), 2)
             audio, lens, tv, phn = self._stage_ring.next()
             np.copyto(audio, batch["audio_inputs"].detach().numpy(), casting="same_kind")
             np.copyto(lens, fl.numpy(), casting="same_kind")

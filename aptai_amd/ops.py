@@ -612,6 +612,36 @@ class CastPlan:
         _lib.call("aptai_cast_multi", self.table.data_ptr(), len(self.jobs), self.max_n, _stream())
 
 
+class PinnedRing:
+    """`slots` sets of pinned host buffers, one buffer per device tensor in `dst`, that take turns carrying a value to the device:
+    a pageable host-to-device copy would block the host until the GPU has drained, and one pinned buffer could be refilled while
+    its copy is still in flight.  The only wait is for the copy that last read the slot being handed out."""
+
+    def __init__(self, dst, slots: int):
+        self.dst = tuple(dst)
+        self.host = [tuple(torch.empty(t.shape, dtype=t.dtype).pin_memory() for t in self.dst) for _ in range(slots)]
+        self.views = [tuple(t.numpy() for t in bufs) for bufs in self.host]       # numpy views of the pinned buffers
+        self.events = [None] * slots
+        self.turn = 0
+
+    def next(self):
+        """The numpy views of the next slot, to be filled and then sent with send()."""
+        ev = self.events[self.turn]
+        if ev is not None:
+            ev.synchronize()                                    # the copies that last read this slot have finished
+        return self.views[self.turn]
+
+    def send(self) -> None:
+        """Asynchronous copies of the slot next() handed out into the device tensors, on the current stream."""
+        slot = self.turn
+        self.turn = (slot + 1) % len(self.host)
+        for d, h in zip(self.dst, self.host[slot]):
+            d.copy_(h, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self.events[slot] = ev
+
+
 GRAD_NORM_CHUNK = 4096      # elements per partial sum of grad_sqnorm_multi (ADAM_CHUNK of csrc/optim.hip)
 
 

@@ -26,6 +26,7 @@ from __future__ import annotations
 import contextlib
 import math
 import operator
+from types import SimpleNamespace
 from typing import Dict, Optional
 
 import torch
@@ -63,6 +64,36 @@ def ema_decay_at(k: int, decay: float, warmup: bool = False) -> float:
     return min(decay, (1.0 + k) / (10.0 + k)) if warmup else decay
 
 
+# Bytes per row of the two tables every launch takes by address (AdamArgs in csrc/optim.hip): `table` rows of six int64
+# {param, exp_avg, exp_avg_sq, copy_dst, n, copy_kind}, `dyn` rows of two {pointer, step count or mode}.
+_TABLE_ROW, _DYN_ROW = 48, 16
+
+
+def _addr(t, plane: int, r0: int = 0):
+    """(job table address, per-call row address) of row `r0` of the job table `t`, the rows in `plane` of its row buffer."""
+    return t.table_ptr + r0 * _TABLE_ROW, t.rows_ptr + (plane * t.n + r0) * _DYN_ROW
+
+
+def _updatable(p) -> bool:
+    return p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()
+
+
+def _packed_fp32(params, dev) -> list:
+    """One fp32 view shaped like each of `params`: slices of ONE new buffer, each 16-byte aligned so that the kernels take their
+    vector paths."""
+    offs, total = [], 0
+    for p in params:
+        offs.append(total)
+        total += (p.numel() + 3) // 4 * 4
+    buf = torch.empty(total, dtype=torch.float32, device=dev)
+    return [buf[o:o + p.numel()].view(p.shape) for o, p in zip(offs, params)]
+
+
+def _encoder_of(model):
+    """The wav2vec2 encoder behind an APTAI / Wav2Vec2_PR / Force_APTAI model, or the model itself."""
+    return getattr(model, "wav2vec2", None) or getattr(getattr(model, "w2v2_pr", None), "wav2vec2", None) or model
+
+
 class Adam(torch.optim.Optimizer):
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
                  max_grad_norm: Optional[float] = None, gradient_accumulation_steps: int = 1, ema_decay: Optional[float] = None,
@@ -71,7 +102,7 @@ class Adam(torch.optim.Optimizer):
             raise ValueError("invalid Adam hyper-parameters")
         # an attribute, not a param_groups key (one norm spans all groups; state_dict() stays interchangeable with torch's)
         self.max_grad_norm = max_grad_norm
-        self._accum = None                          # accumulation: accumulators, pointer tables and the open window (_accum_tables)
+        self._accum = None                          # accumulation: accumulators, their pointer table and the open window (_accumulators)
         self.gradient_accumulation_steps = gradient_accumulation_steps      # an attribute as well: one window spans all groups
         self.last_step_updated = False              # did the last step() / flush() update the parameters (False inside a window)
         self.ema_decay = ema_decay                  # attributes as well: one average spans all groups
@@ -79,16 +110,13 @@ class Adam(torch.optim.Optimizer):
         self._ema = None                            # averaging: the averages by parameter and their pointer table (_ema_tables)
         self._ema_updates = 0
         self._ema_swapped = False                   # swap_ema(): the parameters hold the averages right now
-        self._pending_ema = None
         self._models = []                           # publish_to(): the encoders whose weight copies follow these parameters
         super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay))
         self._copies: Dict[int, tuple] = {}         # id(param) -> (destination tensor, kind)
-        self._tables: Dict[int, tuple] = {}         # group index -> (key, table tensor, max_n)
         self._plans = []
-        self._span = None                           # clipping: one job table over every group (_span_tables)
+        self._table = None                          # the job table over every group, its per-call rows and their ring (_job_table)
         self._clip_result = None                    # clipping: device fp32 {total norm, coefficient, gradient elements}
-        self._pending_clip = None
-        self._pending_accum = None
+        self._pending = None                        # what prepare() decided, for launch_early() and finish()
 
     # ------------------------------------------------------------------ global-norm clipping
     @property
@@ -130,7 +158,7 @@ class Adam(torch.optim.Optimizer):
     @property
     def micro_step(self) -> int:
         """Micro-steps the open window holds so far; 0 after an update (and always at gradient_accumulation_steps=1)."""
-        return 0 if self._accum is None else self._accum["k"]
+        return 0 if self._accum is None else self._accum.k
 
     def accumulated_grad(self, p) -> Optional[torch.Tensor]:
         """The fp32 accumulator of `p` (a view shaped like `p`, not synchronised): the sum over the open window so far or, with no
@@ -139,10 +167,21 @@ class Adam(torch.optim.Optimizer):
         acc = self._accum
         if acc is None:
             return None
-        row = acc["rows"].get(id(p))
-        if row is None or not (acc["seen"] if acc["k"] else acc["applied"])[row]:
+        row = acc.table.row_of.get(id(p))
+        if row is None or not (acc.seen if acc.k else acc.applied)[row]:
             return None
-        return acc["views"][row]
+        return acc.views[row]
+
+    def _accumulators(self, t):
+        """Accumulation: one fp32 accumulator per row of the job table and their device pointer table, allocated when the first
+        window opens.  A rebuilt job table (publish_to, load_state_dict) discards the open window with the old accumulators."""
+        acc = self._accum
+        if acc is None or acc.table is not t:
+            views = _packed_fp32(t.params, t.dev)
+            ptrs = [v.data_ptr() for v in views]
+            acc = self._accum = SimpleNamespace(table=t, views=views, ptrs=ptrs, ptrs_dev=torch.tensor(ptrs, dtype=torch.int64).to(t.dev),
+                                                seen=[False] * t.n, applied=[False] * t.n, k=0)
+        return acc
 
     # ------------------------------------------------------------------ exponential moving average of the weights
     @property
@@ -167,46 +206,31 @@ class Adam(torch.optim.Optimizer):
         updated on the device."""
         if self._ema_decay is None or self._ema is None:
             return None
-        return self._ema["views"].get(id(p))
-
-    def _ema_tables(self, span, ts):
-        """Averaging: one fp32 average per row of the span table (slices of ONE buffer, each 16-byte aligned so that the kernels take
-        their vector paths) and their device pointer table.  The averages are kept BY PARAMETER: a rebuilt span (publish_to,
-        load_state_dict) only rebuilds the pointer table; a parameter seen for the first time starts as a copy of itself."""
-        ema = self._ema
-        if ema is not None and ema["span"] is span:
-            return ema
-        views, bufs = ({}, []) if ema is None else (ema["views"], ema["bufs"])
-        params = [p for t, _ in ts for p in t["params"]]
-        fresh = [p for p in params if id(p) not in views]
-        if fresh:
-            offs, total = [], 0
-            for p in fresh:
-                offs.append(total)
-                total += (p.numel() + 3) // 4 * 4
-            buf = torch.empty(total, dtype=torch.float32, device=span["dev"])
-            for o, p in zip(offs, fresh):
-                views[id(p)] = buf[o:o + p.numel()].view(p.shape)
-                views[id(p)].copy_(p.detach())
-            bufs.append(buf)
-        ptrs = [views[id(p)].data_ptr() for p in params]
-        self._ema = dict(span=span, views=views, bufs=bufs, ptrs_dev=torch.tensor(ptrs, dtype=torch.int64).to(span["dev"]))
-        return self._ema
+        return self._ema.views.get(id(p))
 
     @torch.no_grad()
-    def _ema_ready(self):
-        """The averages and their pointer table over the current job tables (allocated and filled on first use), or None without
-        parameters on the device."""
-        ts = [(self._group_tables(gi, g), g) for gi, g in enumerate(self.param_groups) if any(p.is_cuda for p in g["params"])]
-        if not ts:
+    def _ema_tables(self):
+        """Averaging: one fp32 average per row of the current job table and their device pointer table (allocated and filled on
+        first use), or None without parameters on the device.  The averages are kept BY PARAMETER: a rebuilt job table (publish_to,
+        load_state_dict) only rebuilds the pointer table; a parameter seen for the first time starts as a copy of itself."""
+        t = self._job_table()
+        if t.n == 0:
             return None
-        return self._ema_tables(self._span_tables([t for t, _ in ts], clip=False), ts)
+        ema = self._ema
+        if ema is None or ema.table is not t:
+            views = {} if ema is None else ema.views
+            fresh = [p for p in t.params if id(p) not in views]
+            for p, v in zip(fresh, _packed_fp32(fresh, t.dev)):
+                views[id(p)] = v.copy_(p.detach())
+            ptrs = [views[id(p)].data_ptr() for p in t.params]
+            ema = self._ema = SimpleNamespace(table=t, views=views, ptrs_dev=torch.tensor(ptrs, dtype=torch.int64).to(t.dev))
+        return ema
 
     def ema_state_dict(self) -> dict:
         """What a resumed run needs beside state_dict() (whose keys stay torch's): the settings, k and a copy of every average in
         `param_groups` order (None for a parameter that has none)."""
-        ema = self._ema_ready() if self._ema_decay is not None else self._ema
-        views = {} if ema is None else ema["views"]
+        ema = self._ema_tables() if self._ema_decay is not None else self._ema
+        views = {} if ema is None else ema.views
         return dict(decay=self._ema_decay, warmup=self.ema_warmup, updates=self._ema_updates,
                     ema=[views[id(p)].clone() if id(p) in views else None for g in self.param_groups for p in g["params"]])
 
@@ -216,10 +240,10 @@ class Adam(torch.optim.Optimizer):
         if len(sd["ema"]) != len(params):
             raise ValueError(f"load_ema_state_dict: {len(sd['ema'])} averages for {len(params)} parameters")
         self.ema_decay, self.ema_warmup, self._ema_updates = sd["decay"], bool(sd["warmup"]), int(sd["updates"])
-        ema = self._ema_ready() if self._ema_decay is not None else None
+        ema = self._ema_tables() if self._ema_decay is not None else None
         for p, t in zip(params, sd["ema"]):
-            if t is not None and ema is not None and id(p) in ema["views"]:
-                ema["views"][id(p)].copy_(t)
+            if t is not None and ema is not None and id(p) in ema.views:
+                ema.views[id(p)].copy_(t)
 
     @torch.no_grad()
     def swap_ema(self, model=None) -> None:
@@ -231,16 +255,12 @@ class Adam(torch.optim.Optimizer):
             raise RuntimeError("swap_ema() needs ema_decay: this optimiser keeps no averages")
         if self.micro_step:
             raise RuntimeError("swap_ema() inside an open accumulation window: flush() first")
-        ema = self._ema_ready()
+        ema = self._ema_tables()
         if ema is not None:
-            span = ema["span"]
-            ops.swap_multi(span["table"].data_ptr(), ema["ptrs_dev"].data_ptr(), span["n"], span["max_n"])
+            t = ema.table
+            ops.swap_multi(t.table_ptr, ema.ptrs_dev.data_ptr(), t.n, t.max_n)
         self._ema_swapped = not self._ema_swapped
-        if model is None:
-            moved = self._models
-        else:
-            moved = [getattr(model, "wav2vec2", None) or getattr(getattr(model, "w2v2_pr", None), "wav2vec2", None) or model]
-        for w2v in moved:
+        for w2v in self._models if model is None else [_encoder_of(model)]:
             if hasattr(w2v, "weights_moved"):       # a module without derived weight copies has nothing to be told
                 w2v.weights_moved()
 
@@ -259,7 +279,7 @@ class Adam(torch.optim.Optimizer):
     # ------------------------------------------------------------------ compute copies
     def publish_to(self, model) -> "Adam":
         """Refresh the wav2vec2 layer compute copies (ops.CastPlan destinations) inside the optimiser kernel."""
-        w2v = getattr(model, "wav2vec2", None) or getattr(getattr(model, "w2v2_pr", None), "wav2vec2", None) or model
+        w2v = _encoder_of(model)
         plan = w2v._layer_plan()
         by_ptr = {p.data_ptr(): p for g in self.param_groups for p in g["params"]}
         for src, dst in plan.jobs:
@@ -268,23 +288,41 @@ class Adam(torch.optim.Optimizer):
                 self._copies[id(p)] = (dst, 0 if dst.dtype == torch.bfloat16 else 1)
         self._plans.append(plan)
         self._models.append(w2v)
-        self._tables.clear()
-        self._span = None
+        self._table = None
         self._accum = None
         return self
 
+    @property
+    def publishes_copies(self) -> bool:
+        return bool(self._plans)
+
     # ------------------------------------------------------------------ step
-    def _group_tables(self, gi: int, group):
-        """Static job table of a parameter group (all its parameters, whether or not they get a gradient this step) and a
-        small ring of pinned host buffers for the per-step columns {grad pointer, step count} (two planes: prepare())."""
-        key = tuple(p.data_ptr() for p in group["params"])
-        cached = self._tables.get(gi)
-        if cached is not None and cached["key"] == key:
-            return cached
+    def _job_table(self):
+        """The ONE job table of the optimiser: a static row per updatable parameter of every device-resident group, in group order
+        (whether or not it gets a gradient this step), so that one norm, one window and one average span the groups and the norm's
+        summation order depends on the table alone; each group is a row range of it.  With it the per-call rows, int64 [2][n][2] on
+        the device - plane 0 is what the norm and Adam launches of finish() read {gradient or accumulator pointer, step count}, plane 1
+        what runs before them: the `early` rows of launch_early() or the {gradient, mode} rows of the accumulate launch - and the ring
+        of pinned buffers that feeds them.  Everything a step needs is allocated here or when a mode is first used, never later."""
+        key = tuple(tuple(p.data_ptr() for p in g["params"]) for g in self.param_groups)
+        t = self._table
+        if t is not None and t.key == key:
+            return t
         # parameters the kernel cannot update (e.g. the float64 low-pass taps, which are never trained) stay out of the table;
-        # step() raises if one of them ever shows up with a gradient
-        params = [p for p in group["params"] if p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()]
-        others = [p for p in group["params"] if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous())]
+        # prepare() raises if one of them, or one of a group that lives on the CPU, ever shows up with a gradient
+        params, others, cpu, groups = [], [], [], []
+        for gi, group in enumerate(self.param_groups):
+            if not any(p.is_cuda for p in group["params"]):
+                cpu += group["params"]
+                continue
+            mine = [p for p in group["params"] if _updatable(p)]
+            others += [p for p in group["params"] if not _updatable(p)]
+            if mine:
+                groups.append((gi, len(params), len(params) + len(mine), max(p.numel() for p in mine)))     # (group, r0, r1, max_n)
+                params += mine
+        if len({p.device for p in params}) > 1:
+            raise _lib.AptaiHipError("aptai_amd.optim.Adam(max_grad_norm=... / gradient_accumulation_steps=...): one global norm or "
+                                     "one window needs every parameter group on one device")
         rows = []
         for p in params:
             st = self.state[p]
@@ -295,65 +333,17 @@ class Adam(torch.optim.Optimizer):
             dst, kind = self._copies.get(id(p), (None, 0))
             rows.append([p.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), 0 if dst is None else dst.data_ptr(),
                          p.numel(), kind])
-        dev = params[0].device
-        cached = dict(key=key, table=torch.tensor(rows, dtype=torch.int64).to(dev), max_n=max(r[4] for r in rows),
-                      numels=[r[4] for r in rows], dyn_dev=torch.zeros((2, len(params), 2), dtype=torch.int64, device=dev),
-                      ring=[torch.zeros((2, len(params), 2), dtype=torch.int64).pin_memory() for _ in range(4)],
-                      events=[None] * 4, turn=0, states=[self.state[p] for p in params], params=params, others=others)
-        self._tables[gi] = cached
-        return cached
-
-    def _span_tables(self, ts, clip: bool = True):
-        """Clipping and accumulation: ONE job table over the rows of every group (`ts`: the groups' tables in group order), so that one norm spans
-        them and its summation order depends on the tables alone; per-step rows, pinned ring, partial-sum workspace and the result
-        words are allocated here, never inside a step.  The groups' Adam launches read row ranges of this table.  `clip` False (accumulation
-        without clipping): the table alone; the norm's workspace and result words follow when clipping is first asked for."""
-        span = self._span
-        if span is None or len(span["tables"]) != len(ts) or not all(a is t["table"] for a, t in zip(span["tables"], ts)):
-            devs = {t["table"].device for t in ts}
-            if len(devs) != 1:
-                raise _lib.AptaiHipError("aptai_amd.optim.Adam(max_grad_norm=... / gradient_accumulation_steps=...): one global norm or "
-                                         "one window needs every parameter group on one device")
-            dev = devs.pop()
-            offs, n = {}, 0
-            for t in ts:
-                offs[id(t)] = n
-                n += len(t["params"])
-            numels = [m for t in ts for m in t["numels"]]
-            span = dict(tables=[t["table"] for t in ts], table=torch.cat([t["table"] for t in ts]).contiguous(), offs=offs, n=n,
-                        max_n=max(numels), numels=numels, dev=dev, dyn_dev=torch.zeros((n, 2), dtype=torch.int64, device=dev),
-                        partials=None, ring=[torch.zeros((n, 2), dtype=torch.int64).pin_memory() for _ in range(4)], events=[None] * 4,
-                        turn=0)
-            self._span = span
-        if clip and span["partials"] is None:
-            if self._clip_result is None or self._clip_result.device != span["dev"]:
-                self._clip_result = torch.zeros(3, dtype=torch.float32, device=span["dev"])
-            span["partials"] = torch.zeros(ops.grad_norm_chunks(span["numels"]), dtype=torch.float32, device=span["dev"])
-        return span
-
-    def _accum_tables(self, span, ts):
-        """Accumulation: one fp32 accumulator per row of the span table (slices of ONE buffer, each 16-byte aligned so that the
-        accumulate and Adam kernels take their vector paths), their device pointer table, the per-call rows - plane 0 what the norm
-        and Adam launches of a closing step read {accumulator, step count}, plane 1 what the accumulate launch reads {grad, mode} -
-        and their pinned ring.  Allocated when the first window opens; a rebuilt span (publish_to, load_state_dict) discards the
-        open window with the old accumulators."""
-        acc = self._accum
-        if acc is not None and acc["span"] is span:
-            return acc
-        n, offs, total = span["n"], [], 0
-        for m in span["numels"]:
-            offs.append(total)
-            total += (m + 3) // 4 * 4
-        buf = torch.empty(total, dtype=torch.float32, device=span["dev"])
-        params = [p for t, _ in ts for p in t["params"]]
-        views = [buf[o:o + m].view(p.shape) for o, m, p in zip(offs, span["numels"], params)]
-        ptrs = [v.data_ptr() for v in views]
-        acc = dict(span=span, buf=buf, views=views, ptrs=ptrs, ptrs_dev=torch.tensor(ptrs, dtype=torch.int64).to(span["dev"]),
-                   rows={id(p): r for r, p in enumerate(params)}, dyn_dev=torch.zeros((2, n, 2), dtype=torch.int64, device=span["dev"]),
-                   ring=[torch.zeros((2, n, 2), dtype=torch.int64).pin_memory() for _ in range(4)], events=[None] * 4, turn=0,
-                   seen=[False] * n, applied=[False] * n, k=0)
-        self._accum = acc
-        return acc
+        t = SimpleNamespace(key=key, n=len(params), params=params, states=[self.state[p] for p in params], others=others, cpu=cpu,
+                            groups=groups, row_of={id(p): r for r, p in enumerate(params)}, numels=[r[4] for r in rows],
+                            partials=None)         # clipping: the norm's partial sums, allocated when clipping is first asked for
+        if params:
+            t.dev, t.max_n = params[0].device, max(t.numels)
+            t.table = torch.tensor(rows, dtype=torch.int64).to(t.dev)
+            t.rows = torch.zeros((2, t.n, 2), dtype=torch.int64, device=t.dev)
+            t.table_ptr, t.rows_ptr = t.table.data_ptr(), t.rows.data_ptr()
+            t.ring = ops.PinnedRing((t.rows,), 4)
+        self._table, self._accum = t, None
+        return t
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -368,249 +358,169 @@ class Adam(torch.optim.Optimizer):
     # ------------------------------------------------------------------ the step in pieces (aptai_amd.graphed: optimiser under the backward pass)
     @torch.no_grad()
     def prepare(self, early=()) -> None:
-        """Host half of step(): step counts and the per-step {gradient pointer, step} column of every group, copied to the device
-        on the current stream.  `early` names parameters whose update will be launched by launch_early() (once their gradient is
-        final, on any stream ordered behind this call) before finish() updates the rest.  Every parameter's `.grad` must already
-        be the tensor its gradient WILL be in (static gradient buffers): the kernel reads it only when it is launched."""
-        stream = torch.cuda.current_stream()
-        self._pending = []
-        self._pending_clip = None
-        self._pending_accum = None
-        self._prepare_ema()
-        # the averaging launch follows EVERY update of the step: with it on, every row goes to finish() and `early` is ignored, too
-        early_ids = set() if self._pending_ema is not None else {id(p) for p in early}
-        if self._accum_steps > 1:
-            # a window's mean does not exist before its last gradient does: every row goes to finish(), `early` is ignored
-            return self._prepare_accum(stream, True)
-        if self._max_grad_norm is not None:
-            # the global norm does not exist before the last gradient does: every row goes to finish(), `early` is ignored
-            # (launch_early() then finds nothing to do and the step is the one-launch step, bit for bit)
-            return self._prepare_clipped(stream)
-        for gi, group in enumerate(self.param_groups):
-            if not any(p.is_cuda for p in group["params"]):
-                if any(p.grad is not None for p in group["params"]):
-                    raise _lib.AptaiHipError("aptai_amd.optim.Adam needs parameters on the MI355X (no CPU fallback)")
-                continue
-            t = self._group_tables(gi, group)
-            params = t["params"]
-            if any(p.grad is not None for p in t["others"]):
-                raise _lib.AptaiHipError("aptai_amd.optim.Adam updates contiguous fp32 parameters on the MI355X only")
-            slot = t["turn"]
-            t["turn"] = (slot + 1) % len(t["ring"])
-            if t["events"][slot] is not None:
-                t["events"][slot].synchronize()        # the copy that last used this pinned buffer has been consumed
-            host = t["ring"][slot].numpy()             # [2][n][2]: plane 0 = rows finish() updates, plane 1 = rows launch_early() updates
-            host[:, :, 0] = 0
-            any_late = any_early = False
-            for j, (p, st) in enumerate(zip(params, t["states"])):
-                g = p.grad
-                if g is None:
-                    continue
-                if g.dtype != torch.float32 or not g.is_contiguous():
-                    raise _lib.AptaiHipError("aptai_amd.optim.Adam needs contiguous fp32 gradients")
-                st["step"] += 1
-                plane = 1 if id(p) in early_ids else 0
-                host[plane, j, 0] = g.data_ptr()
-                host[plane, j, 1] = st["step"]
-                any_early |= plane == 1
-                any_late |= plane == 0
-            if not (any_late or any_early):
-                continue
-            t["dyn_dev"].copy_(t["ring"][slot], non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(stream)
-            t["events"][slot] = ev
-            self._pending.append((t, group, any_late))
+        """Host half of step(): step counts and the per-call rows of every group, copied to the device on the current stream.
+        `early` names parameters whose update will be launched by launch_early() (once their gradient is final, on any stream
+        ordered behind this call) before finish() updates the rest.  Every parameter's `.grad` must already be the tensor its
+        gradient WILL be in (static gradient buffers): the kernel reads it only when it is launched."""
+        self._pending = self._prepare(early, True)
 
-    def _prepare_ema(self) -> None:
-        """Averaging on: the averages exist (a copy of the parameters as they are BEFORE the first averaged update) and their pointer
-        table matches the job tables before finish() launches anything."""
+    def _prepare(self, early, contribute: bool):
+        """What finish() will launch, or None for nothing: one micro-step or plain step (`contribute`) or the early close of flush().
+        One pass over the table's rows, one pinned buffer, one copy."""
         if self._ema_swapped:
             raise RuntimeError("the parameters hold their averages (swap_ema() / ema_weights()): swap back before the next step")
-        self._pending_ema = None if self._ema_decay is None else self._ema_ready()
-
-    def _device_groups(self):
-        """[(table, group)] of the groups with parameters on the device, after prepare()'s checks."""
-        ts = []
-        for gi, group in enumerate(self.param_groups):
-            if not any(p.is_cuda for p in group["params"]):
-                if any(p.grad is not None for p in group["params"]):
-                    raise _lib.AptaiHipError("aptai_amd.optim.Adam needs parameters on the MI355X (no CPU fallback)")
-                continue
-            t = self._group_tables(gi, group)
-            if any(p.grad is not None for p in t["others"]):
-                raise _lib.AptaiHipError("aptai_amd.optim.Adam updates contiguous fp32 parameters on the MI355X only")
-            ts.append((t, group))
-        return ts
-
-    def _prepare_accum(self, stream, contribute: bool) -> None:
-        """prepare() with accumulation on: one micro-step (`contribute`) or the early close of flush().  Plane 1 of the per-call rows
-        names this micro-step's gradients for the accumulate launch; a micro-step that closes the window also fills plane 0 with the
-        accumulators as gradient pointers and the step counts of the rows that contributed, which finish() hands to the usual
-        launches.  One pinned buffer, one copy."""
-        ts = self._device_groups()
-        if not ts:
-            return
-        span = self._span_tables([t for t, _ in ts], clip=self._max_grad_norm is not None)
-        acc = self._accum_tables(span, ts)
-        if not contribute and acc["k"] == 0:
-            return
-        slot = acc["turn"]
-        acc["turn"] = (slot + 1) % len(acc["ring"])
-        if acc["events"][slot] is not None:
-            acc["events"][slot].synchronize()          # the copy that last used this pinned buffer has been consumed
-        host = acc["ring"][slot].numpy()               # [2][rows of all groups][2]
+        t = self._job_table()
+        if any(p.grad is not None for p in t.cpu):
+            raise _lib.AptaiHipError("aptai_amd.optim.Adam needs parameters on the MI355X (no CPU fallback)")
+        if any(p.grad is not None for p in t.others):
+            raise _lib.AptaiHipError("aptai_amd.optim.Adam updates contiguous fp32 parameters on the MI355X only")
+        if t.n == 0:
+            return None
+        # averaging on: the averages exist (a copy of the parameters as they are BEFORE the first averaged update)
+        ema = None if self._ema_decay is None else self._ema_tables()
+        clip, acc = self._max_grad_norm, None
+        if clip is not None and t.partials is None:
+            if self._clip_result is None or self._clip_result.device != t.dev:
+                self._clip_result = torch.zeros(3, dtype=torch.float32, device=t.dev)
+            t.partials = torch.zeros(ops.grad_norm_chunks(t.numels), dtype=torch.float32, device=t.dev)
+        if self._accum_steps > 1 or not contribute:
+            acc = self._accumulators(t)
+            if not contribute and acc.k == 0:
+                return None
+        # A window's mean and the global norm do not exist before the last gradient does, and the averaging launch follows EVERY
+        # update of the step: in these modes every row goes to finish() and `early` is ignored (launch_early() then finds nothing to
+        # do and the step is the one-launch step, bit for bit)
+        plain = acc is None and clip is None and ema is None
+        early_ids = {id(p) for p in early} if plain else ()
+        host, = t.ring.next()
         host[:] = 0
-        seen, any_grad = acc["seen"], False
-        for t, group in ts:
-            off = span["offs"][id(t)]
-            for j, p in enumerate(t["params"]):
-                g = p.grad if contribute else None
-                if g is not None:
-                    if g.dtype != torch.float32 or not g.is_contiguous():
-                        raise _lib.AptaiHipError("aptai_amd.optim.Adam needs contiguous fp32 gradients")
-                    host[1, off + j, 0] = g.data_ptr()
-                    host[1, off + j, 1] = 2 if seen[off + j] else 1
-                    seen[off + j] = any_grad = True
-                elif seen[off + j]:
-                    host[1, off + j, 1] = 2
-        if contribute:
-            if not any_grad and acc["k"] == 0:
-                return                                 # nothing has a gradient and no window is open: nothing to do, as at N = 1
-            acc["k"] += 1
-        close = not contribute or acc["k"] >= self._accum_steps
-        scale = 1.0 / acc["k"] if close else 1.0
-        if close:
-            for t, group in ts:
-                off, any_seen = span["offs"][id(t)], False
-                for j, st in enumerate(t["states"]):
-                    if seen[off + j]:
-                        st["step"] += 1
-                        host[0, off + j, 0] = acc["ptrs"][off + j]
-                        host[0, off + j, 1] = st["step"]
-                        any_seen = True
-                if any_seen:
-                    self._pending.append((t, group, True))
-            acc["applied"], acc["seen"], acc["k"] = seen, [False] * span["n"], 0
-        acc["dyn_dev"].copy_(acc["ring"][slot], non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record(stream)
-        acc["events"][slot] = ev
-        # scale == 1 without a gradient (a flush() after one micro-step): the accumulators already hold the mean
-        self._pending_accum = (span, acc, scale, close, any_grad or scale != 1.0, self._max_grad_norm)
-
-    def _prepare_clipped(self, stream) -> None:
-        """prepare() with clipping on: the same checks and step counts, the per-step rows of ALL groups in one table, one copy."""
-        ts = self._device_groups()
-        if not ts:
-            return
-        span = self._span_tables([t for t, _ in ts])
-        slot = span["turn"]
-        span["turn"] = (slot + 1) % len(span["ring"])
-        if span["events"][slot] is not None:
-            span["events"][slot].synchronize()         # the copy that last used this pinned buffer has been consumed
-        host = span["ring"][slot].numpy()              # [rows of all groups][2]
-        host[:, 0] = 0
-        for t, group in ts:
-            off, any_grad = span["offs"][id(t)], False
-            for j, (p, st) in enumerate(zip(t["params"], t["states"])):
-                g = p.grad
+        groups, early_rows, any_grad = [], set(), False
+        params, states, seen = t.params, t.states, None if acc is None else acc.seen
+        for gi, r0, r1, max_n in t.groups:
+            late = hit = False
+            for r in range(r0, r1):
+                g = params[r].grad if contribute else None
                 if g is None:
+                    if seen is not None and seen[r]:
+                        host[1, r, 1] = 2              # no gradient in this micro-step, but part of the window: scaled at its close
                     continue
                 if g.dtype != torch.float32 or not g.is_contiguous():
                     raise _lib.AptaiHipError("aptai_amd.optim.Adam needs contiguous fp32 gradients")
+                hit = True
+                if seen is not None:                   # plane 1 = {gradient, mode: 1 first contribution of the window, 2 a later one}
+                    host[1, r, 0] = g.data_ptr()
+                    host[1, r, 1] = 2 if seen[r] else 1
+                    seen[r] = True
+                    continue
+                st = states[r]
                 st["step"] += 1
-                host[off + j, 0] = g.data_ptr()
-                host[off + j, 1] = st["step"]
-                any_grad = True
-            if any_grad:
-                self._pending.append((t, group, True))
-        if not self._pending:
-            return
-        span["dyn_dev"].copy_(span["ring"][slot], non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record(stream)
-        span["events"][slot] = ev
-        self._pending_clip = (span, self._max_grad_norm)
+                if early_ids and id(params[r]) in early_ids:
+                    host[1, r, 0] = g.data_ptr()
+                    host[1, r, 1] = st["step"]
+                    early_rows.add(r)
+                else:
+                    host[0, r, 0] = g.data_ptr()
+                    host[0, r, 1] = st["step"]
+                    late = True
+            any_grad |= hit
+            if hit and acc is None:
+                groups.append((gi, r0, r1, max_n, late))
+        window = None
+        if acc is not None:
+            if contribute:
+                if not any_grad and acc.k == 0:
+                    return None                        # nothing has a gradient and no window is open: nothing to do, as at N = 1
+                acc.k += 1
+            close = not contribute or acc.k >= self._accum_steps
+            scale = 1.0 / acc.k if close else 1.0
+            if close:
+                # plane 0 = the accumulators as gradient pointers and the step counts of the rows that contributed to the window
+                for gi, r0, r1, max_n in t.groups:
+                    rows = [r for r in range(r0, r1) if seen[r]]
+                    for r in rows:
+                        st = states[r]
+                        st["step"] += 1
+                        host[0, r, 0] = acc.ptrs[r]
+                        host[0, r, 1] = st["step"]
+                    if rows:
+                        groups.append((gi, r0, r1, max_n, True))
+                acc.applied, acc.seen, acc.k = seen, [False] * t.n, 0
+            # scale == 1 without a gradient (a flush() after one micro-step): the accumulators already hold the mean
+            window = SimpleNamespace(ptrs_dev=acc.ptrs_dev, scale=scale, close=close, launch=any_grad or scale != 1.0)
+        elif not groups:
+            return None
+        t.ring.send()
+        return SimpleNamespace(table=t, groups=groups, clip=clip, accum=window, ema=ema, early=early_rows if plain else None)
 
-    def _launch(self, t, group, plane: int, r0: int, r1: int, stream) -> None:
+    def _launch(self, t, gi: int, plane: int, r0: int, r1: int, max_n: int, coef, stream: int) -> None:
+        """The Adam launch over rows [r0, r1) of the table, their gradients multiplied by the device scalar `coef` if there is one."""
+        group = self.param_groups[gi]
         b1, b2 = group["betas"]
-        _lib.call("aptai_adam_multi", t["table"][r0].data_ptr(), t["dyn_dev"][plane, r0].data_ptr(), r1 - r0, max(t["numels"][r0:r1]),
-                  float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]), stream.cuda_stream)
+        args = (*_addr(t, plane, r0), r1 - r0, max_n, float(group["lr"]), float(b1), float(b2), float(group["eps"]),
+                float(group["weight_decay"]))
+        if coef is None:
+            _lib.call("aptai_adam_multi", *args, stream)
+        else:
+            ops.adam_multi_scaled(*args, coef, stream)
 
     @torch.no_grad()
     def launch_early(self, params, stream=None) -> None:
         """Update `params` (named in prepare(early=...)) now, on `stream`: one launch per parameter group over the row range that
-        spans them (rows in between that were not named `early` carry no gradient pointer in this plane and are skipped)."""
+        spans them (rows in between that were not named `early` carry no gradient pointer in this plane and are skipped).  A row
+        in between that WAS named `early` but is not one of `params` would be updated now, with a gradient that may not be final,
+        and again by its own call: that is refused before anything is launched."""
         stream = stream or torch.cuda.current_stream()
-        if self._pending_clip is not None or self._pending_accum is not None or self._pending_ema is not None:
+        pend = self._pending
+        if pend is None or pend.early is None:
             return
-        ids = {id(p) for p in params}
-        for t, group, _ in self._pending:
-            rows = [j for j, p in enumerate(t["params"]) if id(p) in ids]
-            if rows:
-                self._launch(t, group, 1, min(rows), max(rows) + 1, stream)
+        t, ids, spans = pend.table, {id(p) for p in params}, []
+        for gi, r0, r1, _, _ in pend.groups:
+            rows = [r for r in range(r0, r1) if id(t.params[r]) in ids]
+            if not rows:
+                continue
+            lo, hi = min(rows), max(rows) + 1
+            for r in range(lo, hi):
+                if r in pend.early and id(t.params[r]) not in ids:
+                    at = [[q is t.params[x] for q in self.param_groups[gi]["params"]].index(True) for x in (r, lo, hi - 1)]
+                    raise RuntimeError(f"launch_early(): parameter {at[0]} of group {gi} was named `early` in prepare() but is not "
+                                       f"among this call's parameters, whose rows span parameters {at[1]} to {at[2]} of the group: "
+                                       f"it would be updated twice")
+            spans.append((gi, lo, hi))
+        for gi, lo, hi in spans:
+            self._launch(t, gi, 1, lo, hi, max(t.numels[lo:hi]), None, stream.cuda_stream)
 
     @torch.no_grad()
     def finish(self, stream=None) -> None:
         """Update every parameter that has a gradient and was not named `early`."""
-        stream = stream or torch.cuda.current_stream()
-        self.last_step_updated = self._accum_steps == 1
-        applied = bool(self._pending)               # some parameter is updated by this call (inside a window: none)
-        if self._pending_accum is not None:
-            self._finish_accum(stream)
-        elif self._pending_clip is not None:
+        stream = (stream or torch.cuda.current_stream()).cuda_stream
+        pend, self._pending = self._pending, None
+        acc = None if pend is None else pend.accum
+        self.last_step_updated = self._accum_steps == 1 if acc is None else acc.close
+        for plan in self._plans:                    # the copies of every parameter that had a gradient are fresh now;
+            plan.optimizer_synced = True            # parameters without one did not move (nor did any inside a window)
+        if pend is None:
+            return
+        t = pend.table
+        if acc is not None:
+            if acc.launch:
+                ops.grad_accum_multi(*_addr(t, 1), acc.ptrs_dev.data_ptr(), t.n, t.max_n, acc.scale, stream)
+            if not acc.close:
+                return
+        coef = None
+        if pend.clip is not None:
             # here, not in prepare(): every gradient is final now (and, under data parallelism, already averaged: the norm is that
             # of the averaged gradient and the same on every rank).  Two norm launches, then the groups' Adam launches read the
             # coefficient from the device on the same stream
-            span, max_norm = self._pending_clip
-            tab, dyn, coef = span["table"].data_ptr(), span["dyn_dev"].data_ptr(), self._clip_result[1:2]
-            ops.grad_sqnorm_multi(tab, dyn, span["n"], span["max_n"], span["partials"], self._clip_result, max_norm, stream.cuda_stream)
-            for t, group, _ in self._pending:
-                off = span["offs"][id(t)]
-                b1, b2 = group["betas"]
-                ops.adam_multi_scaled(tab + off * 48, dyn + off * 16, len(t["params"]), t["max_n"], group["lr"], b1, b2, group["eps"],
-                                      group["weight_decay"], coef, stream.cuda_stream)
-            self._pending_clip = None
-        else:
-            for t, group, any_late in self._pending:
-                if any_late:
-                    self._launch(t, group, 0, 0, len(t["params"]), stream)
-        self._pending = []
-        for plan in self._plans:                    # the copies of every parameter that had a gradient are fresh now;
-            plan.optimizer_synced = True            # parameters without one did not move (nor did any inside a window)
-        ema, self._pending_ema = self._pending_ema, None
-        if ema is not None and applied and self._ema_decay is not None:
+            ops.grad_sqnorm_multi(*_addr(t, 0), t.n, t.max_n, t.partials, self._clip_result, pend.clip, stream)
+            coef = self._clip_result[1:2]
+        for gi, r0, r1, max_n, late in pend.groups:
+            if late:
+                self._launch(t, gi, 0, r0, r1, max_n, coef, stream)
+        if pend.ema is not None and pend.groups and self._ema_decay is not None:
             # ONE launch over the rows of all groups, behind every Adam launch of this call on the same stream
             self._ema_updates += 1
-            span = ema["span"]
-            ops.ema_multi(span["table"].data_ptr(), ema["ptrs_dev"].data_ptr(), span["n"], span["max_n"],
-                          1.0 - ema_decay_at(self._ema_updates, self._ema_decay, self.ema_warmup), stream.cuda_stream)
-
-    def _finish_accum(self, stream) -> None:
-        """finish() with accumulation on: the accumulate launch and, when the micro-step closes the window, today's launches on the
-        accumulated mean - the groups' Adam launches, behind the norm launches under clipping - over row ranges of the span table."""
-        span, acc, scale, close, launch, max_norm = self._pending_accum
-        self._pending_accum = None
-        tab, dyn = span["table"].data_ptr(), acc["dyn_dev"]
-        if launch:
-            ops.grad_accum_multi(tab, dyn[1].data_ptr(), acc["ptrs_dev"].data_ptr(), span["n"], span["max_n"], scale, stream.cuda_stream)
-        self.last_step_updated = close
-        if not close:
-            return
-        dyn = dyn[0].data_ptr()
-        if max_norm is not None:
-            coef = self._clip_result[1:2]
-            ops.grad_sqnorm_multi(tab, dyn, span["n"], span["max_n"], span["partials"], self._clip_result, max_norm, stream.cuda_stream)
-        for t, group, _ in self._pending:
-            off = span["offs"][id(t)]
-            b1, b2 = group["betas"]
-            if max_norm is not None:
-                ops.adam_multi_scaled(tab + off * 48, dyn + off * 16, len(t["params"]), t["max_n"], group["lr"], b1, b2, group["eps"],
-                                      group["weight_decay"], coef, stream.cuda_stream)
-            else:
-                _lib.call("aptai_adam_multi", tab + off * 48, dyn + off * 16, len(t["params"]), t["max_n"], float(group["lr"]), float(b1),
-                          float(b2), float(group["eps"]), float(group["weight_decay"]), stream.cuda_stream)
+            ops.ema_multi(t.table_ptr, pend.ema.ptrs_dev.data_ptr(), t.n, t.max_n,
+                          1.0 - ema_decay_at(self._ema_updates, self._ema_decay, self.ema_warmup), stream)
 
     @torch.no_grad()
     def flush(self) -> bool:
@@ -619,16 +529,9 @@ class Adam(torch.optim.Optimizer):
         if self.micro_step == 0:
             self.last_step_updated = False
             return False
-        self._pending = []
-        self._pending_clip = None
-        self._prepare_ema()
-        self._prepare_accum(torch.cuda.current_stream(), False)
+        self._pending = self._prepare((), False)
         self.finish()
         return True
-
-    @property
-    def publishes_copies(self) -> bool:
-        return bool(self._plans)
 
     # ------------------------------------------------------------------ checkpoints interchange with torch.optim.Adam
     def state_dict(self):
@@ -643,9 +546,8 @@ class Adam(torch.optim.Optimizer):
         for st in self.state.values():
             if torch.is_tensor(st.get("step")):
                 st["step"] = int(st["step"].item())
-        self._tables.clear()                        # the moment buffers were replaced: rebuild the job tables
-        self._span = None
-        self._accum = None                          # an open window is discarded with them
+        self._table = None                          # the moment buffers were replaced: rebuild the job table
+        self._accum = None                          # an open window is discarded with it
 
 
 def clip_grad_norm_(parameters, max_norm: float, norm_type: float = 2.0, error_if_nonfinite: bool = False, foreach=None) -> torch.Tensor:

@@ -148,7 +148,7 @@ def test_off_means_off_and_on_adds_one_launch(monkeypatch):
             per_step.append(list(calls))
         if decay is None:
             assert per_step == [["aptai_adam_multi"] * 3] * 3, per_step         # group 0 early and late, group 1 late
-            assert opt._ema is None and opt._span is None
+            assert opt._ema is None and opt._accum is None and opt._clip_result is None
         else:
             assert per_step == [["aptai_adam_multi"] * 2 + ["aptai_ema_multi"]] * 3, per_step     # `early` is ignored
     # no allocation after the first averaged step

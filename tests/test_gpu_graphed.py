@@ -451,7 +451,7 @@ def test_pinned_ring_delivers_every_value_in_order():
     """Seven values back to back through a ring of two slots, no host synchronisation in between: each slot is reused three
     times, so a slot refilled before its previous copy had been read would show as a wrong or repeated row."""
     import numpy as np
-    from aptai_amd.graphed import _PinnedRing
+    from aptai_amd.ops import PinnedRing as _PinnedRing
     dst = torch.zeros(2, device="cuda", dtype=torch.int32)
     got = torch.zeros((7, 2), device="cuda", dtype=torch.int32)
     ring = _PinnedRing((dst,), 2)

@@ -58,7 +58,7 @@ def main(rounds=9, iters=20):
         # kernels' time does not depend on the values)
         opt = sets["accum_close"][1]
         acc = opt._accum
-        acc["seen"], acc["k"] = [True] * len(acc["seen"]), 1
+        acc.seen, acc.k = [True] * len(acc.seen), 1
         opt.step()
     opt = sets["accum_close"][1]
     opt.step()

@@ -41,11 +41,11 @@ def main(rounds=9, iters=20):
     opt = Adam(ps, lr=1e-5, ema_decay=0.999)
     opt.step()
     opt.step()
-    t, group = opt._tables[0], opt.param_groups[0]
-    ema, span = opt._ema, opt._ema["span"]
-    stream = torch.cuda.current_stream()
-    tab, ptrs, n, max_n = span["table"].data_ptr(), ema["ptrs_dev"].data_ptr(), span["n"], span["max_n"]
-    fns = {"adam": lambda: opt._launch(t, group, 0, 0, len(t["params"]), stream),       # the per-step rows of the last step()
+    t, ema = opt._table, opt._ema                                                       # one group: its rows are the whole job table
+    gi, r0, r1, max_n = t.groups[0]
+    stream = torch.cuda.current_stream().cuda_stream
+    tab, ptrs, n = t.table_ptr, ema.ptrs_dev.data_ptr(), t.n
+    fns = {"adam": lambda: opt._launch(t, gi, 0, r0, r1, max_n, None, stream),          # the per-step rows of the last step()
            "ema": lambda: ops.ema_multi(tab, ptrs, n, max_n, 1.0 - 0.999),
            "swap": lambda: ops.swap_multi(tab, ptrs, n, max_n)}
     for fn in fns.values():
