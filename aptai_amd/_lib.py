@@ -122,6 +122,8 @@ ARGTYPES = {
     "aptai_eval_collapse_runs": [_P, _I64, _P, _I64, _P, _I64, _P, _P],
     "aptai_eval_edit_distance": [_P, _I64, _P, _P, _I64, _P, _I64, _P, _P],
     "aptai_resample_batch": [_P, _I, _P, _I64, _P, _P, _I64, _I64, _I64, _I64, _P, _P, _I64, _I64, _P],
+    "aptai_resample_batch_multi": [_P, _I, _P, _I64, _P, _I64, _P, _I64, _P, _P, _I64, _P, _P, _P, _P, _I64, _I64, _P],
+    "aptai_warp_targets": [_P, _I64, _P, _I64, _I64, _I64, _P, _P, _P, _P, _I64, _I64, _P],
     "aptai_wave_normalize": [_P, _I64, _P, _I64, _I64, _P, _P],
     "aptai_wave_normalize_workspace_bytes": [_I64, _I64],
     "aptai_device_check": [ctypes.c_char_p, _I],

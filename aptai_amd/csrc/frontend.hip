@@ -35,12 +35,14 @@ __device__ __forceinline__ void stage_vec(const int16_t* s, long g, float* dst) 
     for (int e = 0; e < 8; ++e) dst[e] = (float)v[e] * (1.0f / 32768.0f);
 }
 
+// One tile of row blockIdx.y at the ratio orig -> new_ with its bank (taps, first): the body of both resampling kernels, so a row
+// of the per-row-ratio launch runs the instructions the single-ratio launch runs for it.
 // TL: the tap table and `first` are staged in LDS (ds_read instead of flat loads on the inner loop)
 template <typename SRC, bool TL>
-__global__ __launch_bounds__(FE_THREADS) void resample_kernel(const SRC* __restrict__ src, const long long* __restrict__ offsets,
-                                                              const float* __restrict__ taps, const int* __restrict__ first, int orig,
-                                                              int new_, int Kc, int width, const long long* __restrict__ out_start,
-                                                              float* __restrict__ out, long ld, int ncols, int tile) {
+__device__ __forceinline__ void resample_tile(const SRC* __restrict__ src, const long long* __restrict__ offsets,
+                                              const float* __restrict__ taps, const int* __restrict__ first, int orig,
+                                              int new_, int Kc, int width, const long long* __restrict__ out_start,
+                                              float* __restrict__ out, long ld, int ncols, int tile) {
     constexpr int VEC = 16 / (int)sizeof(SRC);
     extern __shared__ __attribute__((aligned(16))) float fe_lds[];           // xs[RS_SPAN] | taps[new * Kc] | first[new] (the last two when staged)
     float* xs = fe_lds;
@@ -114,6 +116,92 @@ __global__ __launch_bounds__(FE_THREADS) void resample_kernel(const SRC* __restr
             }
         }
         orow[c0 + i] = acc;
+    }
+}
+
+template <typename SRC, bool TL>
+__global__ __launch_bounds__(FE_THREADS) void resample_kernel(const SRC* __restrict__ src, const long long* __restrict__ offsets,
+                                                              const float* __restrict__ taps, const int* __restrict__ first, int orig,
+                                                              int new_, int Kc, int width, const long long* __restrict__ out_start,
+                                                              float* __restrict__ out, long ld, int ncols, int tile) {
+    resample_tile<SRC, TL>(src, offsets, taps, first, orig, new_, Kc, width, out_start, out, ld, ncols, tile);
+}
+
+// Per-row ratios: row b runs at entry ratio[b] of `table` (RS_ENTRY int32 words each: orig, new, Kc, width, the offsets of its taps
+// and `first` inside the concatenated arrays, two spare words).  blockIdx.y picks the row, so the entry is read with scalar loads and
+// every branch on it is uniform.  A bank is staged when it fits both the LDS budget of the single-ratio kernel and what this launch
+// reserved behind the source span (lds_bank entries, taps and `first` together); staging never changes a bit.
+constexpr int RS_ENTRY = 8;
+
+template <typename SRC>
+__global__ __launch_bounds__(FE_THREADS) void resample_multi_kernel(const SRC* __restrict__ src, const long long* __restrict__ offsets,
+                                                                    const float* __restrict__ taps, const int* __restrict__ first,
+                                                                    const int* __restrict__ table, const int* __restrict__ ratio,
+                                                                    int n_ratios, int lds_bank, const long long* __restrict__ out_start,
+                                                                    float* __restrict__ out, long ld, int ncols, int tile) {
+    int r = ratio[blockIdx.y];
+    r = r < 0 ? 0 : (r >= n_ratios ? n_ratios - 1 : r);                      // checked on the host; never an index outside the table
+    const int* e = table + r * RS_ENTRY;
+    const int orig = e[0], new_ = e[1], Kc = e[2], width = e[3];
+    const float* tp = taps + e[4];
+    const int* fp = first + e[5];
+    const bool staged = orig != new_ && (long)new_ * Kc <= RS_TAPS && new_ <= RS_FIRST && (long)new_ * Kc + new_ <= lds_bank;
+    if (staged) resample_tile<SRC, true>(src, offsets, tp, fp, orig, new_, Kc, width, out_start, out, ld, ncols, tile);
+    else resample_tile<SRC, false>(src, offsets, tp, fp, orig, new_, Kc, width, out_start, out, ld, ncols, tile);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- target warping
+// Row r of the launch: a fp64 track (r < R_trk) or an int64 label row, n_in[r] frames -> n_out[r] frames over the same time range.
+// Positions are numpy's linspace(0, n_in - 1, n_out): p_i = i * ((n_in - 1) / (n_out - 1)), the last one n_in - 1 itself.  Every
+// product is rounded before it is used (fe_rounded), so nothing contracts into an fma and a track is hostlogic.warp_track's bits.
+constexpr double WT_IGNORE = -100.0;
+
+__device__ __forceinline__ double fe_rounded(double v) {
+    asm volatile("" : "+v"(v));
+    return v;
+}
+
+__global__ __launch_bounds__(FE_THREADS) void warp_targets_kernel(const double* __restrict__ trk, const long long* __restrict__ lab,
+                                                                  int R_trk, long ld_in, int T_in, const long long* __restrict__ n_in_,
+                                                                  const long long* __restrict__ n_out_, double* __restrict__ trk_out,
+                                                                  long long* __restrict__ lab_out, long ld_out, int T_out) {
+    const int r = blockIdx.y;
+    const int i = blockIdx.x * FE_THREADS + threadIdx.x;
+    if (i >= T_out) return;
+    long long ni = n_in_[r], no = n_out_[r];
+    const int n_in = ni < 0 ? 0 : (ni > T_in ? T_in : (int)ni);              // nothing outside the row is read or written
+    const int n_out = (n_in == 0 || no < 0) ? 0 : (no > T_out ? T_out : (int)no);
+    const bool track = r < R_trk;
+    if (i >= n_out) {
+        if (track) trk_out[(long)r * ld_out + i] = WT_IGNORE;
+        else lab_out[(long)(r - R_trk) * ld_out + i] = 0;
+        return;
+    }
+    double p;
+    if (n_out == 1) p = 0.0;
+    else if (i == n_out - 1) p = (double)(n_in - 1);
+    else p = fe_rounded((double)i * ((double)(n_in - 1) / (double)(n_out - 1)));
+    if (track) {
+        const double* x = trk + (long)r * ld_in;
+        double y;
+        if (n_in == n_out) {
+            y = x[i];
+        } else {
+            int lo = (int)floor(p);
+            const int top = n_in - 2 > 0 ? n_in - 2 : 0;
+            lo = lo < 0 ? 0 : (lo > top ? top : lo);
+            const int hi = lo + 1 < n_in - 1 ? lo + 1 : n_in - 1;
+            const double w = p - (double)lo;
+            const double xl = x[lo], xh = x[hi];
+            y = xl + fe_rounded(fe_rounded(xh - xl) * w);
+            if (xl == WT_IGNORE || (w > 0.0 && xh == WT_IGNORE)) y = WT_IGNORE;
+        }
+        trk_out[(long)r * ld_out + i] = y;
+    } else {
+        const long long* x = lab + (long)(r - R_trk) * ld_in;
+        int k = (int)floor(p + 0.5);
+        k = k > n_in - 1 ? n_in - 1 : (k < 0 ? 0 : k);
+        lab_out[(long)(r - R_trk) * ld_out + i] = x[k];
     }
 }
 
@@ -266,6 +354,79 @@ extern "C" int aptai_resample_batch(const void* src, int src_is_int16, const int
     }
 #undef FE_RESAMPLE
     APTAI_CHECK_LAUNCH("resample_kernel");
+    return APTAI_OK;
+}
+
+extern "C" int aptai_resample_batch_multi(const void* src, int src_is_int16, const int64_t* offsets, int64_t B, const float* taps,
+                                          int64_t n_taps, const int32_t* first, int64_t n_first, const int32_t* table,
+                                          const int32_t* table_host, int64_t n_ratios, const int32_t* ratio, const int32_t* ratio_host,
+                                          const int64_t* out_start, float* out, int64_t ld, int64_t ncols, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    APTAI_REQUIRE(src && offsets && out && table && table_host && ratio && ratio_host, "aptai_resample_batch_multi: null pointer");
+    APTAI_REQUIRE(src_is_int16 == 0 || src_is_int16 == 1, "aptai_resample_batch_multi: src_is_int16 must be 0 or 1 (got %d)", src_is_int16);
+    APTAI_REQUIRE(B > 0 && B <= 65535 && ncols >= 0 && ncols <= 0x7fffffff && ld >= ncols && ld >= 1,
+                  "aptai_resample_batch_multi: bad sizes (B=%ld, ld=%ld, ncols=%ld)", (long)B, (long)ld, (long)ncols);
+    APTAI_REQUIRE(n_ratios >= 1 && n_ratios <= APTAI_RESAMPLE_MAX_RATIOS, "aptai_resample_batch_multi: %ld ratios, 1 .. %d expected",
+                  (long)n_ratios, APTAI_RESAMPLE_MAX_RATIOS);
+    APTAI_REQUIRE(n_taps >= 0 && n_first >= 0 && n_taps <= 0x7fffffff && n_first <= 0x7fffffff,
+                  "aptai_resample_batch_multi: bad table sizes (%ld taps, %ld first)", (long)n_taps, (long)n_first);
+    APTAI_REQUIRE(((uintptr_t)src & 15) == 0, "aptai_resample_batch_multi: the packed source buffer must be 16-byte aligned");
+    bool present[APTAI_RESAMPLE_MAX_RATIOS] = {};
+    for (int64_t b = 0; b < B; ++b) {
+        APTAI_REQUIRE(ratio_host[b] >= 0 && ratio_host[b] < n_ratios, "aptai_resample_batch_multi: row %ld has ratio index %d, the table has %ld",
+                      (long)b, (int)ratio_host[b], (long)n_ratios);
+        present[ratio_host[b]] = true;
+    }
+    // the tile is the smallest fit over the ratios present (the rule of aptai_resample_batch); the LDS behind the source span holds
+    // the largest bank among them that fits the budget
+    int64_t tile = RS_TILE, lds_bank = 0;
+    for (int64_t r = 0; r < n_ratios; ++r) {
+        const int32_t* e = table_host + r * RS_ENTRY;
+        const int64_t orig = e[0], new_ = e[1], Kc = e[2], width = e[3], t_off = e[4], f_off = e[5];
+        APTAI_REQUIRE(orig >= 1 && new_ >= 1, "aptai_resample_batch_multi: entry %ld has the ratio %ld -> %ld", (long)r, (long)orig, (long)new_);
+        if (orig == new_) continue;
+        APTAI_REQUIRE(taps && first, "aptai_resample_batch_multi: null filter table");
+        APTAI_REQUIRE(Kc >= 1 && width >= 0 && width <= 0x3fffffff && Kc <= APTAI_RESAMPLE_MAX_TABLE,
+                      "aptai_resample_batch_multi: entry %ld has a bad filter (Kc=%ld, width=%ld)", (long)r, (long)Kc, (long)width);
+        APTAI_REQUIRE(new_ * Kc <= APTAI_RESAMPLE_MAX_TABLE, "aptai_resample_batch_multi: entry %ld: a tap table of %ld x %ld entries exceeds %d",
+                      (long)r, (long)new_, (long)Kc, APTAI_RESAMPLE_MAX_TABLE);
+        APTAI_REQUIRE(t_off >= 0 && f_off >= 0 && t_off + new_ * Kc <= n_taps && f_off + new_ <= n_first,
+                      "aptai_resample_batch_multi: entry %ld lies outside the concatenated tables", (long)r);
+        if (!present[r]) continue;
+        const int64_t fit = (RS_SPAN - Kc - 10) * new_ / orig;
+        const int64_t t = fit >= RS_TILE ? RS_TILE : (fit < 256 ? 256 : fit / 256 * 256);
+        tile = t < tile ? t : tile;
+        if (new_ * Kc <= RS_TAPS && new_ <= RS_FIRST && new_ * Kc + new_ > lds_bank) lds_bank = new_ * Kc + new_;
+    }
+    if (ncols == 0) return APTAI_OK;
+    const int64_t tiles = ceil_div(ncols, tile);
+    const size_t lds = sizeof(float) * (size_t)(RS_SPAN + lds_bank);
+    const dim3 grid((unsigned)tiles, (unsigned)B);
+#define FE_RESAMPLE_MULTI(SRC)                                                                                                          \
+    APTAI_LAUNCH((resample_multi_kernel<SRC>), grid, dim3(FE_THREADS), lds, stream, (const SRC*)src, (const long long*)offsets, taps, first, \
+                 (const int*)table, (const int*)ratio, (int)n_ratios, (int)lds_bank, (const long long*)out_start, out, (long)ld, (int)ncols, \
+                 (int)tile)
+    if (src_is_int16) FE_RESAMPLE_MULTI(int16_t); else FE_RESAMPLE_MULTI(float);
+#undef FE_RESAMPLE_MULTI
+    APTAI_CHECK_LAUNCH("resample_multi_kernel");
+    return APTAI_OK;
+}
+
+extern "C" int aptai_warp_targets(const double* tracks, int64_t R_trk, const int64_t* labels, int64_t R_lab, int64_t ld_in, int64_t T_in,
+                                  const int64_t* n_in, const int64_t* n_out, double* tracks_out, int64_t* labels_out, int64_t ld_out,
+                                  int64_t T_out, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    APTAI_REQUIRE(R_trk >= 0 && R_lab >= 0 && R_trk + R_lab >= 1 && R_trk + R_lab <= 65535, "aptai_warp_targets: bad row counts (%ld tracks, %ld label rows)",
+                  (long)R_trk, (long)R_lab);
+    APTAI_REQUIRE(n_in && n_out && (R_trk == 0 || (tracks && tracks_out)) && (R_lab == 0 || (labels && labels_out)),
+                  "aptai_warp_targets: null pointer");
+    APTAI_REQUIRE(T_in >= 0 && T_out >= 0 && T_in <= 0x7fffffff && T_out <= 0x7fffffff && ld_in >= T_in && ld_out >= T_out,
+                  "aptai_warp_targets: bad sizes (T_in=%ld, ld_in=%ld, T_out=%ld, ld_out=%ld)", (long)T_in, (long)ld_in, (long)T_out, (long)ld_out);
+    if (T_out == 0) return APTAI_OK;
+    const dim3 grid((unsigned)ceil_div(T_out, FE_THREADS), (unsigned)(R_trk + R_lab));
+    APTAI_LAUNCH(warp_targets_kernel, grid, dim3(FE_THREADS), 0, stream, tracks, (const long long*)labels, (int)R_trk, (long)ld_in, (int)T_in,
+                 (const long long*)n_in, (const long long*)n_out, tracks_out, (long long*)labels_out, (long)ld_out, (int)T_out);
+    APTAI_CHECK_LAUNCH("warp_targets_kernel");
     return APTAI_OK;
 }
 

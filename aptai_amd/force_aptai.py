@@ -459,7 +459,9 @@ class Force_APTAI(nn.Module):
     def forward(self, epoch, audio_inputs, audio_lengths, phoneme_labels, phn_frames_49hz, LA, LP, JA, TTCL, TTCD, TMCL, TMCD,
                 TBCL, TBCD, _phn_pred_list=None, _ac_override=None, _prefetch_next=None, _device_outputs=False):
         """`_prefetch_next = (audio_inputs, audio_lengths)` of the batch the NEXT call will receive (the same tensor objects)
-        starts its frozen-encoder pass on a side stream beside this call's heads (see prefetch)."""
+        starts its frozen-encoder pass on a side stream beside this call's heads (see prefetch).  A row with fewer frames than
+        phonemes (a speed-perturbed utterance: the audio shrinks, the transcript does not) has no alignment; the forward-sum loss
+        runs with zero_infinity and counts it as zero."""
         tv_targets = torch.stack([LA, LP, JA, TTCL, TTCD, TMCL, TMCD, TBCL, TBCD], dim=-1).float()
         labels = phoneme_labels if (self._transcript() == "labels" and _phn_pred_list is None) else None
         res, g, dec = self._run(audio_inputs, audio_lengths, tv_targets, _phn_pred_list, _ac_override, _prefetch_next, labels)

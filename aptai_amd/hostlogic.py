@@ -435,6 +435,46 @@ def interpolate_signal(org_sig, tar_len: int) -> np.ndarray:
     return x[lo] + (x[hi] - x[lo]) * w
 
 
+def speed_rate(rate: int, factor: float) -> int:
+    """The rate a source sampled at `rate` counts as when it is played `factor` times as fast: int(round(rate * factor)), the rule
+    of torchaudio.transforms.Speed (and sox `speed`).  Resampling from it back to the target rate is the speed perturbation of
+    Ko et al. 2015: 16 kHz at 0.9 is 14400 -> 16000 = 9:10, ten samples out for nine in."""
+    return int(round(rate * factor))
+
+
+def _warp_positions(n_in: int, n_out: int) -> np.ndarray:
+    return np.linspace(0, n_in - 1, n_out)
+
+
+def warp_track(x, n_in: int, n_out: int, ignore: float = -100.0) -> np.ndarray:
+    """The first `n_in` frames of a fp64 track stretched to `n_out` frames over the same time range, as `interpolate_signal` does
+    it (the oracle of aptai_warp_targets, bit for bit).  A frame whose left neighbour is `ignore`, or whose right neighbour is and
+    has a weight above 0, is `ignore`.  n_in == n_out returns the frames as they are; n_in == 0 returns n_out frames of `ignore`."""
+    x = np.asarray(x, dtype=np.float64)[:n_in]
+    n_in, n_out = int(n_in), int(n_out)
+    if n_in == 0:
+        return np.full(n_out, ignore, dtype=np.float64)
+    if n_in == n_out:
+        return x.copy()
+    out = interpolate_signal(x, n_out)
+    pos = _warp_positions(n_in, n_out)
+    lo = np.clip(np.floor(pos).astype(np.int64), 0, max(n_in - 2, 0))
+    hi = np.minimum(lo + 1, n_in - 1)
+    out[(x[lo] == ignore) | ((pos - lo > 0) & (x[hi] == ignore))] = ignore
+    return out
+
+
+def warp_frame_labels(lab, n_in: int, n_out: int) -> np.ndarray:
+    """The first `n_in` frame labels stretched to `n_out` frames: frame i takes the label nearest to its position on the old grid,
+    lab[min(floor(p_i + 0.5), n_in - 1)] with warp_track's positions.  n_in == 0 returns n_out zeros (the collate's padding)."""
+    lab = np.asarray(lab)[:n_in]
+    n_in, n_out = int(n_in), int(n_out)
+    if n_in == 0:
+        return np.zeros(n_out, dtype=lab.dtype)
+    k = np.minimum(np.floor(_warp_positions(n_in, n_out) + 0.5).astype(np.int64), n_in - 1)
+    return lab[k]
+
+
 def match_phonemes_to_frames(phoneme_boundaries, phoneme_list, frame_duration: float = 0.02) -> list:
     """Frame labels from phoneme END boundaries (utility.py:317-342): frame k covers [k*step, (k+1)*step) centiseconds with
     step = int(frame_duration*100); it takes the first phoneme whose boundary falls inside, otherwise keeps the previous frame's

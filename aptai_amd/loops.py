@@ -15,15 +15,24 @@ from types import SimpleNamespace
 import torch
 
 from . import hostlogic
-from .frontend import make_frontend, raw_batch_to_device
+from .frontend import make_frontend, parse_speeds, raw_batch_to_device, uses_frontend
 
 
-def to_device(batch, device, frontend, audio_key, length_key, host_lengths=False):
-    """The collate's batch on the device.  With a front end (cfg.source_rate / cfg.normalize_audio) the batch is a `collate_*_raw`
-    one: its packed audio is uploaded as it is and resampled / normalised there into `audio_key` / `length_key`."""
+def to_device(batch, device, frontend, audio_key, length_key, host_lengths=False, augment=False):
+    """The collate's batch on the device.  With a front end (cfg.source_rate / cfg.normalize_audio / cfg.speed_perturb) the batch
+    is a `collate_*_raw` one: its packed audio is uploaded as it is and resampled / normalised there into `audio_key` /
+    `length_key`.  `augment` (the training step only): a front end with speeds perturbs the batch, audio and frame-level targets;
+    the indices it applied stay on it as `frontend.last_speed_index` and do not travel into the model's arguments."""
     if frontend is None:
         return {k: v.to(device) for k, v in batch.items()}
-    return raw_batch_to_device(batch, frontend, device, audio_key, length_key, host_lengths=host_lengths)
+    out = raw_batch_to_device(batch, frontend, device, audio_key, length_key, host_lengths=host_lengths, augment=augment)
+    frontend.last_speed_index = out.pop("_speed_index", None)
+    return out
+
+
+def _dp_rank() -> int:
+    import torch.distributed as dist
+    return dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
 
 
 def adam_and_schedule(params, args_cfg, publish_to=None):
@@ -48,7 +57,8 @@ def default_cfg(overrides, **own):
     cfg = SimpleNamespace(device="cuda", num_epochs=2, adam_beta1=0.9, adam_beta2=0.999, adam_epsilon=1e-8, adam_weight_decay=0.0,
                           num_warmup_epochs=10, num_static_epochs=30, lr_decay=0.96, target_metric_bigger_better=False,
                           device_metrics=False, batch_invariant_eval=False, source_rate=None, normalize_audio=False, ema_decay=None,
-                          ema_warmup=False, mask_feature_prob=None, mask_feature_length=None, **own)
+                          ema_warmup=False, mask_feature_prob=None, mask_feature_length=None, speed_perturb=None, speed_perturb_seed=0,
+                          **own)
     cfg.__dict__.update(overrides)
     return cfg
 
@@ -71,6 +81,10 @@ def add_shared_arguments(ap):
     ap.add_argument("--source_rate", type=int, default=None,
                     help="the corpus' sampling rate: the audio is uploaded at that rate and resampled to 16 kHz on the device")
     ap.add_argument("--normalize_audio", action="store_true", help="zero-mean / unit-variance normalisation on the device")
+    ap.add_argument("--speed_perturb", type=str, default=None,
+                    help="speed perturbation of the training batches on the device: comma-separated factors in [0.5, 2.0], at most 8 "
+                         "(e.g. 0.9,1.0,1.1), one drawn per utterance and step; frame-level targets are stretched to match (off by default)")
+    ap.add_argument("--speed_perturb_seed", type=int, default=0, help="seed of the --speed_perturb draws (a data-parallel rank adds its rank)")
     ap.add_argument("--batch_invariant_eval", action="store_true",
                     help="validate() / test() with the model's batch_invariant switch on: every utterance of a batch scored as if it "
                          "ran alone, so evaluation may run at any batch size (off by default)")
@@ -80,7 +94,8 @@ def shared_arguments(a) -> dict:
     """The parsed flags of add_shared_arguments as default_cfg entries."""
     return dict(max_grad_norm=a.max_grad_norm, gradient_accumulation_steps=a.gradient_accumulation_steps, source_rate=a.source_rate,
                 normalize_audio=a.normalize_audio, batch_invariant_eval=a.batch_invariant_eval, ema_decay=a.ema_decay,
-                ema_warmup=a.ema_warmup, mask_feature_prob=a.mask_feature_prob, mask_feature_length=a.mask_feature_length)
+                ema_warmup=a.ema_warmup, mask_feature_prob=a.mask_feature_prob, mask_feature_length=a.mask_feature_length,
+                speed_perturb=parse_speeds(a.speed_perturb), speed_perturb_seed=a.speed_perturb_seed)
 
 
 def apply_mask_feature_arguments(w2v_cfg, a):
@@ -129,13 +144,14 @@ class EpochDriver:
     """The state a train() carries from step to step and from epoch to epoch.  Per trained batch the loop calls `eager_step` or
     `graphed_step`, per epoch `end_epoch`, at the end `close`.
 
-        frontend   None unless cfg.source_rate / cfg.normalize_audio: then the loaders use the `collate_*_raw` functions
+        frontend   None unless cfg.source_rate / cfg.normalize_audio / cfg.speed_perturb: then the loaders use the `collate_*_raw`
+                   functions (its speed draws are seeded with cfg.speed_perturb_seed + the data-parallel rank)
         steps      batches trained on in this epoch so far
     """
 
     def __init__(self, cfg, model, optimizer, lr_scheduler, best_ckpt_path):
         self.cfg, self.model, self.optimizer, self.lr_scheduler = cfg, model, optimizer, lr_scheduler
-        self.frontend = make_frontend(cfg)
+        self.frontend = make_frontend(cfg, rank=_dp_rank())
         # cfg.max_grad_norm: the optimiser clips at this global norm inside step(); the loop only adds the device-side norm and the
         # "was clipped" flag into two device scalars per step and reads them once per epoch (optim.ClipMonitor)
         self.clip = None

@@ -7,6 +7,7 @@ from __future__ import annotations
 import ctypes
 from typing import Optional
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1110,6 +1111,67 @@ def resample_batch(packed, offsets_i64, B, taps_f32, first_i32, orig, new, Kc, w
     _lib.call("aptai_resample_batch", packed.data_ptr(), int(packed.dtype == torch.int16), offsets_i64.data_ptr(), B, _ptr(taps_f32),
               _ptr(first_i32), orig, new, Kc, width, _ptr(out_start_i64), out.data_ptr(), out.stride(0), ncols, _stream())
     return out
+
+
+RESAMPLE_MAX_RATIOS = 8                 # APTAI_RESAMPLE_MAX_RATIOS
+RESAMPLE_ENTRY = 8                      # int32 words per ratio: orig, new, Kc, width, taps_off, first_off, 0, 0
+
+
+def resample_batch_multi(packed, offsets_i64, B, taps_f32, first_i32, table_i32, table_host, ratio_i32, ratio_host, out, ncols,
+                         out_start_i64=None):
+    """`resample_batch` with a ratio per row - see aptai_resample_batch_multi.  `table_i32` [n][8] / `ratio_i32` [B] are the device
+    copies of the int32 numpy arrays `table_host` / `ratio_host`, which the library checks before the launch; `taps_f32` /
+    `first_i32` are the banks back to back (None when every entry is 1:1).  No synchronisation."""
+    _dev(packed, offsets_i64, taps_f32, first_i32, table_i32, ratio_i32, out, out_start_i64)
+    if packed.dtype not in (torch.float32, torch.int16) or packed.dim() != 1 or not packed.is_contiguous():
+        raise _lib.AptaiHipError("resample_batch_multi: the packed source must be a contiguous 1-D float32 or int16 tensor")
+    if out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != B or out.stride(1) != 1 or ncols > out.shape[1]:
+        raise _lib.AptaiHipError(f"resample_batch_multi: the output must be fp32 [{B}][>= {ncols}] with unit column stride")
+    _i64_vec(offsets_i64, B + 1, "resample_batch_multi", "offsets")
+    if out_start_i64 is not None:
+        _i64_vec(out_start_i64, B, "resample_batch_multi", "out_start")
+    table_host = np.ascontiguousarray(table_host, dtype=np.int32)
+    ratio_host = np.ascontiguousarray(ratio_host, dtype=np.int32).reshape(-1)
+    n = table_host.shape[0] if table_host.ndim == 2 else 0
+    if table_host.ndim != 2 or table_host.shape[1] != RESAMPLE_ENTRY or not 1 <= n <= RESAMPLE_MAX_RATIOS:
+        raise _lib.AptaiHipError(f"resample_batch_multi: a table of 1 .. {RESAMPLE_MAX_RATIOS} entries of {RESAMPLE_ENTRY} int32 words expected")
+    if (table_i32.dtype != torch.int32 or table_i32.numel() != n * RESAMPLE_ENTRY or not table_i32.is_contiguous()
+            or ratio_i32.dtype != torch.int32 or ratio_i32.numel() != B or not ratio_i32.is_contiguous() or ratio_host.size != B):
+        raise _lib.AptaiHipError(f"resample_batch_multi: table int32 [{n}][{RESAMPLE_ENTRY}] and ratio int32 [{B}] expected, on the device and on the host")
+    for t, dt, what in ((taps_f32, torch.float32, "taps fp32"), (first_i32, torch.int32, "first int32")):
+        if t is not None and (t.dtype != dt or not t.is_contiguous()):
+            raise _lib.AptaiHipError(f"resample_batch_multi: contiguous {what} expected")
+    _lib.call("aptai_resample_batch_multi", packed.data_ptr(), int(packed.dtype == torch.int16), offsets_i64.data_ptr(), B, _ptr(taps_f32),
+              0 if taps_f32 is None else taps_f32.numel(), _ptr(first_i32), 0 if first_i32 is None else first_i32.numel(),
+              table_i32.data_ptr(), table_host.ctypes.data, n, ratio_i32.data_ptr(), ratio_host.ctypes.data, _ptr(out_start_i64),
+              out.data_ptr(), out.stride(0), ncols, _stream())
+    return out
+
+
+def warp_targets(tracks_f64, labels_i64, n_in_i64, n_out_i64, T_out):
+    """Frame-level targets stretched from n_in to n_out frames per row - see aptai_warp_targets.  `tracks_f64` fp64 [R_trk][T_in] and
+    `labels_i64` int64 [R_lab][T_in] (either may be None), `n_in_i64` / `n_out_i64` int64 device vectors of R_trk + R_lab entries
+    (tracks first).  Returns (tracks fp64 [R_trk][T_out] or None, labels int64 [R_lab][T_out] or None).  No synchronisation."""
+    _dev(tracks_f64, labels_i64, n_in_i64, n_out_i64)
+    if tracks_f64 is None and labels_i64 is None:
+        raise _lib.AptaiHipError("warp_targets: neither tracks nor labels")
+    for t, dt, what in ((tracks_f64, torch.float64, "tracks fp64"), (labels_i64, torch.int64, "labels int64")):
+        if t is not None and (t.dtype != dt or t.dim() != 2 or not t.is_contiguous()):
+            raise _lib.AptaiHipError(f"warp_targets: contiguous {what} [rows][T_in] expected")
+    if tracks_f64 is not None and labels_i64 is not None and tracks_f64.shape[1] != labels_i64.shape[1]:
+        raise _lib.AptaiHipError("warp_targets: tracks and labels must have the same width")
+    some = tracks_f64 if tracks_f64 is not None else labels_i64
+    R_trk = 0 if tracks_f64 is None else tracks_f64.shape[0]
+    R_lab = 0 if labels_i64 is None else labels_i64.shape[0]
+    T_in, T_out = some.shape[1], int(T_out)
+    _i64_vec(n_in_i64, R_trk + R_lab, "warp_targets", "n_in")
+    _i64_vec(n_out_i64, R_trk + R_lab, "warp_targets", "n_out")
+    ld_out = max(T_out, 1)
+    trk_out = None if tracks_f64 is None else torch.empty((R_trk, ld_out), device=some.device, dtype=torch.float64)[:, :T_out]
+    lab_out = None if labels_i64 is None else torch.empty((R_lab, ld_out), device=some.device, dtype=torch.int64)[:, :T_out]
+    _lib.call("aptai_warp_targets", _ptr(tracks_f64), R_trk, _ptr(labels_i64), R_lab, T_in, T_in,
+              n_in_i64.data_ptr(), n_out_i64.data_ptr(), _ptr(trk_out), _ptr(lab_out), ld_out, T_out, _stream())
+    return trk_out, lab_out
 
 
 def wave_normalize(x, lens_i64, ncols=None):

@@ -49,8 +49,8 @@ class SyntheticHPRC(torch.utils.data.Dataset):
                 "tvs_norm_49hz": {k: g.randn(T) for k in hostlogic.TV_NAMES}}
 
 
-def _to_device(batch_x, device, frontend=None, host_lengths=False):
-    return loops.to_device(batch_x, device, frontend, "audio_inputs", "audio_lengths", host_lengths)
+def _to_device(batch_x, device, frontend=None, host_lengths=False, augment=False):
+    return loops.to_device(batch_x, device, frontend, "audio_inputs", "audio_lengths", host_lengths, augment)
 
 
 def load_model_optimizer(args_cfg):
@@ -72,9 +72,10 @@ def train(cfg, model, optimizer, lr_scheduler, train_dataloader, valid_dataloade
             if getattr(cfg, "graphed", False):
                 # the runners take the collate_fn's HOST batch; with a front end that runs eagerly first, and its output is the
                 # device batch the runners take as well
-                outputs = run.graphed_step(batch_x if frontend is None else _to_device(batch_x, cfg.device, frontend, host_lengths=True))
+                outputs = run.graphed_step(batch_x if frontend is None else _to_device(batch_x, cfg.device, frontend, host_lengths=True,
+                                                                                             augment=True))
             else:
-                batch_x = _to_device(batch_x, cfg.device, frontend)
+                batch_x = _to_device(batch_x, cfg.device, frontend, augment=True)          # cfg.speed_perturb: the train step only
                 outputs = run.eager_step(lambda: model(epoch, **batch_x))
             log(f"\tepoch {epoch + 1} ~ batch {batch_idx + 1}/{len(train_dataloader)}, train_loss: {float(outputs['loss'].detach()):.4f}, "
                 f"train_mse_loss: {float(outputs['mse_loss'].detach()):.4f}, train_ce_loss: {float(outputs['ce_loss'].detach()):.4f}, "
@@ -216,7 +217,7 @@ def main(argv=None):
         model, optimizer, lr_scheduler = load_model_optimizer(cfg)
     train_ds = SyntheticHPRC(a.steps_per_epoch * a.batch_size, a.seconds, vary_length=True, seed=1, cfg=w2v, source_rate=a.source_rate)
     val_ds = SyntheticHPRC(a.val_items, a.seconds, vary_length=True, seed=2, cfg=w2v, source_rate=a.source_rate)
-    collate = hostlogic.collate_aptai_raw if (a.source_rate or a.normalize_audio) else hostlogic.collate_aptai
+    collate = hostlogic.collate_aptai_raw if loops.uses_frontend(a) else hostlogic.collate_aptai
     train_dl = torch.utils.data.DataLoader(train_ds, batch_size=a.batch_size, shuffle=True, drop_last=True, collate_fn=collate)
     val_dl = torch.utils.data.DataLoader(val_ds, batch_size=1, shuffle=False, collate_fn=collate)
     return train(cfg, model, optimizer, lr_scheduler, train_dl, val_dl, "synthetic", a.out)

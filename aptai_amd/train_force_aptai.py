@@ -70,11 +70,11 @@ def train(cfg, model, optimizer, lr_scheduler, train_dataloader, valid_dataloade
         it = iter(train_dataloader)
         nxt = next(it, None)
         if nxt is not None:
-            nxt = _to_device(nxt, cfg.device, frontend)
+            nxt = _to_device(nxt, cfg.device, frontend, augment=True)          # cfg.speed_perturb: the train batches only
         while nxt is not None:
             batch_x, nxt = nxt, next(it, None)
             if nxt is not None:
-                nxt = _to_device(nxt, cfg.device, frontend)
+                nxt = _to_device(nxt, cfg.device, frontend, augment=True)
             ahead = (nxt["audio_inputs"], nxt["audio_lengths"]) if (pipelined and nxt is not None) else None
             outputs = run.eager_step(lambda: model(epoch, **batch_x, _prefetch_next=ahead))
             log(f"\tepoch {epoch + 1} ~ batch {run.steps}/{len(train_dataloader)}, train_loss: {float(outputs['loss'].detach()):.4f}, "
@@ -187,7 +187,7 @@ def main(argv=None):
     train_ds = SyntheticHPRCWithLabels(a.steps_per_epoch * a.batch_size, a.seconds, seed=1, cfg=w2v, vocab_size=len(cfg.vocab),
                                        source_rate=a.source_rate)
     val_ds = SyntheticHPRCWithLabels(a.val_items, a.seconds, seed=2, cfg=w2v, vocab_size=len(cfg.vocab), source_rate=a.source_rate)
-    coll = collate_raw if (a.source_rate or a.normalize_audio) else collate
+    coll = collate_raw if loops.uses_frontend(a) else collate
     train_dl = torch.utils.data.DataLoader(train_ds, batch_size=a.batch_size, shuffle=True, drop_last=True, collate_fn=coll)
     val_dl = torch.utils.data.DataLoader(val_ds, batch_size=1, shuffle=False, collate_fn=coll)
     return train(cfg, model, optimizer, lr_scheduler, train_dl, val_dl, "synthetic", a.out)

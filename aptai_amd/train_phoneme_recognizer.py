@@ -58,8 +58,8 @@ class SyntheticCommonPhone(torch.utils.data.Dataset):
                 "phoneme_label": g.randint(1, self.V, size=int(g.randint(lo, hi + 1))).astype(np.int32)}
 
 
-def _to_device(batch_x, device, frontend=None, host_lengths=False):
-    return loops.to_device(batch_x, device, frontend, "input_values", "input_lengths", host_lengths)
+def _to_device(batch_x, device, frontend=None, host_lengths=False, augment=False):
+    return loops.to_device(batch_x, device, frontend, "input_values", "input_lengths", host_lengths, augment)
 
 
 def load_model_optimizer(args_cfg, vocab):
@@ -111,9 +111,9 @@ def train(cfg, model, optimizer, lr_scheduler, vocab, train_dataloader, valid_da
             if batch_idx not in subset_random:
                 continue
             if getattr(cfg, "graphed", False):
-                outputs = run.graphed_step(_to_device(batch_x, cfg.device, frontend, host_lengths=True))
+                outputs = run.graphed_step(_to_device(batch_x, cfg.device, frontend, host_lengths=True, augment=True))
             else:
-                batch_x = _to_device(batch_x, cfg.device, frontend)
+                batch_x = _to_device(batch_x, cfg.device, frontend, augment=True)          # cfg.speed_perturb: the train step only
                 outputs = run.eager_step(lambda: model(**batch_x))
             log(f"\tepoch {epoch + 1} ~ batch {run.steps}/{epoch_train_steps}, train_loss: {float(outputs['loss'].detach()):.4f}")
         epoch_log = run.end_epoch(epoch, lambda: validate(model, cfg.device, vocab, epoch, valid_dataloader,
@@ -228,7 +228,7 @@ def main(argv=None):
                           learning_rate=a.learning_rate, save_all_epochs=a.save_all_epochs, huggingface_model_id=model_dir,
                           pretrain_cfg=w2v, **loops.shared_arguments(a))
         model, optimizer, lr_scheduler = load_model_optimizer(cfg, vocab)
-    collate = hostlogic.collate_pr_raw if (a.source_rate or a.normalize_audio) else hostlogic.collate_pr
+    collate = hostlogic.collate_pr_raw if loops.uses_frontend(a) else hostlogic.collate_pr
     tr = torch.utils.data.DataLoader(SyntheticCommonPhone(a.train_items, a.seconds, len(vocab), seed=1, source_rate=a.source_rate),
                                      batch_size=a.batch_size, shuffle=True, drop_last=True, collate_fn=collate)
     va = torch.utils.data.DataLoader(SyntheticCommonPhone(a.val_items, a.seconds, len(vocab), seed=2, source_rate=a.source_rate),

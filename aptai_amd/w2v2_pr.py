@@ -95,6 +95,8 @@ class Wav2Vec2_PR(nn.Module):
 
     # ------------------------------------------------------------------ training forward (models/w2v2_pr.py:40-88)
     def forward(self, input_values, input_lengths, phoneme_labels):
+        """A row with fewer frames than its labels need (speed perturbation shortens the audio, not the transcript) has an infinite
+        CTC loss; with `ctc_zero_infinity` (the training loop sets it) it counts as zero, loss and gradient."""
         cfg = self.wav2vec2.config
         with batch_invariant_scope(self.wav2vec2, self.batch_invariant and not self.training):
             outputs = self.wav2vec2(input_values, attention_mask=input_lengths[:, None], return_dict=True, output_hidden_states=True)

@@ -636,6 +636,32 @@ int aptai_eval_edit_distance(const int32_t* a, int64_t lda, const int32_t* a_len
 int aptai_resample_batch(const void* src, int src_is_int16, const int64_t* offsets, int64_t B, const float* taps, const int32_t* first,
                          int64_t orig, int64_t new_, int64_t Kc, int64_t width, const int64_t* out_start, float* out, int64_t ld,
                          int64_t ncols, void* stream);
+/* aptai_resample_batch with a ratio per row (speed perturbation: row b at speed f is the source taken as sampled at
+ * round(rate f) and resampled to the target rate).  ratio int32 [B] on the device: row b runs at entry ratio[b] of `table`, int32
+ * [n_ratios][8] on the device, n_ratios <= APTAI_RESAMPLE_MAX_RATIOS; an entry is {orig, new, Kc, width, taps_off, first_off, 0, 0}
+ * and its bank is taps[taps_off .. taps_off + new Kc) / first[first_off .. first_off + new) of the concatenated fp32 / int32 arrays
+ * (n_taps / n_first entries; an entry with orig == new copies and has no bank).  table_host and ratio_host are the same words in
+ * host memory: the entry point checks them (every index inside the table, every bank inside the arrays) and takes the launch
+ * geometry from them - the tile is the smallest one that aptai_resample_batch would pick for a ratio present in the batch.  Row b
+ * has ceil(new len / orig) samples of ITS ratio and holds, bit for bit, what aptai_resample_batch writes for that utterance alone
+ * with that bank: the sum is the same fma sequence whatever the tile, the neighbours, the crop, or whether a bank is staged in LDS
+ * (decided per row: one that fits is, another is read through L2).  src, offsets, out_start, out, ld, ncols: as above. */
+#define APTAI_RESAMPLE_MAX_RATIOS 8
+int aptai_resample_batch_multi(const void* src, int src_is_int16, const int64_t* offsets, int64_t B, const float* taps, int64_t n_taps,
+                               const int32_t* first, int64_t n_first, const int32_t* table, const int32_t* table_host, int64_t n_ratios,
+                               const int32_t* ratio, const int32_t* ratio_host, const int64_t* out_start, float* out, int64_t ld,
+                               int64_t ncols, void* stream);
+/* The frame-level targets of a batch stretched with its audio, one launch: R_trk rows of fp64 tracks [R_trk][ld_in] and R_lab rows
+ * of int64 frame labels [R_lab][ld_in]; row r (tracks first, then labels) goes from n_in[r] to n_out[r] frames (int64 on the
+ * device, R_trk + R_lab entries, clamped to [0, T_in] / [0, T_out]).  Positions are numpy.linspace(0, n_in - 1, n_out):
+ * p_i = i ((n_in - 1) / (n_out - 1)), the last one n_in - 1 exactly, 0 when n_out == 1.  Tracks: hostlogic.interpolate_signal
+ * operation for operation in fp64 without contraction, out[i] = x[lo] + (x[hi] - x[lo]) w with lo = clip(floor(p), 0,
+ * max(n_in - 2, 0)), w = p - lo, hi = min(lo + 1, n_in - 1); -100 where x[lo] == -100 or (w > 0 and x[hi] == -100); columns
+ * n_out .. T_out-1 are -100.  Labels: out[i] = lab[min(floor(p_i + 0.5), n_in - 1)], padding 0.  n_in == n_out copies the row;
+ * n_in == 0 gives a row of padding.  Equal inputs give the bits of hostlogic.warp_track / warp_frame_labels. */
+int aptai_warp_targets(const double* tracks, int64_t R_trk, const int64_t* labels, int64_t R_lab, int64_t ld_in, int64_t T_in,
+                       const int64_t* n_in, const int64_t* n_out, double* tracks_out, int64_t* labels_out, int64_t ld_out, int64_t T_out,
+                       void* stream);
 /* Wav2Vec2FeatureExtractor.zero_mean_unit_var_norm in place on x fp32 [B][ld]: y = (x - mean) / sqrt(var + 1e-7) over the first
  * lens[b] samples of row b (lens int64 [B] on the device, clamped to [0, ncols]), population variance; the rest of the row is
  * not touched.  Statistics and the affine step in fp64 (sums of x - x[b][0], so a large offset does not cancel), summed in a
