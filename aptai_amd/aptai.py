@@ -21,7 +21,7 @@ from .config import W2V2Config
 from . import hostlogic
 from .hostlogic import TV_NAMES
 from .modules import LowPassFilterLayer
-from .wav2vec2 import Wav2Vec2Model, _seed, batch_invariant_scope
+from .wav2vec2 import _APTAI_HEADS_STREAM, Wav2Vec2Model, _seed, batch_invariant_scope
 
 _PADN = 64      # head Linears run on the MFMA GEMM with N padded to 64
 
@@ -126,7 +126,7 @@ class APTAI(nn.Module):
             phn_targets = torch.zeros((g.B, g.T), device=dev, dtype=torch.long)
         tr = self.training
         st = SimpleNamespace(g=g, p_tv=self.tv_head[0].p if tr else 0.0, p_ph=self.phn_head[0].p if tr else 0.0,
-                             seed=_seed(self.wav2vec2.base_seed, self.wav2vec2._step, 999), taps=self.tv_lowpass.taps(),
+                             seed=_seed(self.wav2vec2.base_seed, self.wav2vec2._step, _APTAI_HEADS_STREAM), taps=self.tv_lowpass.taps(),
                              tv_tgt=tv_targets.contiguous(), phn_tgt=phn_targets.contiguous(), w_mse=0.5, w_ce=0.5)
         if self.dp_loss_norm is not None and tr:
             self.dp_loss_norm.begin(st.tv_tgt, st.phn_tgt)       # 2-scalar all-reduce under the head GEMMs

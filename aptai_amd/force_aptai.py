@@ -24,7 +24,7 @@ from .config import W2V2Config, load_model_cfg
 from .hostlogic import TV_NAMES
 from .modules import CrossAttention, ForwardSumLoss, LowPassFilterLayer, PositionalEncoding, RNN
 from .w2v2_pr import Wav2Vec2_PR
-from .wav2vec2 import _seed, batch_invariant_scope
+from .wav2vec2 import _FORCE_HEADS_STREAM, _seed, batch_invariant_scope
 
 _NPHN = 60                              # the reference's max_phn_seq_len (models/force_aptai.py:36): the default slot count
 MAX_PHN_SLOTS = ops.XATTN_MAX_SLOTS     # 255: what the wide softmax pair and the CTC kernels (256 classes, 511 states) hold
@@ -286,7 +286,7 @@ class Force_APTAI(nn.Module):
                 ids = torch.tensor(np.array(padded), dtype=torch.int32, device=dev)
                 nlen = torch.tensor([len(l) for l in phn_pred_list], dtype=torch.int32, device=dev)
         # with the fp32 residual stream the heads read the UNROUNDED last hidden state (the fp32 GEMM takes either dtype)
-        ac = getattr(out, "_flat_last_f32", None)
+        ac = out._flat_last_f32
         return SimpleNamespace(g=out._geom, ac=ac if ac is not None else out._flat_last, ids=ids, nlen=nlen, frame_lens=frame_lens,
                                step=pr.wav2vec2._step, nlen_full=nlen_full)
 
@@ -309,7 +309,7 @@ class Force_APTAI(nn.Module):
         cur = torch.cuda.current_stream(dev)
         self._enc_stream.wait_stream(cur)                              # the inputs (and the previous step's frees) are ordered first
         key = (tuple(audio_inputs.shape), tuple(audio_lengths.shape), audio_inputs.dtype, audio_lengths.dtype,
-               getattr(self.w2v2_pr.wav2vec2, "_encoder_precision", "bf16"))
+               self.w2v2_pr.wav2vec2.encoder_precision)
         use_graph = os.environ.get("APTAI_FORCE_ENC_GRAPH", "1") != "0"
         if self.batch_invariant and not self.training:
             use_graph = False                                          # the captured pass is a training device: batch-invariant evaluation encodes eagerly
@@ -381,7 +381,7 @@ class Force_APTAI(nn.Module):
         st = SimpleNamespace(g=g, ids=ids, nphn=self.max_phn_seq_len, pe=self.pe_phn.pe.reshape(self.max_phn_seq_len, -1).contiguous(),
                              taps=self.tv_lowpass.taps(),
                              p_hid=self.hidden_drop if tr else 0.0, p_rnn=self.rnn_drop if tr else 0.0,
-                             seed=_seed(pr.wav2vec2.base_seed, step, 4242),
+                             seed=_seed(pr.wav2vec2.base_seed, step, _FORCE_HEADS_STREAM),
                              tv_tgt=tv_targets.contiguous(), fs_targets=consts["fs_targets"], frame_lens=frame_lens, rnn_lens=rnn_lens,
                              text_lens=nlen, vocab_sizes=nlen + 1, readout=self._readout(), mono_targets=consts["mono_targets"])
         if getattr(self, "dp_loss_norm", None) is not None and tr:

@@ -32,7 +32,8 @@ import torch
 from . import _lib, hostlogic, ops
 from .aptai import APTAI, heads_bwd, heads_fwd
 from .w2v2_pr import Wav2Vec2_PR, pr_head_bwd, pr_head_fwd
-from .wav2vec2 import _FEATURE_MASK_STREAM, _TIME_MASK_STREAM, _FinalLNImpl, _FrontImpl, _LayerImpl, _seed
+from .wav2vec2 import (_APTAI_HEADS_STREAM, _FEATURE_MASK_STREAM, _LAYER_STREAM_BASE, _PR_HEAD_STREAM, _TIME_MASK_STREAM, _FinalLNImpl,
+                       _FrontImpl, _LayerImpl, _seed)
 
 
 # thread-local capture: under data parallelism the process group's watchdog thread polls its events while this thread captures,
@@ -158,7 +159,7 @@ class GraphedAPTAIStep(_CapturingRunner):
         self.set_batch(batch)
         # one eager step first: allocates every persistent scratch buffer, loads the code objects and sets the kernel
         # attributes outside of stream capture
-        if getattr(w, "_cache_mode", None) == "frozen":          # another runner of this model froze the cache: the eager step rebuilds
+        if w._cache_mode == "frozen":                            # another runner of this model froze the cache: the eager step rebuilds
             w._cache_mode = None
         model.zero_grad(set_to_none=True)
         (model(**batch) if self.kind == "pr" else model(0, **batch))["loss"].backward()
@@ -271,22 +272,15 @@ class GraphedAPTAIStep(_CapturingRunner):
             if not getattr(self.opt, "publishes_copies", False):     # else the optimiser kernel refreshes the copies itself
                 w._refresh_layer_copies(force=True)
             self.lw = [w._layer_weights(i) for i in range(L)]
-            fp, pc = w.feature_projection, w.encoder.pos_conv_embed.conv
-            w._cached(("proj",), [fp.projection.weight], lambda: ops.cast_bf16(fp.projection.weight))
-            w._cached(("posconv",), [pc.parametrizations.weight.original0, pc.parametrizations.weight.original1],
-                      lambda: ops.posconv_weight(pc.parametrizations.weight.original1,
-                                                 pc.parametrizations.weight.original0.reshape(-1),
-                                                 cfg.num_conv_pos_embedding_groups))
+            w._proj_weight()
+            w._posconv_weights()
         w._cache_mode = "frozen"
 
         # -- front: conv stack (frozen) + projection + masking + positional conv (+ LN)
-        embed = getattr(w, "masked_spec_embed", None)
+        self.fparams = w._front_params(with_embed=True)
+        embed = self.fparams.embed
         self.front = _FrontImpl(cfg, g, self.lens_i32, self.spec if embed is not None else None, True, _seed(seed, 1), w,
                                 feat=self.feat)
-        fp, pc = w.feature_projection, w.encoder.pos_conv_embed.conv
-        self.fparams = [fp.layer_norm.weight, fp.layer_norm.bias, fp.projection.weight, fp.projection.bias, embed,
-                        pc.parametrizations.weight.original0, pc.parametrizations.weight.original1, pc.bias,
-                        w.encoder.layer_norm.weight, w.encoder.layer_norm.bias]
         self.g_front = mk()
         with torch.cuda.graph(self.g_front, pool=pool, stream=self._cap_stream, capture_error_mode=_CAPTURE_MODE):
             if embed is not None and cfg.apply_spec_augment and cfg.mask_time_prob > 0:
@@ -301,10 +295,10 @@ class GraphedAPTAIStep(_CapturingRunner):
 
         # -- layers forward
         self.impl, self.s_layer, self.g_fwd, self.lparams = [], [], [], []
-        for i, layer in enumerate(w.encoder.layers):
+        for i in range(L):
             wt, lin = self.lw[i]
-            impl = _LayerImpl(cfg, g, self.lens_i32, wt, True, _seed(seed, 100 + i))
-            params = [layer.layer_norm.weight, layer.layer_norm.bias, layer.final_layer_norm.weight, layer.final_layer_norm.bias] + lin
+            impl = _LayerImpl(cfg, g, self.lens_i32, wt, True, _seed(seed, _LAYER_STREAM_BASE + i))
+            params = w._layer_ln_params(i) + lin
             gr = mk()
             with torch.cuda.graph(gr, pool=pool, stream=self._cap_stream, capture_error_mode=_CAPTURE_MODE):
                 (y,), s = impl.fwd(self.X[i], params, True)
@@ -316,12 +310,12 @@ class GraphedAPTAIStep(_CapturingRunner):
         self.loss_norm = None
         if self.kind == "pr":
             self.hparams = [model.pr_head.weight, model.pr_head.bias]
-            self.st_heads = SimpleNamespace(g=g, p_final=model.dropout.p, seed=_seed(seed, 777), targets=self.labels,
+            self.st_heads = SimpleNamespace(g=g, p_final=model.dropout.p, seed=_seed(seed, _PR_HEAD_STREAM), targets=self.labels,
                                             state_lens=self.state_lens, target_lens=self.target_lens, blank=getattr(cfg, "blank", 0),
                                             reduction=cfg.ctc_loss_reduction, zero_infinity=cfg.ctc_zero_infinity)
         else:
             self.hparams = [model.tv_head[2].weight, model.tv_head[2].bias, model.phn_head[2].weight, model.phn_head[2].bias]
-            self.st_heads = SimpleNamespace(g=g, p_tv=model.tv_head[0].p, p_ph=model.phn_head[0].p, seed=_seed(seed, 999),
+            self.st_heads = SimpleNamespace(g=g, p_tv=model.tv_head[0].p, p_ph=model.phn_head[0].p, seed=_seed(seed, _APTAI_HEADS_STREAM),
                                             taps=model.tv_lowpass.taps(), tv_tgt=self.tv_tgt, phn_tgt=self.phn_tgt, w_mse=0.5, w_ce=0.5)
             # data parallel: the loss backward inside the tail graph reads the global valid counts / world from this static buffer
             self.loss_norm = getattr(model, "dp_loss_norm", None)
@@ -419,7 +413,7 @@ class GraphedAPTAIStep(_CapturingRunner):
             self.set_batch(batch)
         keep = self._host_randomness()
         L = self.cfg.num_hidden_layers
-        self.w._train_marker = getattr(self.w, "_train_marker", 0) + 1     # eval-mode weight copies built before this step are stale
+        self.w._train_marker += 1                                # eval-mode weight copies built before this step are stale
         if self.loss_norm is not None:
             self.loss_norm.begin(self.tv_tgt, self.phn_tgt)      # travels under the encoder forward
         # Optimiser under the backward pass (APTAI_ADAM_OVERLAP=1; experiment, OFF by default; single GPU, aptai_amd.optim.Adam): a

@@ -590,6 +590,11 @@ class CastPlan:
     persistent, so a plan replays unchanged inside a hipGraph; sources are re-read on every run (parameters move only
     through in-place optimiser updates, so their addresses are stable; `stale()` detects re-allocated parameters)."""
 
+    optimizer_synced = False    # the optimiser's own kernel writes the destinations with every update
+    after_training = False      # the last run() came from a training forward: an optimiser step since is unseen
+    version = None              # the parameter versions the destinations were last built from
+    entries = None              # per-layer views of the destinations
+
     def __init__(self, jobs):
         # jobs: list of (src fp32 tensor, dst tensor [bf16 or fp32])
         self.jobs = list(jobs)
@@ -760,19 +765,23 @@ def spec_augment_mask(frame_lens_i32, B, T, mask_prob, mask_length, min_masks, s
     return m
 
 
-def frame_mask_fwd(h, lens_i32, spec_mask_u8, embed, B, Tp, T, H):
-    _dev(h, lens_i32, spec_mask_u8, embed)
-    _lib.call("aptai_frame_mask_fwd", h.data_ptr(), lens_i32.data_ptr(), _ptr(spec_mask_u8), _ptr(embed), B, Tp, T, H, _stream())
+def frame_mask_fwd(h, lens_i32, spec_mask_u8, embed, B, Tp, T, H, feat_mask_u8=None):
+    """SpecAugment time fill + padded-frame zeroing, in place, one pass; feat_mask_u8 [B][H] uint8 adds SpecAugment along the hidden
+    axis (channels zeroed on every valid frame after the time fill), None launches the time-only entry."""
+    _dev(h, lens_i32, spec_mask_u8, embed, feat_mask_u8)
+    entry, feat = ("aptai_frame_mask_fwd", ()) if feat_mask_u8 is None else ("aptai_frame_feature_mask_fwd", (feat_mask_u8.data_ptr(),))
+    _lib.call(entry, h.data_ptr(), lens_i32.data_ptr(), _ptr(spec_mask_u8), _ptr(embed), *feat, B, Tp, T, H, _stream())
 
 
-def frame_mask_bwd(dy, lens_i32, spec_mask_u8, B, Tp, T, H, want_dembed):
-    _dev(dy, lens_i32, spec_mask_u8)
+def frame_mask_bwd(dy, lens_i32, spec_mask_u8, B, Tp, T, H, want_dembed, feat_mask_u8=None):
+    """Backward of frame_mask_fwd, in place on dy; returns dembed (None without a time mask or when not wanted)."""
+    _dev(dy, lens_i32, spec_mask_u8, feat_mask_u8)
     dembed = ws = None
     if want_dembed and spec_mask_u8 is not None:
         dembed = torch.empty(H, device=dy.device, dtype=torch.float32)
         ws = _ws(_lib.lib().aptai_frame_mask_bwd_workspace_bytes(B, Tp, H), dy.device)
-    _lib.call("aptai_frame_mask_bwd", dy.data_ptr(), lens_i32.data_ptr(), _ptr(spec_mask_u8), _ptr(dembed), _ptr(ws), B, Tp, T, H,
-              _stream())
+    entry, feat = ("aptai_frame_mask_bwd", ()) if feat_mask_u8 is None else ("aptai_frame_feature_mask_bwd", (feat_mask_u8.data_ptr(),))
+    _lib.call(entry, dy.data_ptr(), lens_i32.data_ptr(), _ptr(spec_mask_u8), *feat, _ptr(dembed), _ptr(ws), B, Tp, T, H, _stream())
     return dembed
 
 
@@ -786,26 +795,6 @@ def feature_mask_span_check(H, mask_prob, mask_length, min_masks):
     if most > SPEC_MAX_SPANS:
         raise ValueError(f"mask_feature_prob={mask_prob}, mask_feature_length={mask_length}, mask_feature_min_masks={min_masks} "
                          f"ask for up to {most} spans over {H} channels; the device sampler draws at most {SPEC_MAX_SPANS} per row")
-
-
-def frame_feature_mask_fwd(h, lens_i32, spec_mask_u8, embed, feat_mask_u8, B, Tp, T, H):
-    """frame_mask_fwd plus SpecAugment along the hidden axis: feat_mask_u8 [B][H] uint8 (None = none), channels zeroed on every
-    valid frame after the time fill.  In place, one pass."""
-    _dev(h, lens_i32, spec_mask_u8, embed, feat_mask_u8)
-    _lib.call("aptai_frame_feature_mask_fwd", h.data_ptr(), lens_i32.data_ptr(), _ptr(spec_mask_u8), _ptr(embed), _ptr(feat_mask_u8),
-              B, Tp, T, H, _stream())
-
-
-def frame_feature_mask_bwd(dy, lens_i32, spec_mask_u8, feat_mask_u8, B, Tp, T, H, want_dembed):
-    """Backward of frame_feature_mask_fwd, in place on dy; returns dembed (None without a time mask or when not wanted)."""
-    _dev(dy, lens_i32, spec_mask_u8, feat_mask_u8)
-    dembed = ws = None
-    if want_dembed and spec_mask_u8 is not None:
-        dembed = torch.empty(H, device=dy.device, dtype=torch.float32)
-        ws = _ws(_lib.lib().aptai_frame_mask_bwd_workspace_bytes(B, Tp, H), dy.device)
-    _lib.call("aptai_frame_feature_mask_bwd", dy.data_ptr(), lens_i32.data_ptr(), _ptr(spec_mask_u8), _ptr(feat_mask_u8), _ptr(dembed),
-              _ptr(ws), B, Tp, T, H, _stream())
-    return dembed
 
 
 def colsum(x, rows, N, *, ld=None, out=None, accumulate=False):

@@ -21,7 +21,7 @@ import torch.nn as nn
 
 from . import hostlogic, ops
 from .modules import _LinearFn
-from .wav2vec2 import Wav2Vec2Model, _round_up, _seed, batch_invariant_scope
+from .wav2vec2 import _PR_HEAD_STREAM, Wav2Vec2Model, _round_up, _seed, batch_invariant_scope
 
 
 def pr_head_fwd(h, w, b, st):
@@ -105,7 +105,7 @@ class Wav2Vec2_PR(nn.Module):
         state_lens = self.wav2vec2._get_feat_extract_output_lengths(input_lengths)
         target_lengths = hostlogic.ctc_target_lengths(phoneme_labels)          # count of labels >= 0 (:62-70)
         st = SimpleNamespace(g=g, p_final=self.dropout.p if self.training else 0.0,
-                             seed=_seed(self.wav2vec2.base_seed, self.wav2vec2._step, 777),
+                             seed=_seed(self.wav2vec2.base_seed, self.wav2vec2._step, _PR_HEAD_STREAM),
                              targets=phoneme_labels.to(dev).to(torch.int32).contiguous(),
                              state_lens=state_lens.to(dev).to(torch.int32).contiguous(),
                              target_lens=target_lengths.to(dev).to(torch.int32).contiguous(), blank=getattr(cfg, "blank", 0),
@@ -131,8 +131,8 @@ class Wav2Vec2_PR(nn.Module):
             bp[:V] = self.pr_head.bias.detach()
             return wp, bp
         # padded bf16 head weight: rebuilt only when the parameters moved (eval mode trusts Tensor._version, see _cached)
-        h32 = getattr(out, "_flat_last_f32", None)
-        if h32 is not None and getattr(self.wav2vec2, "_encoder_precision", "bf16") in ("f32x3", "f32x6"):
+        h32 = out._flat_last_f32
+        if h32 is not None and self.wav2vec2.encoder_precision in ("f32x3", "f32x6"):
             # exact inference pass: the head is an fp32 product too (fp32 matrix instruction), so the frame argmax of the decode
             # sees fp32 logits
             def build32():
@@ -222,7 +222,7 @@ class Wav2Vec2_PR(nn.Module):
         last = out.last_hidden_state
         inter = out.hidden_states[intermediate_hidden]
         latter = out.hidden_states[latter_hidden]
-        feats = getattr(out, "_features", None)
+        feats = out._features
         return {'features_hidden': None if feats is None else feats.view(g.B, g.Tp, -1)[:, :g.T].permute(0, 2, 1),
                 'last_transf_hidden': last.permute(0, 2, 1),
                 'phoneme_logits_last': head(last), 'phoneme_logits_inter': head(inter), 'phoneme_logits_latter': head(latter),

@@ -14,8 +14,8 @@ import contextlib
 import json
 import math
 import os
+from collections import namedtuple
 from types import SimpleNamespace
-from typing import List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -127,14 +127,25 @@ def _seed(base: int, *ids: int) -> int:
     return s ^ (s >> 31)
 
 
+# The seed streams, as ids of _seed(parent seed, id); the values are part of every recorded run and never change.  Inside one layer
+# (parent: the layer's seed), inside the front end (the front's seed), then below the step seed: the two SpecAugment masks of the device
+# sampler (drawn independently of each other), layer i = base + i, and the heads of Wav2Vec2_PR, APTAI and Force_APTAI.
+_ATTN_DROPOUT_STREAM, _OUT_PROJ_DROPOUT_STREAM, _ACT_DROPOUT_STREAM, _FFN2_DROPOUT_STREAM = 1, 2, 3, 4
+_PROJ_DROPOUT_STREAM, _FRONT_DROPOUT_STREAM = 11, 12
+_TIME_MASK_STREAM, _FEATURE_MASK_STREAM = 77, 78
+_LAYER_STREAM_BASE = 100
+_PR_HEAD_STREAM, _APTAI_HEADS_STREAM, _FORCE_HEADS_STREAM = 777, 999, 4242
+
+
 # =================================================================================== encoder layer
 class _LayerImpl:
-    """One transformer layer (HF:575-654).  post-LN (base) or pre-LN (do_stable_layer_norm, large)."""
+    """One transformer layer (HF:575-654).  post-LN (base) or pre-LN (do_stable_layer_norm, large).  ``mx``: MXFP8 weight copies (the
+    inference-only _fwd_mxfp8); ``want_attn`` (output_attentions): fwd returns the layer's attention map as a second output;
+    ``attn_state``: shared by the layers of one forward call (.seen = a layer above got a gradient on its map)."""
 
-    def __init__(self, cfg: W2V2Config, geom, lens_i32, w, training: bool, seed: int):
+    def __init__(self, cfg: W2V2Config, geom, lens_i32, w, training: bool, seed: int, *, mx=None, want_attn=False, attn_state=None):
         self.cfg, self.g, self.lens, self.w, self.training, self.seed = cfg, geom, lens_i32, w, training, seed
-        self.want_attn = False      # output_attentions: fwd returns the layer's attention map as a second output
-        self.attn_state = None      # shared by the layers of one forward call: .seen = a layer above got a gradient on its map
+        self.mx, self.want_attn, self.attn_state = mx, want_attn, attn_state
 
     # params: ln1.w ln1.b ln2.w ln2.b, then the 12 fp32 linear parameters (q,k,v weights; q,k,v biases; out w,b;
     # ffn1 w,b; ffn2 w,b).  The forward reads their cached bf16 copies in `w`; the backward returns their gradients.
@@ -148,9 +159,8 @@ class _LayerImpl:
         p_att = cfg.attention_dropout if tr else 0.0
         s = SimpleNamespace(x=x)
         pre = cfg.do_stable_layer_norm
-        mx = getattr(self, "mx", None)
-        if mx is not None and not need:
-            return self._fwd_mxfp8(x, params, mx)
+        if self.mx is not None and not need:
+            return self._fwd_mxfp8(x, params, self.mx)
         if pre:
             n1, s.m1, s.r1 = ops.layernorm_fwd(x, ln1w, ln1b, cfg.layer_norm_eps, save_stats=need)
             attn_in = n1
@@ -161,12 +171,12 @@ class _LayerImpl:
         # their exp2 arguments directly (q_prescaled)
         s.qkv = ops.gemm(attn_in, w.wqkv, M, 3 * H, H, bias=w.bqkv, colscale=(H, ops.attention_qscale(H, cfg.num_attention_heads)))
         s.ctx, s.lse = ops.attention_fwd(s.qkv, self.lens, g.B, g.Tp, H, cfg.num_attention_heads, q_prescaled=True, dropout_p=p_att,
-                                         seed=_seed(self.seed, 1), save_lse=need or self.want_attn)
+                                         seed=_seed(self.seed, _ATTN_DROPOUT_STREAM), save_lse=need or self.want_attn)
         probs = None
         if self.want_attn:          # HF eager attention's second result: the softmax after dropout, with the fused kernel's own mask
             probs = ops.attention_probs_fwd(s.qkv, self.lens, s.lse[0], g.B, g.Tp, H, cfg.num_attention_heads, q_prescaled=True,
-                                            dropout_p=p_att, seed=_seed(self.seed, 1))
-        s.s1 = ops.gemm(s.ctx, w.wo, M, H, H, bias=w.bo, residual=x, dropout_p=p_h, seed=_seed(self.seed, 2))
+                                            dropout_p=p_att, seed=_seed(self.seed, _ATTN_DROPOUT_STREAM))
+        s.s1 = ops.gemm(s.ctx, w.wo, M, H, H, bias=w.bo, residual=x, dropout_p=p_h, seed=_seed(self.seed, _OUT_PROJ_DROPOUT_STREAM))
         if pre:
             ffn_in, s.m2, s.r2 = ops.layernorm_fwd(s.s1, ln2w, ln2b, cfg.layer_norm_eps, save_stats=need)
             s.n2 = ffn_in
@@ -176,9 +186,9 @@ class _LayerImpl:
         s.u = torch.empty((M, I), device=x.device, dtype=torch.bfloat16) if need else None
         # with gradients: s.u holds dropmask/(1-p) * gelu'(pre-activation), the factor the dgrad epilogue multiplies by
         s.hact = ops.gemm(ffn_in, w.w1, M, I, H, bias=w.b1, gelu=True, out_pre=s.u, pre_dgelu=need, dropout_p=p_a,
-                          seed=_seed(self.seed, 3))
+                          seed=_seed(self.seed, _ACT_DROPOUT_STREAM))
         res2 = s.s1 if pre else ffn_in
-        s.s2 = ops.gemm(s.hact, w.w2, M, H, I, bias=w.b2, residual=res2, dropout_p=p_h, seed=_seed(self.seed, 4))
+        s.s2 = ops.gemm(s.hact, w.w2, M, H, I, bias=w.b2, residual=res2, dropout_p=p_h, seed=_seed(self.seed, _FFN2_DROPOUT_STREAM))
         if pre:
             y = s.s2
         else:
@@ -188,34 +198,28 @@ class _LayerImpl:
         return ((y,) if probs is None else (y, probs)), (s if need else None)
 
     def fwd_f32res(self, x, x32, params):
-        """Inference only, opt-in (set_encoder_precision("bf16_f32res")): the residual stream stays in fp32 - out-proj and FFN2
-        write fp32 and add the fp32 residual in their epilogues, LayerNorm reads fp32 and hands the next GEMM a bf16 copy and the
-        next residual add an fp32 one.  GEMM operands and attention stay bf16.  Returns (y_bf16 | None, y_f32); with want_attn the layer's
-        attention map is left in self.probs."""
+        """Inference only, opt-in (set_encoder_precision("bf16_f32res")): the residual stream stays in fp32 - out-proj and FFN2 write
+        fp32 and add the fp32 residual in their epilogues, LayerNorm reads fp32 and hands the next GEMM a bf16 copy and the next residual
+        add an fp32 one.  GEMM operands and attention stay bf16.  Returns (y_bf16 | None for pre-LN, y_f32, attention map | None)."""
         cfg, g, w = self.cfg, self.g, self.w
         M, H, I = g.M, cfg.hidden_size, cfg.intermediate_size
         ln1w, ln1b, ln2w, ln2b = params[:4]
-        heads = cfg.num_attention_heads
-        qs = (H, ops.attention_qscale(H, heads))
-        if cfg.do_stable_layer_norm:                       # pre-LN (large): x32 is the un-normalised stream
-            n1, _ = ops.layernorm_fwd_f32in(x32, ln1w, ln1b, cfg.layer_norm_eps, want_f32=False)
-            qkv = ops.gemm(n1, w.wqkv, M, 3 * H, H, bias=w.bqkv, colscale=qs)
-            ctx, st = ops.attention_fwd(qkv, self.lens, g.B, g.Tp, H, heads, save_lse=self.want_attn, q_prescaled=True)
-            if self.want_attn:
-                self.probs = ops.attention_probs_fwd(qkv, self.lens, st[0], g.B, g.Tp, H, heads, q_prescaled=True)
-            s1 = ops.gemm(ctx, w.wo, M, H, H, bias=w.bo, out_f32=True, residual_f32=x32, tile=128)
-            n2, _ = ops.layernorm_fwd_f32in(s1, ln2w, ln2b, cfg.layer_norm_eps, want_f32=False)
-            u = ops.gemm(n2, w.w1, M, I, H, bias=w.b1, gelu=True)
-            return None, ops.gemm(u, w.w2, M, H, I, bias=w.b2, out_f32=True, residual_f32=s1, tile=128)
-        qkv = ops.gemm(x, w.wqkv, M, 3 * H, H, bias=w.bqkv, colscale=qs)
+        heads, eps, pre = cfg.num_attention_heads, cfg.layer_norm_eps, cfg.do_stable_layer_norm
+        attn_in = ops.layernorm_fwd_f32in(x32, ln1w, ln1b, eps, want_f32=False)[0] if pre else x
+        qkv = ops.gemm(attn_in, w.wqkv, M, 3 * H, H, bias=w.bqkv, colscale=(H, ops.attention_qscale(H, heads)))
         ctx, st = ops.attention_fwd(qkv, self.lens, g.B, g.Tp, H, heads, save_lse=self.want_attn, q_prescaled=True)
-        if self.want_attn:
-            self.probs = ops.attention_probs_fwd(qkv, self.lens, st[0], g.B, g.Tp, H, heads, q_prescaled=True)
+        probs = ops.attention_probs_fwd(qkv, self.lens, st[0], g.B, g.Tp, H, heads, q_prescaled=True) if self.want_attn else None
         s1 = ops.gemm(ctx, w.wo, M, H, H, bias=w.bo, out_f32=True, residual_f32=x32, tile=128)
-        n1, n1_32 = ops.layernorm_fwd_f32in(s1, ln1w, ln1b, cfg.layer_norm_eps)
-        u = ops.gemm(n1, w.w1, M, I, H, bias=w.b1, gelu=True)
-        s2 = ops.gemm(u, w.w2, M, H, I, bias=w.b2, out_f32=True, residual_f32=n1_32, tile=128)
-        return ops.layernorm_fwd_f32in(s2, ln2w, ln2b, cfg.layer_norm_eps)
+        if pre:             # FFN2 adds the un-normalised s1
+            ffn_in, res2 = ops.layernorm_fwd_f32in(s1, ln2w, ln2b, eps, want_f32=False)[0], s1
+        else:               # post-LN: FFN2 adds the normalised rows
+            ffn_in, res2 = ops.layernorm_fwd_f32in(s1, ln1w, ln1b, eps)
+        u = ops.gemm(ffn_in, w.w1, M, I, H, bias=w.b1, gelu=True)
+        s2 = ops.gemm(u, w.w2, M, H, I, bias=w.b2, out_f32=True, residual_f32=res2, tile=128)
+        if pre:
+            return None, s2, probs
+        y, y32 = ops.layernorm_fwd_f32in(s2, ln2w, ln2b, eps)
+        return y, y32, probs
 
     def _fwd_mxfp8(self, x, params, mx):
         """Inference-only forward with MX block-scaled FP8 operands in the Linear layers where they pay (BASELINE configs[4];
@@ -257,10 +261,10 @@ class _LayerImpl:
         # ---- FFN block
         if pre:
             ds2 = dy                                             # y = s1 + D(ffn)
-            d_ffn_out = ops.dropout(ds2, p_h, _seed(self.seed, 4)) if p_h > 0 else ds2
+            d_ffn_out = ops.dropout(ds2, p_h, _seed(self.seed, _FFN2_DROPOUT_STREAM)) if p_h > 0 else ds2
             ffn_in = s.n2
         else:
-            ds2, d_ffn_out, dg2, db2 = ops.layernorm_bwd(dy, s.s2, s.m2, s.r2, ln2w, dropout_p=p_h, seed=_seed(self.seed, 4))
+            ds2, d_ffn_out, dg2, db2 = ops.layernorm_bwd(dy, s.s2, s.m2, s.r2, ln2w, dropout_p=p_h, seed=_seed(self.seed, _FFN2_DROPOUT_STREAM))
             if d_ffn_out is None:
                 d_ffn_out = ds2
             ffn_in = s.x1
@@ -268,10 +272,11 @@ class _LayerImpl:
         if pre:
             dn2 = ops.gemm(du, w.w1, M, H, I, b_kmajor=True)
             ds1, d_att_out, dg2, db2 = ops.layernorm_bwd(dn2, s.s1, s.m2, s.r2, ln2w, dres=ds2, dropout_p=p_h,
-                                                         seed=_seed(self.seed, 2))
+                                                         seed=_seed(self.seed, _OUT_PROJ_DROPOUT_STREAM))
         else:
             dx1 = ops.gemm(du, w.w1, M, H, I, b_kmajor=True, residual=ds2)
-            ds1, d_att_out, dg1, db1 = ops.layernorm_bwd(dx1, s.s1, s.m1, s.r1, ln1w, dropout_p=p_h, seed=_seed(self.seed, 2))
+            ds1, d_att_out, dg1, db1 = ops.layernorm_bwd(dx1, s.s1, s.m1, s.r1, ln1w, dropout_p=p_h,
+                                                         seed=_seed(self.seed, _OUT_PROJ_DROPOUT_STREAM))
         if d_att_out is None:
             d_att_out = ds1
         # ---- attention block
@@ -281,10 +286,10 @@ class _LayerImpl:
         # what a loss puts on them reaches the padded frames of every layer below
         st = self.attn_state
         dqkv = ops.attention_bwd(s.qkv, self.lens, s.ctx, dctx, s.lse, g.B, g.Tp, H, heads, q_prescaled=True, dropout_p=p_att,
-                                 seed=_seed(self.seed, 1), dctx_zero_beyond_len=st is None or not st.seen)
+                                 seed=_seed(self.seed, _ATTN_DROPOUT_STREAM), dctx_zero_beyond_len=st is None or not st.seen)
         if dprobs is not None:      # dQ and dK of the map's gradient, summed into what the fused backward wrote
             ops.attention_probs_bwd(s.qkv, self.lens, s.lse[0], dprobs.contiguous(), g.B, g.Tp, H, heads, q_prescaled=True,
-                                    dropout_p=p_att, seed=_seed(self.seed, 1), dqkv=dqkv)
+                                    dropout_p=p_att, seed=_seed(self.seed, _ATTN_DROPOUT_STREAM), dqkv=dqkv)
             if st is not None:
                 st.seen = True
         attn_in = s.n1 if pre else s.x
@@ -305,9 +310,6 @@ class _LayerImpl:
 
 
 _SPEC_ON_DEVICE = os.environ.get("APTAI_SPEC_ON_DEVICE", "1") != "0"      # =0: numpy sampler with HF's RNG order (host round trip)
-# seed streams of the device sampler, as ids of _seed(step seed, id): the two masks are drawn independently of each other
-_TIME_MASK_STREAM, _FEATURE_MASK_STREAM = 77, 78
-
 
 def _host_spec_masks(cfg, B, T, frame_lens, want_time, want_feat):
     """The numpy sampler path (_SPEC_ON_DEVICE off): the time mask [B][T] over each row's valid frames (`frame_lens`, a host tensor, or
@@ -325,11 +327,16 @@ def _host_spec_masks(cfg, B, T, frame_lens, want_time, want_feat):
 
 
 # =================================================================================== front end of the encoder
+# The front end's parameters (Wav2Vec2Model._front_params), in the order _FrontImpl.bwd returns their gradients.  embed: masked_spec_embed
+# or None; pc_gain, pc_v: original0 / original1 of the positional conv's weight norm; enc_ln_*: encoder.layer_norm (post-LN models only)
+_FrontParams = namedtuple("_FrontParams", "fp_ln_w fp_ln_b proj_w proj_b embed pc_gain pc_v pc_bias enc_ln_w enc_ln_b")
+
+
 class _FrontImpl:
     """Feature projection (HF:422-434) -> SpecAugment fill + padded-frame zeroing (HF:1292-1295, 678-681) ->
     h + GELU(grouped positional conv(h)) (HF:326-379, 689-692) -> [LayerNorm for post-LN models] -> dropout.
     ``feat`` is the SpecAugment mask along the hidden axis ([B][H] uint8, HF `_mask_hidden_states`: `mask_feature_prob`), applied
-    in the same pass as the time fill; None launches the kernels of the time-only path."""
+    in the same pass as the time fill; None launches the kernels of the time-only path.  ``params`` of fwd: a _FrontParams."""
 
     def __init__(self, cfg, geom, lens_i32, spec, training, seed, model, feat=None):
         self.cfg, self.g, self.lens, self.spec, self.training, self.seed, self.model = cfg, geom, lens_i32, spec, training, seed, model
@@ -353,56 +360,53 @@ class _FrontImpl:
 
     def fwd(self, feats, params, need):
         cfg, g = self.cfg, self.g
-        (fplw, fplb, pw, pb, embed, pcg, pcv, pcb, elw, elb) = params
+        p = _FrontParams(*params)
         M, H, C = g.M, cfg.hidden_size, feats.shape[1]
         tr = self.training
-        s = SimpleNamespace(feats=feats, params=params)
-        s.n0, s.m0, s.r0 = ops.layernorm_fwd(feats, fplw, fplb, cfg.layer_norm_eps, save_stats=need)
-        wp = self.model._cached(("proj",), [pw], lambda: ops.cast_bf16(pw))
+        s = SimpleNamespace(feats=feats, params=p)
+        s.n0, s.m0, s.r0 = ops.layernorm_fwd(feats, p.fp_ln_w, p.fp_ln_b, cfg.layer_norm_eps, save_stats=need)
         s.p_fp = cfg.feat_proj_dropout if tr else 0.0
-        h0 = ops.gemm(s.n0, wp, M, H, C, bias=pb, dropout_p=s.p_fp, seed=_seed(self.seed, 11))
-        if self.feat is None:
-            ops.frame_mask_fwd(h0, self.lens, self.spec, embed, g.B, g.Tp, g.T, H)
-        else:
-            ops.frame_feature_mask_fwd(h0, self.lens, self.spec, embed, self.feat, g.B, g.Tp, g.T, H)
+        h0 = ops.gemm(s.n0, self.model._proj_weight(), M, H, C, bias=p.proj_b, dropout_p=s.p_fp,
+                      seed=_seed(self.seed, _PROJ_DROPOUT_STREAM))
+        ops.frame_mask_fwd(h0, self.lens, self.spec, p.embed, g.B, g.Tp, g.T, H, feat_mask_u8=self.feat)
         s.h0 = h0
         # positional conv as ONE batched implicit GEMM over (utterance, group) on a zero-gapped group-major copy
         G, Kw = cfg.num_conv_pos_embedding_groups, cfg.num_conv_pos_embeddings
         xg, rows_p, Cg, pad = self._packed("pc_x", feats.device)
         ops.posconv_pack(h0, xg, g.B, g.Tp, H, G, pad)
-        s.wf, s.wd, s.norm = self.model._cached(("posconv",), [pcg, pcv], lambda: ops.posconv_weight(pcv, pcg.reshape(-1), G))
+        s.wf, s.wd, s.norm = self.model._posconv_weights()
         K = Kw * Cg
         s.u = torch.empty((M, H), device=feats.device, dtype=torch.bfloat16) if need else None
         s.s = torch.empty((M, H), device=feats.device, dtype=torch.bfloat16)
         if ops.posconv_kernel_fits(H, G, Kw):            # wav2vec2-base: dedicated Toeplitz-window kernel (csrc/posconv.hip)
-            ops.posconv_gemm(xg, s.wf, s.s, g.B, g.Tp, H, G, Kw, pad, bias=pcb, gelu=True, residual=h0, out_pre=s.u)
+            ops.posconv_gemm(xg, s.wf, s.s, g.B, g.Tp, H, G, Kw, pad, bias=p.pc_bias, gelu=True, residual=h0, out_pre=s.u)
         else:
-            ops.gemm(xg, s.wf, g.Tp, Cg, K, lda=Cg, ldb=K, out=s.s, ldc=H, bias=pcb, gelu=True, residual=h0, ldr=H, out_pre=s.u,
+            ops.gemm(xg, s.wf, g.Tp, Cg, K, lda=Cg, ldb=K, out=s.s, ldc=H, bias=p.pc_bias, gelu=True, residual=h0, ldr=H, out_pre=s.u,
                      batch=self._posconv_batch(Cg, rows_p, K))
         s.xg_key = "pc_x"
         self.model._scratch_owner["pc_x"] = s
         if cfg.do_stable_layer_norm:
             y = s.s
         else:
-            y, s.m1, s.r1 = ops.layernorm_fwd(s.s, elw, elb, cfg.layer_norm_eps, save_stats=need)
+            y, s.m1, s.r1 = ops.layernorm_fwd(s.s, p.enc_ln_w, p.enc_ln_b, cfg.layer_norm_eps, save_stats=need)
         s.p_h = cfg.hidden_dropout if tr else 0.0
         if s.p_h > 0:
-            y = ops.dropout(y, s.p_h, _seed(self.seed, 12))
+            y = ops.dropout(y, s.p_h, _seed(self.seed, _FRONT_DROPOUT_STREAM))
         return (y,), (s if need else None)
 
     def bwd(self, s, grads, x_needs):
         cfg, g = self.cfg, self.g
-        (fplw, fplb, pw, pb, embed, pcg, pcv, pcb, elw, elb) = s.params
+        p = s.params
         M, H, C = g.M, cfg.hidden_size, s.feats.shape[1]
         G, Kw = cfg.num_conv_pos_embedding_groups, cfg.num_conv_pos_embeddings
         dy = grads[0].contiguous()
         if s.p_h > 0:
-            dy = ops.dropout(dy, s.p_h, _seed(self.seed, 12))
+            dy = ops.dropout(dy, s.p_h, _seed(self.seed, _FRONT_DROPOUT_STREAM))
         delw = delb = None
         if cfg.do_stable_layer_norm:
             ds = dy
         else:
-            ds, _, delw, delb = ops.layernorm_bwd(dy, s.s, s.m1, s.r1, elw)
+            ds, _, delw, delb = ops.layernorm_bwd(dy, s.s, s.m1, s.r1, p.enc_ln_w)
         # ---- positional conv backward
         dug, rows_p, Cg, pad = self._packed("pc_du", dy.device)
         K = Kw * Cg
@@ -426,21 +430,18 @@ class _FrontImpl:
             ops.gemm(dug[pad * Cg:], xg, Cg, K, kred, a_kmajor=True, b_kmajor=True, out_f32=True, lda=Cg, ldb=Cg, out=dwf, ldc=K,
                      batch=dict(outer=1, inner=G, a=(0, g.B * rows_p * Cg), b=(0, g.B * rows_p * Cg), c=(0, Cg * K)))
         # weight-norm backward (parameter-sized fp32 math): w = g * v / ||v||
-        dpcv, dgain = ops.posconv_weight_bwd(dwf, pcv.detach().contiguous(), pcg.detach().reshape(-1).contiguous(), s.norm, G)
-        dpcg = dgain.reshape(pcg.shape)
+        dpcv, dgain = ops.posconv_weight_bwd(dwf, p.pc_v.detach().contiguous(), p.pc_gain.detach().reshape(-1).contiguous(), s.norm, G)
+        dpcg = dgain.reshape(p.pc_gain.shape)
         # ---- mask + projection + LN
-        if self.feat is None:
-            dembed = ops.frame_mask_bwd(dh0, self.lens, self.spec, g.B, g.Tp, g.T, H, want_dembed=embed is not None)
-        else:
-            dembed = ops.frame_feature_mask_bwd(dh0, self.lens, self.spec, self.feat, g.B, g.Tp, g.T, H, want_dembed=embed is not None)
+        dembed = ops.frame_mask_bwd(dh0, self.lens, self.spec, g.B, g.Tp, g.T, H, want_dembed=p.embed is not None,
+                                    feat_mask_u8=self.feat)
         if s.p_fp > 0:
-            dh0 = ops.dropout(dh0, s.p_fp, _seed(self.seed, 11))
+            dh0 = ops.dropout(dh0, s.p_fp, _seed(self.seed, _PROJ_DROPOUT_STREAM))
         sk = max(1, min(8, M // 2048))
         dpw = ops.gemm(dh0, s.n0, H, C, M, a_kmajor=True, b_kmajor=True, out_f32=True, split_k=sk)
         dpb = ops.colsum(dh0, M, H)
-        wp = self.model._cached(("proj",), [pw], lambda: ops.cast_bf16(pw))
-        dn0 = ops.gemm(dh0, wp, M, C, H, b_kmajor=True)
-        dfeats, _, dfplw, dfplb = ops.layernorm_bwd(dn0, s.feats, s.m0, s.r0, fplw)
+        dn0 = ops.gemm(dh0, self.model._proj_weight(), M, C, H, b_kmajor=True)
+        dfeats, _, dfplw, dfplb = ops.layernorm_bwd(dn0, s.feats, s.m0, s.r0, p.fp_ln_w)
         return (dfeats if x_needs else None), (dfplw, dfplb, dpw, dpb, dembed, dpcg, dpcv, dpcb, delw, delb)
 
 
@@ -475,6 +476,18 @@ def batch_invariant_scope(encoder, on: bool):
         encoder.batch_invariant = prev
 
 
+def _copies_stale(mode, training, any_trainable, version_equal, synced=False, after_training=False) -> bool:
+    """Must a compute copy be rebuilt from its fp32 parameters?  The one rule behind Wav2Vec2Model._cached and _refresh_layer_copies.
+    ``mode`` is the model's _cache_mode (graph capture): "frozen" = never (replayed steps read the copies without asking), "build" =
+    always.  Otherwise Tensor._version (``version_equal``: the key of _versions is the one the copy was built from) is trusted only
+    where no optimiser can have stepped unseen: those with kernels of their own (torch's fused Adam, aptai_amd.optim.Adam) update
+    parameters in place WITHOUT bumping it.  So a training-mode forward rebuilds the copies of trainable parameters every time, and so
+    does the first eval forward after one (``after_training``) - unless the optimiser writes the copies itself (``synced``)."""
+    if mode in ("frozen", "build"):
+        return mode == "build"
+    return bool(((training and any_trainable) or after_training) and not synced or not version_equal)
+
+
 class Wav2Vec2Model(nn.Module):
     """Drop-in for ``transformers.Wav2Vec2Model`` on the reference's call pattern."""
 
@@ -484,6 +497,11 @@ class Wav2Vec2Model(nn.Module):
     # collated length (HF:317-323 on a padded batch), so at batch > 1 it deliberately differs from the reference and equals the
     # reference's batch-1 result.  Train-mode forwards ignore it; gradients through it are refused.
     batch_invariant = False
+
+    _encoder_precision = "bf16"     # set_encoder_precision
+    _cache_mode = None              # graph capture: "build" = every compute copy is rebuilt, "frozen" = every copy hits (_copies_stale)
+    _train_marker = 0               # training steps of this model so far: part of the eval-mode version key (_versions)
+    _lplan = _feat_lens = None      # _layer_plan, _feature_axis_lens
 
     def __init__(self, config):
         super().__init__()
@@ -613,6 +631,8 @@ class Wav2Vec2Model(nn.Module):
         self._encoder_precision = precision
         return self
 
+    encoder_precision = property(lambda self: self._encoder_precision)      # read-only, for the other modules
+
     def _mx_layer_weights(self, i: int):
         """MXFP8 copies (elements, scales) of layer i's four weight matrices, quantised from the bf16 compute copies; rebuilt only
         when the parameters moved (eval mode trusts Tensor._version, see _cached)."""
@@ -638,30 +658,43 @@ class Wav2Vec2Model(nn.Module):
 
     # ------------------------------------------------------------------ bf16 compute copies of the parameters
     def _versions(self, params):
-        # Tensor._version alone is not enough: optimisers with their own kernels (torch's fused Adam, aptai_amd.optim.Adam) update
-        # parameters in place without bumping it.  `_train_marker` counts training steps of this model (every training-mode forward
-        # under autograd, every replayed graph step), so a copy built in eval mode is rebuilt by the first eval forward after any
-        # training step - validation then sees the LAST update, not the copies the last training forward made.
-        # (training-mode forwards do not key on it: trainable copies are rebuilt on every forward there, frozen ones never move)
-        return (0 if self.training else getattr(self, "_train_marker", 0),) + tuple((p.data_ptr(), p._version) for p in params)
+        # `_train_marker` counts training steps of this model (training-mode forwards under autograd, replayed graph steps, weights_moved),
+        # so a copy built in eval mode is rebuilt by the first eval forward after any: validation sees the LAST update (_copies_stale)
+        return (0 if self.training else self._train_marker,) + tuple((p.data_ptr(), p._version) for p in params)
 
     def _cached(self, key, params, build):
-        mode = getattr(self, "_cache_mode", None)            # graph capture: "build" = always rebuild, "frozen" = always hit
-        if mode == "frozen":
-            return self._cache[key][1]
-        ver = self._versions(params)
+        """The compute copy `key` of `params`, rebuilt by `build` when _copies_stale says so (the layers' copies: _refresh_layer_copies)."""
+        mode = self._cache_mode
+        ver = None if mode == "frozen" else self._versions(params)
         hit = self._cache.get(key)
-        # In training mode the copies are rebuilt on every forward: optimisers with fused kernels (e.g.
-        # torch.optim.Adam(fused=True)) update parameters in place WITHOUT bumping Tensor._version, so a version check
-        # would silently keep stale weights.  Eval mode trusts the version.  (The transformer-layer copies go through
-        # _refresh_layer_copies / ops.CastPlan instead: one launch, or none when the optimiser publishes them.)
-        trainable = self.training and any(p.requires_grad for p in params)
-        if mode != "build" and not trainable and hit is not None and hit[0] == ver:
-            return hit[1]
+        if not _copies_stale(mode, self.training, any(p.requires_grad for p in params), hit is not None and hit[0] == ver):
+            return self._cache[key][1]
         with torch.no_grad():
             val = build()
         self._cache[key] = (ver, val)
         return val
+
+    def _proj_weight(self):                                  # bf16 copy of the feature projection's weight
+        pw = self.feature_projection.projection.weight
+        return self._cached(("proj",), [pw], lambda: ops.cast_bf16(pw))
+
+    def _posconv_weights(self):                              # (forward, data-gradient) bf16 weights of the positional conv, norm of v
+        wn = self.encoder.pos_conv_embed.conv.parametrizations.weight
+        gain, v = wn.original0, wn.original1
+        return self._cached(("posconv",), [gain, v],
+                            lambda: ops.posconv_weight(v, gain.reshape(-1), self.config.num_conv_pos_embedding_groups))
+
+    def _front_params(self, with_embed: bool):               # with_embed=False (no time mask in this forward) leaves masked_spec_embed out
+        fp, pc, enc = self.feature_projection, self.encoder.pos_conv_embed.conv, self.encoder
+        return _FrontParams(fp.layer_norm.weight, fp.layer_norm.bias, fp.projection.weight, fp.projection.bias,
+                            getattr(self, "masked_spec_embed", None) if with_embed else None,
+                            pc.parametrizations.weight.original0, pc.parametrizations.weight.original1, pc.bias,
+                            enc.layer_norm.weight, enc.layer_norm.bias)
+
+    def _layer_ln_params(self, i: int):
+        """The four LayerNorm parameters of layer i; followed by _layer_params(i) they are the parameter list of _LayerImpl."""
+        l = self.encoder.layers[i]
+        return [l.layer_norm.weight, l.layer_norm.bias, l.final_layer_norm.weight, l.final_layer_norm.bias]
 
     def _layer_params(self, i: int):
         l = self.encoder.layers[i]
@@ -673,7 +706,7 @@ class Wav2Vec2Model(nn.Module):
     def _layer_plan(self):
         """Persistent bf16 copies of every transformer-layer weight (+ packed fp32 q/k/v biases) and the ONE-launch cast
         plan (ops.CastPlan) that refreshes them: 12 layers x 9 jobs instead of ~90 separate cast / cat kernels."""
-        plan = getattr(self, "_lplan", None)
+        plan = self._lplan
         if plan is not None and not plan.stale():
             return plan
         H, I = self.config.hidden_size, self.config.intermediate_size
@@ -691,40 +724,33 @@ class Wav2Vec2Model(nn.Module):
             entries.append(e)
         plan = ops.CastPlan(jobs)
         plan.entries = entries
-        plan.version = None
         self._lplan = plan
         return plan
 
     def _refresh_layer_copies(self, force: bool = False):
-        """Runs the cast plan when the copies may be stale.  Training mode: every forward (fused optimisers update
-        parameters in place without bumping Tensor._version, see _cached); eval mode: when a parameter version moved."""
-        mode = getattr(self, "_cache_mode", None)
-        if mode == "frozen":
+        """Runs the cast plan when the copies may be stale (_copies_stale) or on `force`; a frozen cache outranks both."""
+        if self._cache_mode == "frozen":
             return
         plan = self._layer_plan()
         params = [p for i in range(len(self.encoder.layers)) for p in self._layer_params(i)]
         ver = self._versions(params)
-        trainable = self.training and any(p.requires_grad for p in params)
-        # an eval forward right after training must not trust the versions either (the last optimiser step is unseen) -
-        # unless the optimiser itself writes the copies (aptai_amd.optim.Adam.publish_to sets plan.optimizer_synced)
-        synced = getattr(plan, "optimizer_synced", False)
-        stale_by_training = (trainable or getattr(plan, "after_training", False)) and not synced
-        if force or mode == "build" or stale_by_training or plan.version != ver:
+        trainable = any(p.requires_grad for p in params)
+        if force or _copies_stale(self._cache_mode, self.training, trainable, plan.version == ver, plan.optimizer_synced, plan.after_training):
             with torch.no_grad():
                 plan.run()
             plan.version = ver
-            plan.after_training = bool(trainable) and not synced
+            plan.after_training = self.training and trainable and not plan.optimizer_synced
 
     def weights_moved(self) -> None:
         """Something other than a training step rewrote the parameters in place (aptai_amd.optim.Adam.swap_ema: averaged weights
         in, training weights back).  Every `_cached` copy misses in eval mode from here on, and the layer copies are re-cast NOW,
         also when the optimiser publishes them (`optimizer_synced`) and when a graph runner froze the cache: a replayed step reads
         them without asking."""
-        self._train_marker = getattr(self, "_train_marker", 0) + 1
-        if getattr(self, "_cache_mode", None) == "frozen":       # as BucketedGraphedStep.suspend(): the graphs keep their own copies
+        self._train_marker += 1
+        if self._cache_mode == "frozen":       # as BucketedGraphedStep.suspend(): the graphs keep their own copies
             self._cache_mode = None
             self._cache.clear()
-        plan = getattr(self, "_lplan", None)
+        plan = self._lplan
         if plan is not None and not plan.stale():
             with torch.no_grad():
                 plan.run()
@@ -749,7 +775,7 @@ class Wav2Vec2Model(nn.Module):
     # ------------------------------------------------------------------ geometry of one batch
     def _feature_axis_lens(self, B: int, dev) -> torch.Tensor:
         """[B] int32 filled with hidden_size: the row lengths of the span sampler on the feature axis (a cached constant)."""
-        c = getattr(self, "_feat_lens", None)
+        c = self._feat_lens
         if c is None or c.shape[0] != B or c.device != dev:
             c = self._feat_lens = torch.full((B,), self.config.hidden_size, device=dev, dtype=torch.int32)
         return c
@@ -1079,7 +1105,145 @@ class Wav2Vec2Model(nn.Module):
         hidden.append(h)
         return h, hidden
 
-    # ------------------------------------------------------------------ forward
+    # ------------------------------------------------------------------ forward, step by step
+    def _samples_feature_mask(self, mask_feature_indices) -> bool:
+        return mask_feature_indices is None and self.training and self.config.apply_spec_augment and self.config.mask_feature_prob > 0
+
+    def _check_request(self, input_values, want_attn: bool, batch_invariant: bool, mask_feature_indices) -> None:
+        """Every refusal of forward(), before anything is launched and before `_step` moves."""
+        cfg, prec = self.config, self._encoder_precision
+        if not input_values.is_cuda:
+            raise ops._lib.AptaiHipError("Wav2Vec2Model runs on the MI355X only (no CPU fallback)")
+        if want_attn and prec not in ("bf16", "bf16_f32res"):
+            raise NotImplementedError(f"output_attentions is not available with encoder precision {prec!r}: "
+                                      "the attention maps come from the bf16 attention kernels ('bf16', 'bf16_f32res')")
+        if batch_invariant:                                  # opt-in, eval mode only
+            if prec not in _BATCH_INVARIANT_PRECISIONS:
+                raise NotImplementedError(f"batch_invariant is not available with encoder precision {prec!r}: its first conv layer "
+                                          "does not take the per-utterance statistics")
+            if torch.is_grad_enabled() and input_values.requires_grad:
+                raise NotImplementedError("batch_invariant: no gradient w.r.t. the waveform (the per-utterance GroupNorm backward is "
+                                          "not built); switch it off for input gradients")
+        if mask_feature_indices is not None:
+            shape, want = tuple(torch.as_tensor(mask_feature_indices).shape), (input_values.shape[0], cfg.hidden_size)
+            if shape != want:
+                raise ValueError(f"mask_feature_indices has shape {shape}, expected (batch, hidden_size) = {want}")
+        elif self._samples_feature_mask(mask_feature_indices):
+            if cfg.mask_feature_length < 1 or cfg.mask_feature_length > cfg.hidden_size:
+                raise ValueError(f"mask_feature_length={cfg.mask_feature_length} must lie in [1, hidden_size={cfg.hidden_size}]")
+            if _SPEC_ON_DEVICE:
+                ops.feature_mask_span_check(cfg.hidden_size, cfg.mask_feature_prob, cfg.mask_feature_length, cfg.mask_feature_min_masks)
+
+    def _lengths(self, attention_mask, g, dev, batch_invariant: bool):
+        """(frame_lens int64 [B], lens_i32, sample_lens | None).  Batch-invariant inference, each row as if it ran alone: the first conv
+        layer's statistics over the row's own frames (g.lens0), the heads' FIR zero padding at the row's own length (g.fir_lens)."""
+        cfg = self.config
+        sample_lens = None if attention_mask is None else attention_mask.to(dev).long().sum(-1)
+        if sample_lens is not None:
+            frame_lens = hostlogic.feat_extract_output_lengths(sample_lens, cfg.conv_kernel, cfg.conv_stride).clamp(min=1, max=g.T)
+        else:
+            frame_lens = torch.full((g.B,), g.T, device=dev, dtype=torch.long)
+        lens_i32 = frame_lens.to(torch.int32).contiguous()
+        g.lens0 = None
+        if batch_invariant and sample_lens is not None:
+            g.lens0 = hostlogic.conv0_frame_lengths(sample_lens, cfg.conv_kernel[0], cfg.conv_stride[0]).clamp(min=1, max=g.Tl[0])
+        elif batch_invariant:
+            g.lens0 = torch.full((g.B,), g.Tl[0], device=dev, dtype=torch.int32)
+        g.fir_lens = lens_i32 if batch_invariant else None
+        return frame_lens, lens_i32, sample_lens
+
+    def _spec_masks(self, g, lens_i32, ragged_lens, seed, mask_time_indices, mask_feature_indices):
+        """(spec [B][T] | None, feat [B][H] | None), device uint8: the SpecAugment masks along time (HF:1272-1316) and along the hidden
+        axis (HF `_mask_hidden_states`, second half: spans over the H channels, every row of length H).  Each is the explicit mask, or
+        sampled in train mode: by a kernel from the device-resident lengths (no device->host copy, a 2.3 ms stall of the eager loop per
+        step; HF's `_compute_mask_indices` rule, counter-hash draws, a seed stream per mask) or, with _SPEC_ON_DEVICE off, by numpy in
+        HF's RNG order (`ragged_lens`: frame counts an attention mask gave).  ``apply_spec_augment = False``: none, explicit ones included."""
+        cfg = self.config
+        if not cfg.apply_spec_augment:
+            return None, None
+        dev, B, H = lens_i32.device, g.B, cfg.hidden_size
+        sample_time = mask_time_indices is None and cfg.mask_time_prob > 0 and self.training
+        sample_feat = self._samples_feature_mask(mask_feature_indices)
+        spec = feat = None
+        if mask_time_indices is not None:
+            spec = torch.as_tensor(mask_time_indices).to(dev).to(torch.uint8).contiguous()
+        elif sample_time and _SPEC_ON_DEVICE:
+            spec = ops.spec_augment_mask(lens_i32, B, g.T, cfg.mask_time_prob, cfg.mask_time_length, cfg.mask_time_min_masks,
+                                         _seed(seed, _TIME_MASK_STREAM))
+        if mask_feature_indices is not None:
+            feat = torch.as_tensor(mask_feature_indices).to(dev).to(torch.uint8).contiguous()
+            if feat.data_ptr() % 4:                          # the kernels load four mask bytes as one word
+                feat = feat.clone()
+        elif sample_feat and _SPEC_ON_DEVICE:
+            feat = ops.spec_augment_mask(self._feature_axis_lens(B, dev), B, H, cfg.mask_feature_prob, cfg.mask_feature_length,
+                                         cfg.mask_feature_min_masks, _seed(seed, _FEATURE_MASK_STREAM))
+        if (sample_time or sample_feat) and not _SPEC_ON_DEVICE:
+            m_time, m_feat = _host_spec_masks(cfg, B, g.T, None if ragged_lens is None else ragged_lens.cpu(), sample_time, sample_feat)
+            if sample_time:
+                spec = torch.from_numpy(m_time.astype(np.uint8)).to(dev)
+            if sample_feat:
+                feat = torch.from_numpy(m_feat.astype(np.uint8)).to(dev)
+        return spec, feat
+
+    # The three passes return (last hidden state bf16 [M][H], the same in fp32 | None, hidden states: the input of every layer and the
+    # last one, attention maps: one [B, heads, T, T] fp32 per layer (None where LayerDrop skipped it) | None).
+    def _encode_exact(self, audio, g, lens_i32, P, output_hidden_states, mask_time_indices, mask_feature_indices):
+        """Inference at fp32-class accuracy (set_encoder_precision("f32x3" | "f32x6")): the whole encoder, conv stack included."""
+        if mask_time_indices is not None or mask_feature_indices is not None:
+            raise NotImplementedError("the exact inference pass takes no SpecAugment mask (eval mode never samples one)")
+        h32, hidden32 = self._forward_exact(audio, g, lens_i32, P, output_hidden_states)
+        return h32.to(torch.bfloat16), h32, hidden32, None
+
+    def _encode_f32res(self, h, g, lens_i32, want_attn: bool):
+        """Inference with the residual stream in fp32 (set_encoder_precision("bf16_f32res")): the transformer layers."""
+        cfg = self.config
+        hidden, attn = [], []
+        h32 = h.float()
+        for i in range(len(self.encoder.layers)):
+            hidden.append(h if h is not None else h32)
+            impl = _LayerImpl(cfg, g, lens_i32, self._layer_plan().entries[i], False, 0, want_attn=want_attn)
+            h, h32, probs = impl.fwd_f32res(h, h32, self._layer_ln_params(i))
+            if want_attn:
+                attn.append(probs[:, :, :g.T, :g.T])
+        if cfg.do_stable_layer_norm:
+            h, h32 = ops.layernorm_fwd_f32in(h32, self.encoder.layer_norm.weight, self.encoder.layer_norm.bias, cfg.layer_norm_eps)
+        hidden.append(h)
+        return h, h32, hidden, attn if want_attn else None
+
+    def _encode_default(self, h, g, lens_i32, seed, want_attn: bool):
+        """The transformer layers under autograd with LayerDrop (HF:694-707 / 767-780); eval-mode MXFP8 operands with "mxfp8"."""
+        cfg, training = self.config, self.training
+        hidden, attn = [], []
+        attn_state = SimpleNamespace(seen=False) if want_attn else None
+        mx = self._encoder_precision == "mxfp8" and not training
+        for i in range(len(self.encoder.layers)):
+            hidden.append(h)
+            if training and cfg.layerdrop > 0 and float(torch.rand([], generator=self._layerdrop_gen)) < cfg.layerdrop:
+                attn.append(None)
+                continue
+            w, lin_params = self._layer_weights(i)
+            impl = _LayerImpl(cfg, g, lens_i32, w, training, _seed(seed, _LAYER_STREAM_BASE + i),
+                              mx=self._mx_layer_weights(i) if mx else None, want_attn=want_attn, attn_state=attn_state)
+            out = _run(impl, h, *self._layer_ln_params(i), *lin_params)
+            h, probs = out if want_attn else (out, None)
+            if want_attn:
+                attn.append(probs[:, :, :g.T, :g.T])
+        if cfg.do_stable_layer_norm:
+            h = _run(_FinalLNImpl(cfg, g), h, self.encoder.layer_norm.weight, self.encoder.layer_norm.bias)
+        hidden.append(h)
+        return h, None, hidden, attn if want_attn else None
+
+    def _output(self, g, frame_lens, last, last_f32, hidden, attn, feats, feat, output_hidden_states):
+        def view(t):
+            return t.view(g.B, g.Tp, -1)[:, :g.T]
+        out = Wav2Vec2BaseModelOutput(
+            last_hidden_state=view(hidden[-1]), extract_features=None,       # fp32 from the exact pass, bf16 otherwise
+            hidden_states=tuple(view(t) for t in hidden) if output_hidden_states else None,
+            attentions=tuple(attn) if attn is not None else None)
+        out._geom, out._frame_lens, out._flat_last, out._flat_last_f32 = g, frame_lens, last, last_f32      # flat [M][H]: bf16; fp32 | None
+        out._features, out._feature_mask = feats, feat       # conv features [M][512] bf16 | None; the feature-axis mask applied | None
+        return out
+
     def forward(self, input_values, attention_mask=None, mask_time_indices=None, output_attentions=None,
                 output_hidden_states=None, return_dict=None, mask_feature_indices=None, **kw):
         """HF:1319-1375.  ``attention_mask`` follows the reference's convention: the (B,1) tensor of sample
@@ -1091,181 +1255,33 @@ class Wav2Vec2Model(nn.Module):
         such argument (it only samples the mask, in train mode, when ``mask_feature_prob > 0``, which this forward does as well);
         it exists so that a run can be reproduced and tested.  The mask that was applied, sampled or given, is
         ``out._feature_mask`` (a device uint8 ``[B, hidden_size]``, or None)."""
-        cfg = self.config
-        if not input_values.is_cuda:
-            raise ops._lib.AptaiHipError("Wav2Vec2Model runs on the MI355X only (no CPU fallback)")
         want_attn = bool(output_attentions)
-        if want_attn and getattr(self, "_encoder_precision", "bf16") not in ("bf16", "bf16_f32res"):
-            raise NotImplementedError(f"output_attentions is not available with encoder precision {self._encoder_precision!r}: "
-                                      "the attention maps come from the bf16 attention kernels ('bf16', 'bf16_f32res')")
-        # batch-invariant inference (opt-in, eval mode only): refusals first, before anything is launched
         batch_invariant = bool(self.batch_invariant) and not self.training
-        if batch_invariant:
-            prec = getattr(self, "_encoder_precision", "bf16")
-            if prec not in _BATCH_INVARIANT_PRECISIONS:
-                raise NotImplementedError(f"batch_invariant is not available with encoder precision {prec!r}: its first conv layer "
-                                          "does not take the per-utterance statistics")
-            if torch.is_grad_enabled() and input_values.requires_grad:
-                raise NotImplementedError("batch_invariant: no gradient w.r.t. the waveform (the per-utterance GroupNorm backward is "
-                                          "not built); switch it off for input gradients")
+        self._check_request(input_values, want_attn, batch_invariant, mask_feature_indices)
         audio = input_values.float().contiguous()
-        B, S = audio.shape
-        # SpecAugment along the hidden axis: refusals first, before anything is launched
-        feat = None
-        sample_feat = (mask_feature_indices is None and self.training and getattr(cfg, "apply_spec_augment", True)
-                       and cfg.mask_feature_prob > 0)
-        if mask_feature_indices is not None:
-            feat = torch.as_tensor(mask_feature_indices)
-            if feat.dim() != 2 or tuple(feat.shape) != (B, cfg.hidden_size):
-                raise ValueError(f"mask_feature_indices has shape {tuple(feat.shape)}, expected (batch, hidden_size) = "
-                                 f"{(B, cfg.hidden_size)}")
-        elif sample_feat:
-            if cfg.mask_feature_length < 1 or cfg.mask_feature_length > cfg.hidden_size:
-                raise ValueError(f"mask_feature_length={cfg.mask_feature_length} must lie in [1, hidden_size={cfg.hidden_size}]")
-            if _SPEC_ON_DEVICE:
-                ops.feature_mask_span_check(cfg.hidden_size, cfg.mask_feature_prob, cfg.mask_feature_length, cfg.mask_feature_min_masks)
-        g = self._geometry(B, S)
-        dev = audio.device
-        if attention_mask is not None:
-            sample_lens = attention_mask.to(dev).long().sum(-1)
-            frame_lens = hostlogic.feat_extract_output_lengths(sample_lens, cfg.conv_kernel, cfg.conv_stride)
-            frame_lens = frame_lens.clamp(min=1, max=g.T)
-        else:
-            frame_lens = torch.full((B,), g.T, device=dev, dtype=torch.long)
-        lens_i32 = frame_lens.to(torch.int32).contiguous()
-        # ---- batch-invariant inference (opt-in, eval mode only): each row as if it ran alone - the first conv layer's statistics over
-        # the row's own frames (g.lens0) and, in the heads that follow, the FIR's zero padding at the row's own length (g.fir_lens)
-        g.lens0 = g.fir_lens = None
-        if batch_invariant:
-            if attention_mask is not None:
-                g.lens0 = hostlogic.conv0_frame_lengths(sample_lens, cfg.conv_kernel[0], cfg.conv_stride[0]).clamp(min=1, max=g.Tl[0])
-            else:
-                g.lens0 = torch.full((B,), g.Tl[0], device=dev, dtype=torch.int32)
-            g.fir_lens = lens_i32
+        g = self._geometry(*audio.shape)
+        frame_lens, lens_i32, _ = self._lengths(attention_mask, g, audio.device, batch_invariant)
         self._step += 1
         seed = _seed(self.base_seed, self._step)
-        training = self.training
-        if training and torch.is_grad_enabled():
-            self._train_marker = getattr(self, "_train_marker", 0) + 1
-
-        prec = getattr(self, "_encoder_precision", "bf16")
-        if prec in ("f32x3", "f32x6") and not training and not torch.is_grad_enabled():
-            if mask_time_indices is not None or mask_feature_indices is not None:
-                raise NotImplementedError("the exact inference pass takes no SpecAugment mask (eval mode never samples one)")
-            h32, hidden32 = self._forward_exact(audio, g, lens_i32, 3 if prec == "f32x3" else 6, output_hidden_states)
-            hb = h32.to(torch.bfloat16)
-            out = Wav2Vec2BaseModelOutput(last_hidden_state=h32.view(B, g.Tp, -1)[:, :g.T], extract_features=None,
-                                          hidden_states=tuple(t.view(B, g.Tp, -1)[:, :g.T] for t in hidden32) if output_hidden_states else None,
-                                          attentions=None)
-            out._geom, out._frame_lens, out._flat_last, out._flat_last_f32, out._features = g, frame_lens, hb, h32, None
-            out._feature_mask = None
-            return out
-        feats = self._feature_encoder(audio, g)                                         # [M][512] bf16
-        # ---- feature projection + SpecAugment + padded-frame zeroing (HF:429-434, 1272-1316, 678-681)
-        spec = None
-        host_time = False
-        if getattr(cfg, "apply_spec_augment", True):
-            if mask_time_indices is not None:
-                spec = torch.as_tensor(mask_time_indices).to(dev).to(torch.uint8).contiguous()
-            elif cfg.mask_time_prob > 0 and training:
-                if _SPEC_ON_DEVICE:
-                    # sampled by a kernel from the device-resident lengths: no device->host copy (a 2.3 ms stall of the eager
-                    # loop per step).  Same rule as HF `_compute_mask_indices`, counter-hash draws instead of numpy's.
-                    spec = ops.spec_augment_mask(lens_i32, B, g.T, cfg.mask_time_prob, cfg.mask_time_length, cfg.mask_time_min_masks,
-                                                 _seed(seed, _TIME_MASK_STREAM))
-                else:
-                    host_time = True
-        # along the hidden axis (HF `_mask_hidden_states`, second half): spans over the H channels of each row, every row of length H,
-        # drawn after the time mask (HF's RNG order on the host path) from a seed stream of its own on the device
-        H = cfg.hidden_size
-        if feat is not None and not getattr(cfg, "apply_spec_augment", True):
-            feat = None                                  # as mask_time_indices: HF `_mask_hidden_states` returns early
-        if feat is not None:
-            feat = feat.to(dev).to(torch.uint8).contiguous()
-            if feat.data_ptr() % 4:
-                feat = feat.clone()
-        elif sample_feat and _SPEC_ON_DEVICE:
-            feat = ops.spec_augment_mask(self._feature_axis_lens(B, dev), B, H, cfg.mask_feature_prob, cfg.mask_feature_length,
-                                         cfg.mask_feature_min_masks, _seed(seed, _FEATURE_MASK_STREAM))
-        host_feat = sample_feat and not _SPEC_ON_DEVICE
-        if host_time or host_feat:
-            m_time, m_feat = _host_spec_masks(cfg, B, g.T, frame_lens.cpu() if attention_mask is not None else None, host_time,
-                                              host_feat)
-            if host_time:
-                spec = torch.from_numpy(m_time.astype(np.uint8)).to(dev)
-            if host_feat:
-                feat = torch.from_numpy(m_feat.astype(np.uint8)).to(dev)
-        fp = self.feature_projection
-        embed = getattr(self, "masked_spec_embed", None)
-        front = _FrontImpl(cfg, g, lens_i32, spec, training, seed, self, feat=feat)
-        pc = self.encoder.pos_conv_embed.conv
-        fparams = [fp.layer_norm.weight, fp.layer_norm.bias, fp.projection.weight, fp.projection.bias,
-                   embed if (embed is not None and spec is not None) else None,
-                   pc.parametrizations.weight.original0, pc.parametrizations.weight.original1, pc.bias,
-                   self.encoder.layer_norm.weight, self.encoder.layer_norm.bias]
-        h = _run(front, feats, *fparams)
-        # ---- transformer layers with LayerDrop (HF:694-707 / 767-780)
-        self._refresh_layer_copies()
-        hidden = []
-        attn = []                    # output_attentions: one [B, heads, T, T] fp32 map per layer (None where LayerDrop skipped it)
-        attn_state = SimpleNamespace(seen=False) if want_attn else None
-        if getattr(self, "_encoder_precision", "bf16") == "bf16_f32res" and not training and not torch.is_grad_enabled():
-            # fp32 residual stream (inference only, see set_encoder_precision)
-            h32 = h.float()
-            for i, layer in enumerate(self.encoder.layers):
-                hidden.append(h if h is not None else h32)
-                wt, _lin = self._layer_weights(i)
-                impl = _LayerImpl(cfg, g, lens_i32, wt, False, 0)
-                impl.want_attn = want_attn
-                h, h32 = impl.fwd_f32res(h, h32, [layer.layer_norm.weight, layer.layer_norm.bias, layer.final_layer_norm.weight,
-                                                   layer.final_layer_norm.bias])
-                if want_attn:
-                    attn.append(impl.probs[:, :, :g.T, :g.T])
-            if cfg.do_stable_layer_norm:
-                h, h32 = ops.layernorm_fwd_f32in(h32, self.encoder.layer_norm.weight, self.encoder.layer_norm.bias, cfg.layer_norm_eps)
-            hidden.append(h)
-            out = Wav2Vec2BaseModelOutput(last_hidden_state=h.view(B, g.Tp, -1)[:, :g.T], extract_features=None,
-                                          hidden_states=tuple(t.view(B, g.Tp, -1)[:, :g.T] for t in hidden) if output_hidden_states else None,
-                                          attentions=tuple(attn) if want_attn else None)
-            out._geom, out._frame_lens, out._flat_last, out._flat_last_f32 = g, frame_lens, h, h32
-            out._feature_mask = feat
-            return out
-        for i, layer in enumerate(self.encoder.layers):
-            hidden.append(h)
-            skip = training and cfg.layerdrop > 0 and (float(torch.rand([], generator=self._layerdrop_gen)) < cfg.layerdrop)
-            if skip:
-                if want_attn:
-                    attn.append(None)
-                continue
-            w, lin_params = self._layer_weights(i)
-            impl = _LayerImpl(cfg, g, lens_i32, w, training, _seed(seed, 100 + i))
-            if getattr(self, "_encoder_precision", "bf16") == "mxfp8" and not training:
-                impl.mx = self._mx_layer_weights(i)
-            if want_attn:
-                impl.want_attn, impl.attn_state = True, attn_state
-                h, probs = _run(impl, h, layer.layer_norm.weight, layer.layer_norm.bias, layer.final_layer_norm.weight,
-                                layer.final_layer_norm.bias, *lin_params)
-                attn.append(probs[:, :, :g.T, :g.T])
-                continue
-            h = _run(impl, h, layer.layer_norm.weight, layer.layer_norm.bias, layer.final_layer_norm.weight,
-                            layer.final_layer_norm.bias, *lin_params)
-        if cfg.do_stable_layer_norm:
-            fin = _FinalLNImpl(cfg, g)
-            h = _run(fin, h, self.encoder.layer_norm.weight, self.encoder.layer_norm.bias)
-        hidden.append(h)
-
-        def view(t):
-            return t.view(B, g.Tp, -1)[:, :g.T]
-        out = Wav2Vec2BaseModelOutput(
-            last_hidden_state=view(h),
-            extract_features=None,
-            hidden_states=tuple(view(t) for t in hidden) if output_hidden_states else None,
-            attentions=tuple(attn) if want_attn else None)
-        out._geom = g
-        out._feature_mask = feat
-        out._frame_lens = frame_lens
-        out._flat_last = h
-        out._features = feats
-        return out
-
-
+        inference = not self.training and not torch.is_grad_enabled()
+        if self.training and torch.is_grad_enabled():
+            self._train_marker += 1
+        prec = self._encoder_precision
+        feats = feat = None
+        if prec in ("f32x3", "f32x6") and inference:
+            enc = self._encode_exact(audio, g, lens_i32, 3 if prec == "f32x3" else 6, output_hidden_states, mask_time_indices,
+                                     mask_feature_indices)
+        else:
+            feats = self._feature_encoder(audio, g)                                     # [M][512] bf16
+            spec, feat = self._spec_masks(g, lens_i32, frame_lens if attention_mask is not None else None, seed, mask_time_indices,
+                                          mask_feature_indices)
+            # feature projection + SpecAugment + padded-frame zeroing + positional conv (HF:429-434, 678-681, 689-692).  The eager front
+            # draws from the step seed itself, the graph runners from _seed(their seed, 1): existing behaviour, part of recorded runs
+            front = _FrontImpl(self.config, g, lens_i32, spec, self.training, seed, self, feat=feat)
+            h = _run(front, feats, *self._front_params(with_embed=spec is not None))
+            self._refresh_layer_copies()
+            if prec == "bf16_f32res" and inference:
+                enc = self._encode_f32res(h, g, lens_i32, want_attn)
+            else:
+                enc = self._encode_default(h, g, lens_i32, seed, want_attn)
+        return self._output(g, frame_lens, *enc, feats, feat, output_hidden_states)

@@ -24,8 +24,9 @@ def test_new_entry_points_are_declared_exported_and_typed():
     # the arguments of aptai_frame_mask_fwd / _bwd plus one pointer (the feature mask)
     assert len(_lib.ARGTYPES["aptai_frame_feature_mask_fwd"]) == len(_lib.ARGTYPES["aptai_frame_mask_fwd"]) + 1
     assert len(_lib.ARGTYPES["aptai_frame_feature_mask_bwd"]) == len(_lib.ARGTYPES["aptai_frame_mask_bwd"]) + 1
-    for w in ("frame_feature_mask_fwd", "frame_feature_mask_bwd"):
-        assert callable(getattr(ops, w))
+    import inspect
+    for w in ("frame_mask_fwd", "frame_mask_bwd"):                     # one wrapper pair: the feature mask is an optional argument
+        assert inspect.signature(getattr(ops, w)).parameters["feat_mask_u8"].default is None
 
 
 def test_wrappers_refuse_host_tensors():
@@ -34,9 +35,9 @@ def test_wrappers_refuse_host_tensors():
     lens = torch.ones(1, dtype=torch.int32)
     feat = torch.zeros(1, 8, dtype=torch.uint8)
     with pytest.raises(_lib.AptaiHipError):
-        ops.frame_feature_mask_fwd(h, lens, None, None, feat, 1, 8, 8, 8)
+        ops.frame_mask_fwd(h, lens, None, None, 1, 8, 8, 8, feat_mask_u8=feat)
     with pytest.raises(_lib.AptaiHipError):
-        ops.frame_feature_mask_bwd(h, lens, None, feat, 1, 8, 8, 8, want_dembed=False)
+        ops.frame_mask_bwd(h, lens, None, 1, 8, 8, 8, want_dembed=False, feat_mask_u8=feat)
 
 
 def _parse(argv):

@@ -22,6 +22,30 @@ def _bits(x):
     return x.contiguous().view(torch.int16)
 
 
+def _feature_entry_fwd(h, lens, spec, embed, feat, B, Tp, T, H):
+    """aptai_frame_feature_mask_fwd: through ops.frame_mask_fwd with a feature mask, called directly with a null one (the wrapper
+    launches the time-only entry then)."""
+    from aptai_amd import _lib, ops
+    if feat is not None:
+        return ops.frame_mask_fwd(h, lens, spec, embed, B, Tp, T, H, feat_mask_u8=feat)
+    _lib.call("aptai_frame_feature_mask_fwd", h.data_ptr(), lens.data_ptr(), ops._ptr(spec), ops._ptr(embed), None, B, Tp, T, H,
+              ops._stream())
+
+
+def _feature_entry_bwd(dy, lens, spec, feat, B, Tp, T, H):
+    """aptai_frame_feature_mask_bwd with want_dembed, reached as in _feature_entry_fwd; returns dembed (None without a time mask)."""
+    from aptai_amd import _lib, ops
+    if feat is not None:
+        return ops.frame_mask_bwd(dy, lens, spec, B, Tp, T, H, want_dembed=True, feat_mask_u8=feat)
+    dembed = ws = None
+    if spec is not None:
+        dembed = torch.empty(H, device=dy.device, dtype=torch.float32)
+        ws = ops._ws(_lib.lib().aptai_frame_mask_bwd_workspace_bytes(B, Tp, H), dy.device)
+    _lib.call("aptai_frame_feature_mask_bwd", dy.data_ptr(), lens.data_ptr(), ops._ptr(spec), None, ops._ptr(dembed), ops._ptr(ws),
+              B, Tp, T, H, ops._stream())
+    return dembed
+
+
 # ------------------------------------------------------------------------------------------------ 1. operator
 @pytest.mark.parametrize("case", ["time+feature", "feature", "neither"])
 @pytest.mark.parametrize("H", [768, 1024])
@@ -58,7 +82,7 @@ def test_frame_feature_mask_forward_and_backward(H, case):
     want[fzero] = 0
     want[~valid] = 0
     h_d = h.cuda()
-    ops.frame_feature_mask_fwd(h_d, lens_d, spec_d, embed_d, feat_d, B, Tp, T, H)
+    _feature_entry_fwd(h_d, lens_d, spec_d, embed_d, feat_d, B, Tp, T, H)
     torch.cuda.synchronize()
     assert torch.equal(_bits(h_d.cpu()), _bits(want.view(B * Tp, H)))
     # ---- backward (in place): dy zeroed on padded and time-masked rows and on masked channels, bit-unchanged elsewhere
@@ -67,7 +91,7 @@ def test_frame_feature_mask_forward_and_backward(H, case):
     want[masked | ~valid] = 0
     want[fzero] = 0
     dy_d = dy.cuda()
-    dembed = ops.frame_feature_mask_bwd(dy_d, lens_d, spec_d, feat_d, B, Tp, T, H, want_dembed=True)
+    dembed = _feature_entry_bwd(dy_d, lens_d, spec_d, feat_d, B, Tp, T, H)
     torch.cuda.synchronize()
     assert torch.equal(_bits(dy_d.cpu()), _bits(want.view(B * Tp, H)))
     if case == "neither":
@@ -80,9 +104,9 @@ def test_frame_feature_mask_forward_and_backward(H, case):
         # and with a time mask but no feature mask: the shared kernel with a null feature mask, dembed included
         h0, h1, dy0, dy1 = h.cuda(), h.cuda(), dy.cuda(), dy.cuda()
         ops.frame_mask_fwd(h0, lens_d, spec.cuda(), embed.cuda(), B, Tp, T, H)
-        ops.frame_feature_mask_fwd(h1, lens_d, spec.cuda(), embed.cuda(), None, B, Tp, T, H)
+        _feature_entry_fwd(h1, lens_d, spec.cuda(), embed.cuda(), None, B, Tp, T, H)
         de0 = ops.frame_mask_bwd(dy0, lens_d, spec.cuda(), B, Tp, T, H, want_dembed=True)
-        de1 = ops.frame_feature_mask_bwd(dy1, lens_d, spec.cuda(), None, B, Tp, T, H, want_dembed=True)
+        de1 = _feature_entry_bwd(dy1, lens_d, spec.cuda(), None, B, Tp, T, H)
         assert torch.equal(_bits(h0), _bits(h1)) and torch.equal(_bits(dy0), _bits(dy1))
         assert torch.equal(de0.view(torch.int32), de1.view(torch.int32))
         return
