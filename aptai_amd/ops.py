@@ -12,35 +12,33 @@ import torch
 
 from . import _lib
 
-EPI_BIAS, EPI_GELU, EPI_RESIDUAL, EPI_DROPOUT, EPI_DGELU, EPI_ALPHA, EPI_PRE_DGELU, EPI_MUL_AUX, EPI_RESIDUAL_F32, EPI_SPLIT_OUT, EPI_BIAS_ROW = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512, 1024
-
-c_void_p, c_i64, c_int, c_float, c_u64 = (ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_float,
-                                          ctypes.c_uint64)
+_C = _lib.ABI.constants     # the header's enum values and #defines, under the names this module has always exported
+EPI_BIAS = _C["APTAI_EPI_BIAS"]
+EPI_GELU = _C["APTAI_EPI_GELU"]
+EPI_RESIDUAL = _C["APTAI_EPI_RESIDUAL"]
+EPI_DROPOUT = _C["APTAI_EPI_DROPOUT"]
+EPI_DGELU = _C["APTAI_EPI_DGELU"]
+EPI_ALPHA = _C["APTAI_EPI_ALPHA"]
+EPI_PRE_DGELU = _C["APTAI_EPI_PRE_DGELU"]
+EPI_MUL_AUX = _C["APTAI_EPI_MUL_AUX"]
+EPI_RESIDUAL_F32 = _C["APTAI_EPI_RESIDUAL_F32"]
+EPI_SPLIT_OUT = _C["APTAI_EPI_SPLIT_OUT"]
+EPI_BIAS_ROW = _C["APTAI_EPI_BIAS_ROW"]
 
 
 class GemmDesc(ctypes.Structure):
-    _fields_ = [("A", c_void_p), ("lda", c_i64), ("B", c_void_p), ("ldb", c_i64), ("C", c_void_p), ("ldc", c_i64),
-                ("M", c_i64), ("N", c_i64), ("K", c_i64),
-                ("a_kmajor", c_int), ("b_kmajor", c_int), ("out_f32", c_int), ("flags", c_int),
-                ("bias", c_void_p), ("residual", c_void_p), ("ldr", c_i64), ("out_pre", c_void_p),
-                ("aux", c_void_p), ("ldaux", c_i64), ("alpha", c_float), ("dropout_p", c_float), ("seed", c_u64),
-                ("split_k", c_int), ("accumulate", c_int), ("workspace", c_void_p), ("workspace_bytes", c_i64),
-                ("batch_outer", c_int), ("batch_inner", c_int),
-                ("batch_stride_a", c_i64 * 2), ("batch_stride_b", c_i64 * 2), ("batch_stride_c", c_i64 * 2),
-                ("batch_stride_bias", c_i64 * 2), ("batch_stride_res", c_i64 * 2), ("batch_stride_aux", c_i64 * 2),
-                ("tile", c_int), ("colscale_n", c_int), ("colscale", c_float),
-                ("sk_workspace", c_void_p), ("sk_workspace_bytes", c_i64), ("split_out_pieces", c_int), ("split_out_bcol", c_int)]
+    _fields_ = _lib.ABI.structs["aptai_gemm_desc"]
 
 
 class GemmPlanInfo(ctypes.Structure):
-    _fields_ = [("tile", c_int), ("nbatch", c_int), ("nsplit", c_int), ("ktiles_per_split", c_int), ("raster_gm", c_int), ("split_n", c_i64)]
+    _fields_ = _lib.ABI.structs["aptai_gemm_plan_info"]
 
 
 def gemm_plan(d: GemmDesc) -> GemmPlanInfo:
     """What aptai_gemm_bf16 would launch for `d` in this process (aptai_gemm_plan: host only, no device needed); raises where
     aptai_gemm_bf16 would refuse the descriptor, with the same text."""
     info = GemmPlanInfo()
-    _lib.check(_lib.lib().aptai_gemm_plan(ctypes.byref(d), ctypes.byref(info)), "aptai_gemm_plan")
+    _lib.call("aptai_gemm_plan", ctypes.byref(d), ctypes.byref(info))
     return info
 
 
@@ -66,7 +64,7 @@ def gemm_sk_check(device=None) -> None:
         if device is not None and d != str(device):
             continue
         out = ctypes.c_int(0)
-        _lib.check(_lib.lib().aptai_gemm_sk_status(c_void_p(ws.data_ptr()), c_void_p(st), ctypes.byref(out)), "aptai_gemm_sk_status")
+        _lib.call("aptai_gemm_sk_status", ws.data_ptr(), st, ctypes.byref(out))
         if out.value != 0:
             raise _lib.AptaiHipError("aptai_gemm_bf16 (stream-K): a wait for another workgroup's partial tile timed out; "
                                      "the output of that launch is incomplete")
@@ -222,16 +220,16 @@ def gemm(a: torch.Tensor, b: torch.Tensor, M: int, N: int, K: int, **kw) -> torc
     d = GemmDesc()
     out, _ws_keep = _gemm_desc(d, a, b, M, N, K, **kw)
     pr = _probe
-    if pr is not None and pr.key == (bool(d.a_kmajor), bool(d.b_kmajor), bool(d.out_f32)) and not torch.cuda.is_current_stream_capturing():
+    timed = pr is not None and pr.key == (bool(d.a_kmajor), bool(d.b_kmajor), bool(d.out_f32)) and not torch.cuda.is_current_stream_capturing()
+    if timed:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        _lib.check(_lib.lib().aptai_gemm_bf16(ctypes.byref(d), c_void_p(_stream())), "aptai_gemm_bf16")
+    _lib.call("aptai_gemm_bf16", ctypes.byref(d), _stream())
+    if timed:
         e1.record()
         batch = kw.get("batch")
         nb = (batch.get("outer", 1) * batch.get("inner", 1)) if batch else 1
         pr.records.append((2.0 * M * N * K * nb, e0, e1))
-        return out
-    _lib.check(_lib.lib().aptai_gemm_bf16(ctypes.byref(d), c_void_p(_stream())), "aptai_gemm_bf16")
     return out
 
 
@@ -244,7 +242,7 @@ def gemm_grouped(problems) -> list:
     problems = list(problems)
     descs = (GemmDesc * len(problems))()
     outs, keep, sums = [], [], []
-    rs_ptrs = (c_void_p * len(problems))()
+    rs_ptrs = (ctypes.c_void_p * len(problems))()
     flops = 0.0
     for i, (d, (a, b, M, N, K, kw)) in enumerate(zip(descs, problems)):
         kw = dict(kw)
@@ -264,10 +262,9 @@ def gemm_grouped(problems) -> list:
 
     def launch():
         if sums:
-            _lib.check(_lib.lib().aptai_gemm_bf16_grouped_rowsum(descs, rs_ptrs, len(problems), c_void_p(_stream())),
-                       "aptai_gemm_bf16_grouped_rowsum")
+            _lib.call("aptai_gemm_bf16_grouped_rowsum", descs, rs_ptrs, len(problems), _stream())
         else:
-            _lib.check(_lib.lib().aptai_gemm_bf16_grouped(descs, len(problems), c_void_p(_stream())), "aptai_gemm_bf16_grouped")
+            _lib.call("aptai_gemm_bf16_grouped", descs, len(problems), _stream())
 
     pr = _probe
     d0 = descs[0]
@@ -996,7 +993,7 @@ def ctc_viterbi(logits, ldl, rows_per_b, targets_i32, input_lens_i32, target_len
 
 
 # ----------------------------------------------------------------------------- evaluation metrics (csrc/eval.hip)
-EVAL_EDIT_MAX_LANE_SIDE = 2048          # APTAI_EVAL_EDIT_MAX_LANE_SIDE
+EVAL_EDIT_MAX_LANE_SIDE = _C["APTAI_EVAL_EDIT_MAX_LANE_SIDE"]
 
 
 def _eval_lens(lens, B, name):
@@ -1073,7 +1070,7 @@ def eval_edit_distance(a_i32, lda, a_lens_i32, b_i32, ldb, b_lens_i32, B):
 
 
 # ----------------------------------------------------------------------------- audio front end (csrc/frontend.hip)
-RESAMPLE_MAX_TABLE = 1 << 22            # APTAI_RESAMPLE_MAX_TABLE
+RESAMPLE_MAX_TABLE = _C["APTAI_RESAMPLE_MAX_TABLE"]
 
 
 def _i64_vec(t, n, name, what):
@@ -1102,7 +1099,7 @@ def resample_batch(packed, offsets_i64, B, taps_f32, first_i32, orig, new, Kc, w
     return out
 
 
-RESAMPLE_MAX_RATIOS = 8                 # APTAI_RESAMPLE_MAX_RATIOS
+RESAMPLE_MAX_RATIOS = _C["APTAI_RESAMPLE_MAX_RATIOS"]
 RESAMPLE_ENTRY = 8                      # int32 words per ratio: orig, new, Kc, width, taps_off, first_off, 0, 0
 
 
