@@ -5,8 +5,9 @@ only, models/w2v2_pr.py:124-127) -> cross-attention forced aligner + BiLSTM regr
 
 Differences from the shipped reference, all forced by defects recorded in SURVEY.md §0:
  * batch > 1 works (the reference's ``RNN.forward`` raises NameError at models/modules.py:207; intent followed);
- * the CTC decode inside the step is the best path (torchaudio's beam decoder is absent: parity unpinned) and costs ONE
-   device->host transfer per batch; the alignment read-out (:148-161, B*T host syncs in the reference) is one gather
+ * the CTC decode inside the step is the recogniser's: the best path by default, its `decoder = "flashlight"` / `"beam"` (the
+   device beam search, aptai_ctc_beam_search) when set there; parity with torchaudio's decoder itself is unpinned, the package is
+   not available.  It costs ONE device->host transfer per batch; the alignment read-out (:148-161, B*T host syncs in the reference) is one gather
    kernel + one transfer;
  * the encoder runs once per step (the reference ran the conv stack twice, models/w2v2_pr.py:129,132).
 """

@@ -241,7 +241,7 @@ def ctc_bracketed_best_path(logits: np.ndarray, length: int, blank: int = 0, sil
 
 
 def ctc_beam_search(emissions: np.ndarray, blank: int, sil: int, beam_size: int = 10, beam_size_token: int = None,
-                    beam_threshold: float = 50.0, log_add: bool = False, nbest: int = 1, sil_score: float = 0.0):
+                    beam_threshold: float = 50.0, log_add: bool = False, nbest: int = 1, sil_score: float = 0.0, stats: dict = None):
     """flashlight's lexicon-free CTC beam search without a language model, restated from the published sources (see
     ctc_bracketed_best_path), plus torchaudio's read-out of each hypothesis.  emissions [T][N] (any scores: the reference feeds raw
     logits).  Returns the `nbest` best hypotheses, best first, as (tokens int64, timesteps int32, score float).
@@ -249,23 +249,54 @@ def ctc_beam_search(emissions: np.ndarray, blank: int, sil: int, beam_size: int 
     State of a hypothesis = (token history, last token, last-was-blank); per frame every hypothesis is extended by every token (the
     `beam_size_token` best of the frame when given): a non-blank token that differs from the last one, or follows a blank, EXTENDS
     the history; a blank keeps it and sets the flag; a repeat keeps it.  Candidates below best - beam_threshold are dropped,
-    candidates of equal state are merged (max, or log-add with `log_add`), the `beam_size` best survive.  Test infrastructure for the
-    closed form above and the opt-in `Wav2Vec2_PR.decoder = "flashlight"`: O(T beam N) Python, not a product hot path."""
+    candidates of equal state are merged (max, or log-add with `log_add`), the `beam_size` best survive.  The oracle of the device
+    search (aptai_ctc_beam_search, `Wav2Vec2_PR.decoder = "beam"`) and of the closed form above: O(T beam N) Python, not a product
+    hot path.
+
+    `stats` (optional dict; the result does not depend on it) receives what a test needs to know about its INPUT before it compares
+    another implementation with this one:
+      min_decision_gap   the smallest score difference any decision of the search rests on: last kept vs first dropped merged
+                         candidate, any candidate vs the floor, adjacent n-best scores (the first one not returned included), the
+                         k-th vs (k+1)-th token score where `beam_size_token` cuts, and the best vs second candidate of a merged
+                         state (whose back-pointer survives).  inf when no such pair exists.
+      revived_histories  survivors that extend into a history which existed before the frame, is held by no hypothesis of the beam
+                         it is extended from, and has a descendant in that beam
+      max_merge          the largest number of candidates merged into one state"""
     em = np.asarray(emissions, dtype=np.float64)
     T, N = em.shape
     k_tok = N if beam_size_token is None else min(int(beam_size_token), N)
     trie = {}                                      # (history id, token) -> history id (the ZeroLM state tree)
+    parent_of = {0: None}                          # history id -> parent history id
+    if stats is not None:
+        stats.update(min_decision_gap=float("inf"), revived_histories=0, max_merge=0)
+
+    def gap(d):
+        if stats is not None and d == d:
+            stats["min_decision_gap"] = min(stats["min_decision_gap"], abs(float(d)))
 
     def child(hist, tok):
         key = (hist, tok)
         if key not in trie:
             trie[key] = len(trie) + 1
+            parent_of[trie[key]] = hist
         return trie[key]
 
     # a hypothesis: (score, history id, parent hypothesis or None, token, last-was-blank)
     hyps = [(0.0, 0, None, sil, False)]
     for t in range(T):
         order = np.argsort(-em[t], kind="stable")[:k_tok] if k_tok < N else np.arange(N)
+        if stats is not None:
+            if 0 < k_tok < N:
+                by_score = np.sort(em[t])[::-1]
+                gap(by_score[k_tok - 1] - by_score[k_tok])
+            known = len(trie)                      # history ids up to here existed before the frame
+            held = {h[1] for h in hyps}
+            ancestors = set()
+            for hist in held:
+                hist = parent_of[hist]
+                while hist is not None and hist not in ancestors:
+                    ancestors.add(hist)
+                    hist = parent_of[hist]
         cands, best = [], -np.inf
         for h in hyps:
             hs, hist, _, prev, prev_blank = h
@@ -281,9 +312,27 @@ def ctc_beam_search(emissions: np.ndarray, blank: int, sil: int, beam_size: int 
                 best = max(best, sc)
                 if sc >= best - beam_threshold:
                     cands.append(c)
-        hyps = _merge_and_prune(cands, best - beam_threshold, beam_size, log_add)
+        if stats is not None:                  # every candidate against the floor, those the running maximum dropped included;
+            for h in hyps:                     # the maximum itself passes by construction (threshold >= 0): not a decision
+                for n in order:
+                    sc = h[0] + em[t, int(n)] + (sil_score if int(n) == sil else 0.0)
+                    if sc != best:
+                        gap(sc - (best - beam_threshold))
+        hyps = _merge_and_prune(cands, best - beam_threshold, beam_size, log_add, stats)
+        if stats is not None:
+            stats["revived_histories"] += sum(1 for h in hyps if h[1] != h[2][1] and h[1] <= known and h[1] not in held
+                                              and h[1] in ancestors)
     cands = [(h[0], h[1], h, sil, False) for h in hyps]
-    final = _merge_and_prune(cands, max(c[0] for c in cands) - beam_threshold, beam_size, log_add)
+    best = max(c[0] for c in cands)
+    floor = best - beam_threshold
+    if stats is not None:
+        for c in cands:
+            if c[0] != best:
+                gap(c[0] - floor)
+    final = _merge_and_prune(cands, floor, beam_size, log_add, stats)
+    if stats is not None:
+        for a, b in zip(final[:nbest], final[1:nbest + 1]):
+            gap(a[0] - b[0])
     out = []
     for h in final[:nbest]:
         row, node = [], h
@@ -299,18 +348,28 @@ def ctc_beam_search(emissions: np.ndarray, blank: int, sil: int, beam_size: int 
     return out
 
 
-def _merge_and_prune(cands, floor, beam_size, log_add):
+def _merge_and_prune(cands, floor, beam_size, log_add, stats=None):
     cands = [c for c in cands if c[0] >= floor]
     cands.sort(key=lambda c: (c[1], c[3], c[4], -c[0]))          # equal states adjacent, the best of each first
-    merged = []
+    merged, size = [], 0
     for c in cands:
         if merged and merged[-1][1] == c[1] and merged[-1][3] == c[3] and merged[-1][4] == c[4]:
+            size += 1
+            if stats is not None:
+                stats["max_merge"] = max(stats["max_merge"], size)
+                if size == 2:                                    # best vs second of the state: which back-pointer survives
+                    stats["min_decision_gap"] = min(stats["min_decision_gap"], abs(best_of_state - c[0]))
             if log_add:
                 m = merged[-1]
                 merged[-1] = (float(np.logaddexp(m[0], c[0])),) + m[1:]
             continue
         merged.append(c)
+        size, best_of_state = 1, c[0]
+        if stats is not None:
+            stats["max_merge"] = max(stats["max_merge"], 1)
     merged.sort(key=lambda c: -c[0])
+    if stats is not None and len(merged) > beam_size:
+        stats["min_decision_gap"] = min(stats["min_decision_gap"], abs(merged[beam_size - 1][0] - merged[beam_size][0]))
     return merged[:beam_size]
 
 

@@ -968,6 +968,50 @@ def ctc_greedy_decode(logits, ldl, rows_per_b, B, T, V, blank, max_n):
     return ids, n
 
 
+BEAM_MAX = _C["APTAI_BEAM_MAX"]
+BEAM_MAX_V = _C["APTAI_BEAM_MAX_V"]
+
+
+def ctc_beam_search(logits, ldl, rows_per_b, B, T, V, blank, sil, *, input_lens_i32=None, beam_size=10, beam_size_token=None,
+                    beam_threshold=50.0, log_add=False, sil_score=0.0, nbest=1, max_n=None):
+    """Lexicon-free CTC beam search on the device (aptai_ctc_beam_search, which states the semantics and the tie rule):
+    (tokens int32 [B][nbest][max_n], timesteps int32 [B][nbest][max_n], n_tok int32 [B][nbest], score fp64 [B][nbest],
+    n_hyp int32 [B]), best hypothesis first.  `logits` is read like ctc_greedy_decode reads it; input_lens_i32 = None decodes all T
+    frames of every row; beam_size_token = None uses all V tokens; max_n defaults to T + 2, the longest a hypothesis can be.
+    Nothing here synchronises host and device."""
+    _dev(logits, input_lens_i32)
+    max_n = T + 2 if max_n is None else int(max_n)
+    k_tok = 0 if beam_size_token is None else int(beam_size_token)
+    if not 1 <= beam_size <= BEAM_MAX:
+        raise ValueError(f"ctc_beam_search: beam_size must be 1..{BEAM_MAX}, not {beam_size}")
+    if not 1 <= nbest <= beam_size:
+        raise ValueError(f"ctc_beam_search: nbest must be 1..beam_size ({beam_size}), not {nbest}")
+    if not 1 <= V <= BEAM_MAX_V:
+        raise ValueError(f"ctc_beam_search: V must be 1..{BEAM_MAX_V}, not {V}")
+    if beam_size_token is not None and k_tok < 1:
+        raise ValueError(f"ctc_beam_search: beam_size_token must be None (all tokens) or >= 1, not {beam_size_token}")
+    if not beam_threshold >= 0:
+        raise ValueError(f"ctc_beam_search: beam_threshold must be >= 0, not {beam_threshold}")
+    if not (0 <= blank < V and 0 <= sil < V and blank != sil):
+        raise ValueError(f"ctc_beam_search: blank ({blank}) and sil ({sil}) must be different tokens below V = {V}")
+    if B < 1 or T < 1 or max_n < 1 or ldl < V or rows_per_b < T:
+        raise ValueError(f"ctc_beam_search: bad sizes (B={B}, T={T}, max_n={max_n}, ldl={ldl}, rows_per_b={rows_per_b})")
+    if input_lens_i32 is not None and (input_lens_i32.dtype != torch.int32 or input_lens_i32.numel() != B
+                                       or not input_lens_i32.is_contiguous()):
+        raise ValueError(f"ctc_beam_search: input_lens_i32 must be a contiguous int32 vector of {B} entries")
+    dev = logits.device
+    ws = torch.empty(_lib.lib().aptai_ctc_beam_search_workspace_bytes(B, T, beam_size, nbest), device=dev, dtype=torch.uint8)
+    tokens = torch.empty((B, nbest, max_n), device=dev, dtype=torch.int32)
+    timesteps = torch.empty((B, nbest, max_n), device=dev, dtype=torch.int32)
+    n_tok = torch.empty((B, nbest), device=dev, dtype=torch.int32)
+    score = torch.empty((B, nbest), device=dev, dtype=torch.float64)
+    n_hyp = torch.empty(B, device=dev, dtype=torch.int32)
+    _lib.call("aptai_ctc_beam_search", logits.data_ptr(), ldl, rows_per_b, _ptr(input_lens_i32), B, T, V, blank, sil, beam_size, k_tok,
+              float(beam_threshold), int(bool(log_add)), float(sil_score), nbest, max_n, ws.data_ptr(), tokens.data_ptr(),
+              timesteps.data_ptr(), n_tok.data_ptr(), score.data_ptr(), n_hyp.data_ptr(), _stream())
+    return tokens, timesteps, n_tok, score, n_hyp
+
+
 _TOPOLOGY = {"ctc": 0, "monotonic": 1}
 
 

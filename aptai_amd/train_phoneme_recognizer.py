@@ -3,7 +3,10 @@ function surface (`load_model_optimizer`, `train`, `validate`, `test`), per-batc
 `loss.backward()` -> `optimizer.step()`, everything trainable unless `freeze_feature_extractor`), the reference's RANDOM SUBSET of
 batches per epoch (:406,413), LambdaLR schedule, PER metric, and the three checkpoint families it writes (:472-486):
 `best-model-ckpt/`, `model-ckpts/e%04d.bin` (with `save_all_epochs`) and `last-model-ckpt/` incl. optimizer / scheduler state.
-Decoding for the PER is the best path (the torchaudio beam decoder of utility.py:448-471 is absent: parity unpinned).
+Decoding for the PER is the best path by default.  The torchaudio package behind the beam decoder of utility.py:448-471 is absent,
+so parity with torchaudio itself stays unpinned; `--decoder beam` (cfg.decoder, with cfg.beam_size / cfg.beam_log_add) runs that
+decoder's published algorithm on the device instead (aptai_ctc_beam_search, pinned against hostlogic.ctc_beam_search), and
+`--decoder flashlight` its closed form for the reference's settings.
 The CommonPhone reader, wandb and resume-from-hub are out of scope; `SyntheticCommonPhone` yields items
 with the fields `_collator` consumes.  The shipped script's stale imports / constructor arity are not
 reproduced: the model is `aptai_amd.w2v2_pr.Wav2Vec2_PR(pretrain_cfg, cache_dir, huggingface_model_id, vocab)`.
@@ -17,6 +20,7 @@ import pickle
 import random
 import tempfile
 from pathlib import Path
+from types import SimpleNamespace
 from typing import Dict, Optional
 
 import numpy as np
@@ -76,6 +80,12 @@ def load_model_optimizer(args_cfg, vocab):
     model = Wav2Vec2_PR(pretrain_cfg, getattr(args_cfg, "cache_dir", None), args_cfg.huggingface_model_id, vocab).to(args_cfg.device)
     if getattr(args_cfg, "freeze_feature_extractor", False):
         model.freeze_feature_encoder()
+    # opt-in decoder for the PER of validate() / test(); the class defaults (best path; the reference's beam settings) otherwise
+    model.decoder = getattr(args_cfg, "decoder", None) or Wav2Vec2_PR.decoder
+    beam = {k: v for k, v in (("beam_size", getattr(args_cfg, "beam_size", None)),
+                              ("log_add", getattr(args_cfg, "beam_log_add", None))) if v is not None}
+    if beam:
+        model.beam_options = dict(Wav2Vec2_PR.beam_options, **beam)
     optimizer, lr_scheduler = loops.adam_and_schedule(model.parameters(), args_cfg, publish_to=model)
     return model, optimizer, lr_scheduler
 
@@ -125,20 +135,28 @@ def train(cfg, model, optimizer, lr_scheduler, vocab, train_dataloader, valid_da
     return run.close()
 
 
-def _decode(model, outputs) -> list:
-    """Stand-in for `_ctc_decode(vocab, phoneme_logits)` (utility.py:448-471): best path over all frames of the batch-1 logits
-    (the device decode kernel reads the fp32 logits the forward just produced)."""
+def _decode_ids(model, outputs):
+    """(ids int32 [B][slots] zero-padded, n int32 [B]) on the device, over all frames of the fp32 logits the forward just produced:
+    the best path (aptai_ctc_greedy_decode) unless the model's `decoder` says "flashlight" or "beam" (Wav2Vec2_PR._decode_device)."""
     lg = outputs["phoneme_logits"].float().contiguous()
     B, T, V = lg.shape
+    if getattr(model, "decoder", "best_path") != "best_path":
+        out = SimpleNamespace(_geom=SimpleNamespace(B=B, T=T, Tp=T), _logits_full=lg.view(B * T, V))
+        return model._decode_device(out, T + 2)
     from . import ops
-    ids, n = ops.ctc_greedy_decode(lg, V, T, B, T, V, model._blank(), T)
+    return ops.ctc_greedy_decode(lg, V, T, B, T, V, model._blank(), T)
+
+
+def _decode(model, outputs) -> list:
+    """`_ctc_decode(vocab, phoneme_logits)` (utility.py:448-471) for the batch-1 logits: `_decode_ids`, read back."""
+    ids, n = _decode_ids(model, outputs)
     return [int(i) for i in ids[0, :int(n[0])].cpu().numpy()]
 
 
 def _device_eval(model, device, dl, acc, with_loss, laptop=False, frontend=None):
-    """validate()/test() with `device_metrics=True`: the best-path decode's ids and lengths go straight into the device
+    """validate()/test() with `device_metrics=True`: the decode's ids and lengths go straight into the device
     Levenshtein kernel; nothing is read back before `acc.result()`.  Any batch size (label counts from the -100 padding)."""
-    from . import device_metrics as dm, ops
+    from . import device_metrics as dm
     for batch_idx, batch_x in enumerate(dl):
         if laptop and batch_idx >= 1:
             break
@@ -147,9 +165,7 @@ def _device_eval(model, device, dl, acc, with_loss, laptop=False, frontend=None)
             outputs = model(**batch_x)
         if with_loss:
             acc.add_loss(outputs["loss"])
-        lg = outputs["phoneme_logits"].float().contiguous()
-        B, T, V = lg.shape
-        ids, n = ops.ctc_greedy_decode(lg, V, T, B, T, V, model._blank(), T)
+        ids, n = _decode_ids(model, outputs)
         labels = batch_x["phoneme_labels"]
         acc.add_edit(labels, dm.label_lengths(labels), ids, n)
     return acc.result()
@@ -213,6 +229,12 @@ def main(argv=None):
     ap.add_argument("--learning_rate", type=float, default=5e-6)
     loops.add_shared_arguments(ap)
     ap.add_argument("--save_all_epochs", action="store_true")
+    ap.add_argument("--decoder", default=None, choices=["best_path", "flashlight", "beam"],
+                    help="decoder behind the PER of validate() / test(): the frame argmax (default), the reference's decoder call in "
+                         "closed form, or the lexicon-free CTC beam search on the device")
+    ap.add_argument("--beam_size", type=int, default=None, help="with --decoder beam: hypotheses kept per frame, 1..32 (default 10)")
+    ap.add_argument("--beam_log_add", action="store_true", default=None,
+                    help="with --decoder beam: sum the scores of hypotheses with equal history (true prefix scores) instead of the maximum")
     ap.add_argument("--out", default="pr_exp")
     a = ap.parse_args(argv)
     vocab = default_vocab()
@@ -226,7 +248,8 @@ def main(argv=None):
             model_dir = tmp
         cfg = default_cfg(num_epochs=a.num_epochs, batch_size=a.batch_size, samples_per_epoch=a.samples_per_epoch,
                           learning_rate=a.learning_rate, save_all_epochs=a.save_all_epochs, huggingface_model_id=model_dir,
-                          pretrain_cfg=w2v, **loops.shared_arguments(a))
+                          pretrain_cfg=w2v, decoder=a.decoder, beam_size=a.beam_size, beam_log_add=a.beam_log_add,
+                          **loops.shared_arguments(a))
         model, optimizer, lr_scheduler = load_model_optimizer(cfg, vocab)
     collate = hostlogic.collate_pr_raw if loops.uses_frontend(a) else hostlogic.collate_pr
     tr = torch.utils.data.DataLoader(SyntheticCommonPhone(a.train_items, a.seconds, len(vocab), seed=1, source_rate=a.source_rate),

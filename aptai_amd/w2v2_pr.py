@@ -1,9 +1,15 @@
 """``Wav2Vec2_PR`` — drop-in for the reference's CTC phoneme recogniser (models/w2v2_pr.py:18-291) on MI355X.
 
 Same constructor ``(pretrain_cfg, cache_dir, huggingface_model_id, vocab)``, ``forward(input_values, input_lengths,
-phoneme_labels)`` dict, inference helpers and state-dict keys (``wav2vec2.*``, ``pr_head.*``).  The torchaudio /
-flashlight beam-search decoder the reference calls (models/w2v2_pr.py:143-159) is not in the image: decoding here is
-the best path (frame argmax on the device, collapse + blank removal on the host) — *parity unpinned* (SURVEY.md §8c).
+phoneme_labels)`` dict, inference helpers and state-dict keys (``wav2vec2.*``, ``pr_head.*``).  The torchaudio package whose
+flashlight beam-search decoder the reference calls (models/w2v2_pr.py:143-159) is not in the image, so parity with torchaudio
+itself stays *unpinned* (SURVEY.md §8c); the default decoding is the best path (frame argmax on the device, collapse + blank
+removal on the host).
+
+``model.decoder = "beam"`` (opt-in) runs the published algorithm of that decoder on the device (aptai_ctc_beam_search,
+csrc/decode.hip), pinned against its Python restatement hostlogic.ctc_beam_search: ``beam_options`` default to the reference's
+call (beam 10, threshold 50, max-merge, 1-best) and also give what no closed form can: true prefix scores (``log_add``), token
+beams, and through ``decode_nbest`` / ``predict_nbest`` n-best lists with per-token timesteps.
 
 ``model.decoder = "flashlight"`` (opt-in) returns what the published decoder sources say that call returns for the
 reference's settings: the same best path FRAMED by the decoder's opening / closing silence token ``'(...)'``, timesteps as
@@ -153,22 +159,43 @@ class Wav2Vec2_PR(nn.Module):
     def _blank(self) -> int:
         return int(self.vocab.get('(blank)', 0)) if isinstance(self.vocab, dict) else 0
 
-    decoder = "best_path"           # or "flashlight": framed like the reference's torchaudio decoder call (module docstring)
+    decoder = "best_path"           # or "flashlight": framed like the reference's torchaudio decoder call; or "beam": the search
+    #                                 itself on the device (module docstring)
+    # keywords of ops.ctc_beam_search for decoder = "beam"; the defaults are the reference's decoder call (models/w2v2_pr.py:144-153)
+    beam_options = {"beam_size": 10, "beam_threshold": 50.0, "log_add": False, "nbest": 1}
 
     def _sil(self):
         if self.decoder == "best_path":
             return None
-        if self.decoder != "flashlight":
-            raise ValueError(f"Wav2Vec2_PR.decoder must be 'best_path' or 'flashlight', not {self.decoder!r}")
+        if self.decoder not in ("flashlight", "beam"):
+            raise ValueError(f"Wav2Vec2_PR.decoder must be 'best_path', 'flashlight' or 'beam', not {self.decoder!r}")
         if not (isinstance(self.vocab, dict) and '(...)' in self.vocab):
-            raise ValueError("decoder = 'flashlight' needs the silence token '(...)' in the vocabulary (models/w2v2_pr.py:153)")
+            raise ValueError(f"decoder = {self.decoder!r} needs the silence token '(...)' in the vocabulary (models/w2v2_pr.py:153)")
         return int(self.vocab['(...)'])
+
+    def _beam_search(self, out, **options):
+        """ops.ctc_beam_search over the logits of `out`, `beam_options` overridden by `options`: the five device tensors.  All
+        frames of the padded batch are decoded, like the reference's decoder call; with batch_invariant each row stops at its own
+        frame count (`input_lens`), which is what the utterance gets alone.  Nothing here synchronises host and device."""
+        if not (isinstance(self.vocab, dict) and '(...)' in self.vocab):
+            raise ValueError("the beam search needs the silence token '(...)' in the vocabulary (models/w2v2_pr.py:153)")
+        g, full = out._geom, out._logits_full
+        opts = dict(self.beam_options)
+        opts.update(options)
+        own = getattr(g, "fir_lens", None)
+        lens = None if own is None else own.to(torch.int32).contiguous()
+        return ops.ctc_beam_search(full, full.shape[1], g.Tp, g.B, g.T, self.pr_head.weight.shape[0], self._blank(),
+                                   int(self.vocab['(...)']), input_lens_i32=lens, **opts)
 
     def _decode_device(self, out, max_n: int):
         """Best-path decode on the device (aptai_ctc_greedy_decode): (ids int32 [B][max_n] zero-padded, n int32 [B]) over ALL
         frames of the padded batch, like the reference's decoder call (models/w2v2_pr.py:155 passes no lengths).  Nothing
         here synchronises host and device.  decoder = "flashlight": the sequence is framed by the silence token on the device
-        (hostlogic.ctc_bracketed_best_path: prepended / appended unless the first / last frame's own token is the silence)."""
+        (hostlogic.ctc_bracketed_best_path: prepended / appended unless the first / last frame's own token is the silence).
+        decoder = "beam": the top hypothesis of the device beam search (aptai_ctc_beam_search), n = its full length."""
+        if self.decoder == "beam":
+            tokens, _, n_tok, _, _ = self._beam_search(out, max_n=max_n)
+            return tokens[:, 0].contiguous(), n_tok[:, 0].contiguous()
         g, full = out._geom, out._logits_full
         V = self.pr_head.weight.shape[0]
         own = getattr(g, "fir_lens", None)
@@ -206,6 +233,44 @@ class Wav2Vec2_PR(nn.Module):
         ids, n = self._decode_device(out, out._geom.T + 2)
         ids, n = ids.cpu().numpy(), n.cpu().numpy()
         return [ids[b, :n[b]].astype(np.int64) for b in range(len(n))]
+
+    def _nbest(self, audio_inputs, audio_lengths, options):
+        self.eval()
+        with torch.no_grad():
+            out, _ = self._logits_eval(audio_inputs, audio_lengths[:, None] if audio_lengths.dim() == 1 else audio_lengths)
+            tokens, timesteps, n_tok, score, n_hyp = self._beam_search(out, **options)
+            frame_lens = self.wav2vec2._get_feat_extract_output_lengths(audio_lengths.reshape(-1).to(tokens.device)).to(torch.int32)
+            return {'tokens': tokens, 'timesteps': timesteps, 'n_tok': n_tok, 'score': score, 'n_hyp': n_hyp,
+                    'frame_seq_lens': frame_lens}, out._geom.T
+
+    def decode_nbest(self, audio_inputs, audio_lengths, **options):
+        """n-best lists of the batch from the device beam search, whatever `decoder` is set to: `beam_options` overridden by
+        `options` (beam_size, beam_size_token, beam_threshold, log_add, sil_score, nbest, max_n: ops.ctc_beam_search).  Runs in eval
+        mode without gradients.  Returns DEVICE tensors and never synchronises:
+          tokens, timesteps int32 [B][nbest][max_n]  zero-padded; a timestep is the position in the framed token row (frame t -> t + 1)
+          n_tok             int32 [B][nbest]         length of each hypothesis (0: the row has fewer hypotheses)
+          score             fp64  [B][nbest]         best first; -inf where the row has fewer hypotheses
+          n_hyp             int32 [B]
+          frame_seq_lens    int32 [B]"""
+        return self._nbest(audio_inputs, audio_lengths, options)[0]
+
+    def predict_nbest(self, wav, vocab, **options):
+        """`predict_phonemes_durations` for every hypothesis of the n-best list of ONE utterance, best first: a list of
+        {'phn_seq_idx', 'phn_seq_ipa', 'phn_seq_dur', 'score'}.  One device->host transfer (int32 values are exact in fp64)."""
+        wav, wav_input, wav_len = self._wav(wav)
+        res, n_frames = self._nbest(wav_input, wav_len, options)
+        nb, max_n = res['tokens'].shape[1:]
+        packed = torch.cat([res['tokens'][0].double(), res['timesteps'][0].double(), res['n_tok'][0, :, None].double(),
+                            res['score'][0, :, None], res['n_hyp'][:1, None].expand(nb, 1).double()], dim=1).cpu().numpy()
+        frame_sec_ratio = len(wav) / n_frames / 16000
+        inv = {v: k for k, v in vocab.items()}
+        hyps = []
+        for r in packed[:int(packed[0, -1])]:
+            n = min(int(r[2 * max_n]), max_n)
+            idx = r[:n].astype(np.int64)
+            hyps.append({'phn_seq_idx': idx, 'phn_seq_ipa': [inv.get(int(i), '?') for i in idx],
+                         'phn_seq_dur': [int(t) * frame_sec_ratio for t in r[max_n:max_n + n]], 'score': float(r[2 * max_n + 1])})
+        return hyps
 
     def get_embeddings_grad(self, audio_inputs, audio_lengths, vocab, intermediate_hidden, latter_hidden):
         """models/w2v2_pr.py:91-122: the encoder in whatever mode the module is in, WITH gradients (probing / saliency use):
@@ -268,9 +333,15 @@ class Wav2Vec2_PR(nn.Module):
         self.eval()
         with torch.no_grad():
             wav, wav_input, wav_len = self._wav(wav)
-            _, logits = self._logits_eval(wav_input, wav_len)
+            out, logits = self._logits_eval(wav_input, wav_len)
             frame_sec_ratio = len(wav) / logits.size(1) / 16000
-            idx, ts = hostlogic.ctc_bracketed_best_path(logits[0].cpu().numpy(), logits.size(1), self._blank(), self._sil())
+            if self.decoder == "beam":      # tokens AND timesteps of the device search's top hypothesis, one transfer
+                tokens, timesteps, n_tok, _, _ = self._beam_search(out)
+                row = torch.cat([n_tok[0, :1], tokens[0, 0], timesteps[0, 0]]).cpu().numpy()
+                n = min(int(row[0]), tokens.shape[2])
+                idx, ts = row[1:1 + n].astype(np.int64), row[1 + tokens.shape[2]:1 + tokens.shape[2] + n].astype(np.int32)
+            else:
+                idx, ts = hostlogic.ctc_bracketed_best_path(logits[0].cpu().numpy(), logits.size(1), self._blank(), self._sil())
             inv = {v: k for k, v in vocab.items()}
             return {'phn_seq_idx': idx, 'phn_seq_ipa': [inv.get(int(i), '?') for i in idx],
                     'phn_seq_dur': [t * frame_sec_ratio for t in ts]}

@@ -514,6 +514,38 @@ int64_t aptai_ctc_viterbi_workspace_bytes(int64_t B, int64_t T, int64_t ldt);
  * decoded length, which the caller compares with max_n (models/force_aptai.py:111). */
 int aptai_ctc_greedy_decode(const float* logits, int64_t ldl, int64_t rows_per_b, int64_t B, int64_t T, int64_t V, int blank,
                             int32_t* ids_out, int64_t max_n, int32_t* n_out, void* stream);
+/* Lexicon-free CTC beam search without a language model, on the device: the decoder the reference calls through torchaudio
+ * (models/w2v2_pr.py:143-159, flashlight's LexiconFreeDecoder with a zero LM) as its published sources state it, with n-best
+ * lists, true prefix scores (log_add) and per-token timesteps.  aptai_amd/hostlogic.py ctc_beam_search restates the same search
+ * in Python and is what the tests compare against; torchaudio itself is not available to this project: parity with it is unpinned.
+ * logits fp32 rows (b*rows_per_b + t) stride ldl (the layout of aptai_ctc_greedy_decode); input_lens int32 [B] or null (= all T
+ * frames of every row); V <= 256; blank != sil, both < V; beam_size 1..APTAI_BEAM_MAX; beam_size_token 0 = all V tokens, else the
+ * k best tokens of each frame (ties to the lower id); beam_threshold >= 0; nbest 1..beam_size; caller-owned workspace of
+ * aptai_ctc_beam_search_workspace_bytes, 16-byte aligned; the passed stream; no synchronisation.
+ * A hypothesis is (token history, last token, last-was-blank) and starts as (empty, sil, no) with score 0.  Per frame t every
+ * hypothesis is extended by every token n of the token beam: sc = (score + (double)x[t][n]) + (n == sil ? sil_score : 0) in fp64,
+ * in that order.  A non-blank n that differs from the last token, or follows a blank, extends the history; a blank keeps it and
+ * sets the flag; a repeat keeps it.  Candidates below (frame maximum - beam_threshold) are dropped; candidates of equal state
+ * merge, the best one's back-pointer survives; its score stays (log_add 0) or the scores are folded with logaddexp in descending
+ * order starting from the best (log_add 1); the beam_size best merged candidates survive.  Histories are equal when their token
+ * sequences are, for the whole utterance, also when a history left the beam and is reached again.  After the last frame every
+ * hypothesis takes the closing silence, which makes its state (history, sil, no): equal histories merge, floor and cut are applied
+ * once more and the nbest best are read out: the T_b + 2 token row (opening silence, one token per frame, closing silence) has its
+ * repeats collapsed and its blanks dropped, the row positions kept are the timesteps (a frame t appears as t + 1).  T_b == 0 gives
+ * the single hypothesis [sil] at timestep 0 with score 0.
+ * TIE RULE: of two candidates with exactly equal scores the one from the lower beam slot (the better parent) comes first, then
+ * the lower token id, in the merge (whose back-pointer survives) as in the selection.  No atomics: same inputs -> same bits.
+ * Outputs: tokens, timesteps int32 [B][nbest][max_n], zero-padded; n_tok int32 [B][nbest] = full length (what exceeds max_n is
+ * cut, as in aptai_ctc_greedy_decode), 0 for a rank without hypothesis; score fp64 [B][nbest], -inf for a rank without hypothesis;
+ * n_hyp int32 [B] = hypotheses returned for the row.  Non-finite logits are not supported (a NaN never wins a comparison). */
+#define APTAI_BEAM_MAX 32
+#define APTAI_BEAM_MAX_V 256
+int aptai_ctc_beam_search(const float* logits, int64_t ldl, int64_t rows_per_b, const int32_t* input_lens, int64_t B, int64_t T,
+                          int64_t V, int blank, int sil, int beam_size, int beam_size_token, double beam_threshold, int log_add,
+                          double sil_score, int nbest, int64_t max_n, void* workspace, int32_t* tokens, int32_t* timesteps,
+                          int32_t* n_tok, double* score, int32_t* n_hyp, void* stream);
+/* 0 for arguments outside the limits above */
+int64_t aptai_ctc_beam_search_workspace_bytes(int64_t B, int64_t T, int64_t beam_size, int64_t nbest);
 
 /* ------------------------------------------------------------------------------------------------ Force_APTAI heads (fp32)
  * Small layers behind the frozen encoder of models/force_aptai.py:108-161.  fp32 because they feed an argmax whose
