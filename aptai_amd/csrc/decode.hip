@@ -12,6 +12,10 @@
 //      lane rank: no atomics), writes the next beam and the frame's back-pointers.
 // Histories are nodes (parent, token) of a trie in the workspace, found through a chained hash table keyed by (parent, token): equal
 // token sequences have equal node ids for the whole utterance, also when a history left the beam and is reached again.
+// aptai_ctc_beam_search_lm is the second instantiation of the same kernel (template <bool LM>): a token n-gram compiled to a dense
+// automaton (aptai_amd/ngram.py) adds lm_w[state][n] to every candidate that extends its history.  The state of a history lives in
+// the fourth int of its trie node and, per beam slot, in LDS; the frame maximum, which slot 0 no longer has to reach, is a pass over
+// all candidates in front of step 2.  The nh table rows of a frame are read straight through L2 (DESIGN.md has the reasoning).
 // Memory: trie, hash heads, back-pointers and token rows are written and read by this workgroup only, always with a __syncthreads()
 // between (workgroup scope is enough).
 #include <math.h>
@@ -33,13 +37,21 @@ struct BeamArgs {
     const int32_t* input_lens;
     int T, V, blank, sil, beam, ktok, log_add, nbest, max_n;
     double thr, sil_score;
-    int4* nodes;        // per utterance node_cap entries {parent node, token, next in hash chain, 0}
+    int4* nodes;        // per utterance node_cap entries {parent node, token, next in hash chain, LM state (0 without an LM)}
     int* heads;         // per utterance n_heads (power of two) chain heads, -1 = empty
     uint16_t* bp;       // per utterance [T][beam]  (parent slot << 8) | token
     uint8_t* rows;      // per utterance [nbest][T + 2] token rows of the hypotheses read out
     long node_cap, n_heads;
     int32_t *tokens, *timesteps, *n_tok, *n_hyp;
     double* score;
+};
+
+// the n-gram automaton of aptai_ctc_beam_search_lm, pre-multiplied by the LM weight on the host: w [C][V], next [C][V], wfinal [C]
+struct LmArgs {
+    const double* w;
+    const int32_t* next;
+    const double* wfinal;
+    int start;
 };
 
 struct Key {
@@ -91,19 +103,55 @@ struct Shared {
     int nh, pool_n, n_hyp;
 };
 
+// with a language model: its state per beam slot, and the waves' shares of the frame maximum
+struct SharedLM : Shared {
+    int lms[2][BMAX];
+    double wmax[NWAVES];
+};
+template <bool LM> struct SharedOf { typedef Shared type; };
+template <> struct SharedOf<true> { typedef SharedLM type; };
+
+// the LM term of token n from slot h, which must extend there: the table arrives multiplied by the LM weight, read through L2
+__device__ __forceinline__ double lm_term(const SharedLM& sh, int cur, int h, int n, int V, const LmArgs& lm) {
+    return lm.w[sh.lms[cur][h] * V + n];
+}
+
+// Score of candidate (slot h, token n) on its own: (hs + x) + bonus in fp64, then, with an LM and where n extends the history
+// of h, + lm_w[state][n] as a plain add (no multiply on the device, so nothing for the compiler to fuse).
+template <bool LM, typename S>
+__device__ __forceinline__ double cand_score(const S& sh, int cur, int h, int n, const BeamArgs& a, const LmArgs& lm) {
+    double sc = (sh.hs[cur][h] + (double)sh.x[cur][n]) + (n == a.sil ? a.sil_score : 0.0);
+    if constexpr (LM) {
+        if (n != a.blank && (n != sh.prev[cur][h] || sh.flag[cur][h])) sc = sc + lm_term(sh, cur, h, n, a.V, lm);
+    }
+    return sc;
+}
+
 // Candidate (slot h, token n) of the frame.  States that can coincide (at most three candidates per state):
 //   blank        (hist_h, blank, 1)   <- the blank of the other slot with history hist_h
 //   repeat       (hist_h, n, 0)       <- token n from the slots whose history is the parent of hist_h, where it extends
 //   extension    (hist_h + n, n, 0)   <- token n from the other slot with history hist_h, where it extends, and the repeat of the
 //                                        slot whose history is hist_h + n
 // The best of a state (tie: lower slot; the token is the same) returns the merged score, the others return a dead key.
-__device__ __forceinline__ Key eval_cand(const Shared& sh, int cur, int h, int n, double floor_, const BeamArgs& a) {
+// LM: every partner takes its own term by the rule of cand_score: the twin that extends shares the history, hence the state and
+// the term; pa / pb extend from the parent's state; blanks and repeats take none.
+template <bool LM, typename S>
+__device__ __forceinline__ Key eval_cand(const S& sh, int cur, int h, int n, double floor_, const BeamArgs& a, const LmArgs& lm) {
     const Key dead = {-INFINITY, DEAD};
     const double xs = (double)sh.x[cur][n];
     const double bonus = n == a.sil ? a.sil_score : 0.0;
-    const double sc = (sh.hs[cur][h] + xs) + bonus;
-    if (!(sc >= floor_)) return dead;
     const int prev = sh.prev[cur][h], flag = sh.flag[cur][h];
+    double sc = (sh.hs[cur][h] + xs) + bonus;
+    double t1 = 0.0, t2 = 0.0;       // LM terms of the partners q1, q2
+    bool lm1 = false, lm2 = false;
+    if constexpr (LM) {
+        if (n != a.blank && (n != prev || flag)) {
+            t1 = lm_term(sh, cur, h, n, a.V, lm);
+            sc = sc + t1;
+            lm1 = true;
+        }
+    }
+    if (!(sc >= floor_)) return dead;
     int q1 = -1, q2 = -1;
     if (n == a.blank) {
         q1 = sh.twin[h];
@@ -112,6 +160,10 @@ __device__ __forceinline__ Key eval_cand(const Shared& sh, int cur, int h, int n
         if (p >= 0 && (sh.prev[cur][p] != n || sh.flag[cur][p])) q1 = p;
         p = sh.pb[h];
         if (p >= 0 && (sh.prev[cur][p] != n || sh.flag[cur][p])) q2 = p;
+        if constexpr (LM) {
+            if (q1 >= 0) { t1 = lm_term(sh, cur, q1, n, a.V, lm); lm1 = true; }
+            if (q2 >= 0) { t2 = lm_term(sh, cur, q2, n, a.V, lm); lm2 = true; }
+        }
     } else {
         const int p = sh.twin[h];
         if (p >= 0 && (sh.prev[cur][p] != n || sh.flag[cur][p])) q1 = p;
@@ -123,8 +175,16 @@ __device__ __forceinline__ Key eval_cand(const Shared& sh, int cur, int h, int n
     }
     double s1 = -INFINITY, s2 = -INFINITY;
     bool v1 = false, v2 = false;
-    if (q1 >= 0) { s1 = (sh.hs[cur][q1] + xs) + bonus; v1 = s1 >= floor_; }
-    if (q2 >= 0) { s2 = (sh.hs[cur][q2] + xs) + bonus; v2 = s2 >= floor_; }
+    if (q1 >= 0) {
+        s1 = (sh.hs[cur][q1] + xs) + bonus;
+        if constexpr (LM) { if (lm1) s1 = s1 + t1; }
+        v1 = s1 >= floor_;
+    }
+    if (q2 >= 0) {
+        s2 = (sh.hs[cur][q2] + xs) + bonus;
+        if constexpr (LM) { if (lm2) s2 = s2 + t2; }
+        v2 = s2 >= floor_;
+    }
     if (v1 && (s1 > sc || (s1 == sc && q1 < h))) return dead;
     if (v2 && (s2 > sc || (s2 == sc && q2 < h))) return dead;
     double m = sc;
@@ -146,8 +206,10 @@ __device__ __forceinline__ uint32_t node_hash(int parent, int tok) {
     return h ^ (h >> 15);
 }
 
-__global__ __launch_bounds__(NTHREADS) void ctc_beam_kernel(BeamArgs a) {
-    __shared__ Shared sh;
+// LM = false is the search without a language model (`lm` is not read); LM = true adds the n-gram automaton `lm`
+template <bool LM>
+__global__ __launch_bounds__(NTHREADS) void ctc_beam_kernel(BeamArgs a, LmArgs lm) {
+    __shared__ typename SharedOf<LM>::type sh;
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int V = a.V, beam = a.beam;
     int Tb = a.input_lens ? a.input_lens[b] : a.T;
@@ -161,7 +223,8 @@ __global__ __launch_bounds__(NTHREADS) void ctc_beam_kernel(BeamArgs a) {
 
     for (long i = tid; i < a.n_heads; i += NTHREADS) heads[i] = -1;
     if (tid == 0) {
-        nodes[0] = make_int4(-1, a.sil, -1, 0);
+        nodes[0] = make_int4(-1, a.sil, -1, LM ? lm.start : 0);
+        if constexpr (LM) sh.lms[0][0] = lm.start;
         sh.hs[0][0] = 0.0;
         sh.hist[0][0] = 0;
         sh.par[0][0] = -1;
@@ -212,25 +275,39 @@ __global__ __launch_bounds__(NTHREADS) void ctc_beam_kernel(BeamArgs a) {
             sh.pb[tid] = p1;
         }
         __syncthreads();
-        // ---- 2: candidates, 32 best per wave.  The frame maximum is reached from slot 0 (the beam is sorted and rounding is monotone).
+        // ---- 2: candidates, 32 best per wave.  The frame maximum is reached from slot 0 (the beam is sorted and rounding is monotone)
+        // without an LM; with one any slot can reach it: a pass over all nh x na candidates, the waves' maxima meet in LDS.
+        const int NC = nh * na;
         double best = -INFINITY;
-        for (int i = lane; i < na; i += 64) {
-            const int n = sh.act[i];
-            best = fmax(best, (sh.hs[cur][0] + (double)sh.x[cur][n]) + (n == a.sil ? a.sil_score : 0.0));
+        if constexpr (LM) {
+            for (int idx = tid; idx < NC; idx += NTHREADS) {
+                const int h = idx / na;
+                best = fmax(best, cand_score<true>(sh, cur, h, sh.act[idx - h * na], a, lm));
+            }
+        } else {
+            for (int i = lane; i < na; i += 64) {
+                const int n = sh.act[i];
+                best = fmax(best, (sh.hs[cur][0] + (double)sh.x[cur][n]) + (n == a.sil ? a.sil_score : 0.0));
+            }
         }
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) best = fmax(best, __shfl_xor(best, o, 64));
+        if constexpr (LM) {
+            if (lane == 0) sh.wmax[wave] = best;
+            __syncthreads();
+#pragma unroll
+            for (int w = 0; w < NWAVES; ++w) best = fmax(best, sh.wmax[w]);
+        }
         const double floor_ = best - a.thr;
         double rs = -INFINITY;
         uint32_t rc = DEAD;
-        const int NC = nh * na;
         bool first = true;
         for (int base = wave * 64; base < NC; base += NTHREADS) {
             const int idx = base + lane;
             Key k = {-INFINITY, DEAD};
             if (idx < NC) {
                 const int h = idx / na;
-                k = eval_cand(sh, cur, h, sh.act[idx - h * na], floor_, a);
+                k = eval_cand<LM>(sh, cur, h, sh.act[idx - h * na], floor_, a, lm);
             }
             if (!__ballot(k.c != DEAD)) continue;
             sort64(k.s, k.c, lane);
@@ -259,13 +336,21 @@ __global__ __launch_bounds__(NTHREADS) void ctc_beam_kernel(BeamArgs a) {
             const bool ext = surv && n != a.blank && (n != oprev || oflag);
             int id = -1, headv = -1;
             uint32_t bucket = 0xffffffffu;
+            int nstate = 0;            // LM: the state of the survivor's history: kept, read from a known node, or next[state][n]
+            if constexpr (LM) nstate = sh.lms[cur][h];
             if (ext) {
                 bucket = node_hash(ohist, n) & hmask;
                 headv = heads[bucket];
                 for (id = headv; id >= 0;) {
                     const int4 nd = nodes[id];
-                    if (nd.x == ohist && nd.y == n) break;
+                    if (nd.x == ohist && nd.y == n) {
+                        if constexpr (LM) nstate = nd.w;
+                        break;
+                    }
                     id = nd.z;
+                }
+                if constexpr (LM) {
+                    if (id < 0) nstate = lm.next[nstate * V + n];
                 }
             }
             const bool alloc = ext && id < 0;
@@ -284,7 +369,7 @@ __global__ __launch_bounds__(NTHREADS) void ctc_beam_kernel(BeamArgs a) {
                     }
                 }
                 if (alloc) {
-                    nodes[id] = make_int4(ohist, n, chain, 0);
+                    nodes[id] = make_int4(ohist, n, chain, nstate);
                     if (lowest) heads[bucket] = id;
                 }
             }
@@ -294,6 +379,7 @@ __global__ __launch_bounds__(NTHREADS) void ctc_beam_kernel(BeamArgs a) {
                 sh.par[nxt][lane] = ext ? ohist : opar;
                 sh.prev[nxt][lane] = n;
                 sh.flag[nxt][lane] = n == a.blank ? 1 : 0;
+                if constexpr (LM) sh.lms[nxt][lane] = nstate;
                 bp[(long)t * beam + lane] = (uint16_t)rc;
             }
             if (lane == 0) {
@@ -308,11 +394,22 @@ __global__ __launch_bounds__(NTHREADS) void ctc_beam_kernel(BeamArgs a) {
     // ---- the closing silence: hypotheses of equal history merge, floor and cut once more, the nbest best are walked back
     if (wave == 0) {
         const int cur = Tb & 1, nh = sh.nh;
-        const double floor_ = sh.hs[cur][0] - a.thr;
+        // LM: every hypothesis takes lm_wfinal of its history's state first; the maximum is then any slot's
+        double fin = 0.0, top = sh.hs[cur][0];
+        if constexpr (LM) {
+            top = -INFINITY;
+            if (lane < nh) {
+                fin = lm.wfinal[sh.lms[cur][lane]];
+                top = sh.hs[cur][lane] + fin;
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) top = fmax(top, __shfl_xor(top, o, 64));
+        }
+        const double floor_ = top - a.thr;
         double rs = -INFINITY;
         uint32_t rc = DEAD;
         if (lane < nh) {
-            const double sc = sh.hs[cur][lane];
+            const double sc = LM ? sh.hs[cur][lane] + fin : sh.hs[cur][lane];
             const int hh = sh.hist[cur][lane];
             int q = -1;
             for (int h = 0; h < nh; ++h)
@@ -320,7 +417,7 @@ __global__ __launch_bounds__(NTHREADS) void ctc_beam_kernel(BeamArgs a) {
             bool alive = sc >= floor_;
             double m = sc;
             if (alive && q >= 0) {
-                const double sq = sh.hs[cur][q];
+                const double sq = LM ? sh.hs[cur][q] + fin : sh.hs[cur][q];      // equal history, equal state, equal term
                 if (sq >= floor_) {
                     if (sq > sc || (sq == sc && q < lane)) alive = false;
                     else if (a.log_add) m = logaddexp_ge(sc, sq);
@@ -391,18 +488,11 @@ BeamLayout beam_layout(int64_t B, int64_t T, int64_t beam, int64_t nbest) {
     return l;
 }
 
-}  // namespace
-
-extern "C" int64_t aptai_ctc_beam_search_workspace_bytes(int64_t B, int64_t T, int64_t beam_size, int64_t nbest) {
-    if (B <= 0 || T <= 0 || beam_size <= 0 || beam_size > BMAX || nbest <= 0 || nbest > beam_size) return 0;
-    return beam_layout(B, T, beam_size, nbest).total;
-}
-
-extern "C" int aptai_ctc_beam_search(const float* logits, int64_t ldl, int64_t rows_per_b, const int32_t* input_lens, int64_t B,
-                                     int64_t T, int64_t V, int blank, int sil, int beam_size, int beam_size_token,
-                                     double beam_threshold, int log_add, double sil_score, int nbest, int64_t max_n, void* workspace,
-                                     int32_t* tokens, int32_t* timesteps, int32_t* n_tok, double* score, int32_t* n_hyp, void* stream) {
-    const char* who = "aptai_ctc_beam_search";
+// both entry points: the checks they share, then the instantiation without (lm == nullptr) or with a language model
+int beam_search(const char* who, const LmArgs* lm, const float* logits, int64_t ldl, int64_t rows_per_b, const int32_t* input_lens,
+                int64_t B, int64_t T, int64_t V, int blank, int sil, int beam_size, int beam_size_token, double beam_threshold,
+                int log_add, double sil_score, int nbest, int64_t max_n, void* workspace, int32_t* tokens, int32_t* timesteps,
+                int32_t* n_tok, double* score, int32_t* n_hyp, void* stream) {
     APTAI_REQUIRE(logits && workspace && tokens && timesteps && n_tok && score && n_hyp, "%s: null pointer", who);
     APTAI_REQUIRE(B > 0 && T > 0 && V > 0 && V <= MAXV && ldl >= V && rows_per_b >= T && T < (1 << 24),
                   "%s: bad sizes (V=%ld, max %d)", who, (long)V, MAXV);
@@ -428,7 +518,44 @@ extern "C" int aptai_ctc_beam_search(const float* logits, int64_t ldl, int64_t r
     a.rows = (uint8_t*)((char*)workspace + l.rows);
     a.node_cap = l.node_cap; a.n_heads = l.n_heads;
     a.tokens = tokens; a.timesteps = timesteps; a.n_tok = n_tok; a.n_hyp = n_hyp; a.score = score;
-    APTAI_LAUNCH(ctc_beam_kernel, dim3((unsigned)B), dim3(NTHREADS), 0, (hipStream_t)stream, a);
+    if (lm) {
+        APTAI_LAUNCH(ctc_beam_kernel<true>, dim3((unsigned)B), dim3(NTHREADS), 0, (hipStream_t)stream, a, *lm);
+    } else {
+        APTAI_LAUNCH(ctc_beam_kernel<false>, dim3((unsigned)B), dim3(NTHREADS), 0, (hipStream_t)stream, a, LmArgs{});
+    }
     APTAI_CHECK_LAUNCH("ctc_beam_kernel");
     return APTAI_OK;
+}
+
+}  // namespace
+
+extern "C" int64_t aptai_ctc_beam_search_workspace_bytes(int64_t B, int64_t T, int64_t beam_size, int64_t nbest) {
+    if (B <= 0 || T <= 0 || beam_size <= 0 || beam_size > BMAX || nbest <= 0 || nbest > beam_size) return 0;
+    return beam_layout(B, T, beam_size, nbest).total;
+}
+
+extern "C" int aptai_ctc_beam_search(const float* logits, int64_t ldl, int64_t rows_per_b, const int32_t* input_lens, int64_t B,
+                                     int64_t T, int64_t V, int blank, int sil, int beam_size, int beam_size_token,
+                                     double beam_threshold, int log_add, double sil_score, int nbest, int64_t max_n, void* workspace,
+                                     int32_t* tokens, int32_t* timesteps, int32_t* n_tok, double* score, int32_t* n_hyp, void* stream) {
+    return beam_search("aptai_ctc_beam_search", nullptr, logits, ldl, rows_per_b, input_lens, B, T, V, blank, sil, beam_size,
+                       beam_size_token, beam_threshold, log_add, sil_score, nbest, max_n, workspace, tokens, timesteps, n_tok, score,
+                       n_hyp, stream);
+}
+
+extern "C" int aptai_ctc_beam_search_lm(const float* logits, int64_t ldl, int64_t rows_per_b, const int32_t* input_lens, int64_t B,
+                                        int64_t T, int64_t V, int blank, int sil, int beam_size, int beam_size_token,
+                                        double beam_threshold, int log_add, double sil_score, int nbest, int64_t max_n,
+                                        void* workspace, int32_t* tokens, int32_t* timesteps, int32_t* n_tok, double* score,
+                                        int32_t* n_hyp, const double* lm_w, const int32_t* lm_next, const double* lm_wfinal,
+                                        int64_t lm_states, int lm_start, void* stream) {
+    const char* who = "aptai_ctc_beam_search_lm";
+    APTAI_REQUIRE(lm_w && lm_next && lm_wfinal, "%s: null language model table", who);
+    APTAI_REQUIRE(lm_states >= 1, "%s: lm_states must be >= 1 (got %ld)", who, (long)lm_states);
+    APTAI_REQUIRE(lm_start >= 0 && lm_start < lm_states, "%s: lm_start %d outside [0, lm_states = %ld)", who, lm_start, (long)lm_states);
+    APTAI_REQUIRE(V > 0 && lm_states <= (1ll << 24) / V, "%s: lm_states * V must not exceed 2^24 (lm_states %ld, V=%ld)", who,
+                  (long)lm_states, (long)V);
+    const LmArgs lm = {lm_w, lm_next, lm_wfinal, lm_start};
+    return beam_search(who, &lm, logits, ldl, rows_per_b, input_lens, B, T, V, blank, sil, beam_size, beam_size_token, beam_threshold,
+                       log_add, sil_score, nbest, max_n, workspace, tokens, timesteps, n_tok, score, n_hyp, stream);
 }

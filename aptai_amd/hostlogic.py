@@ -241,10 +241,11 @@ def ctc_bracketed_best_path(logits: np.ndarray, length: int, blank: int = 0, sil
 
 
 def ctc_beam_search(emissions: np.ndarray, blank: int, sil: int, beam_size: int = 10, beam_size_token: int = None,
-                    beam_threshold: float = 50.0, log_add: bool = False, nbest: int = 1, sil_score: float = 0.0, stats: dict = None):
-    """flashlight's lexicon-free CTC beam search without a language model, restated from the published sources (see
-    ctc_bracketed_best_path), plus torchaudio's read-out of each hypothesis.  emissions [T][N] (any scores: the reference feeds raw
-    logits).  Returns the `nbest` best hypotheses, best first, as (tokens int64, timesteps int32, score float).
+                    beam_threshold: float = 50.0, log_add: bool = False, nbest: int = 1, sil_score: float = 0.0, stats: dict = None,
+                    lm=None, lm_weight: float = 1.0):
+    """flashlight's lexicon-free CTC beam search, without a language model or with a token n-gram (`lm`), restated from the
+    published sources (see ctc_bracketed_best_path), plus torchaudio's read-out of each hypothesis.  emissions [T][N] (any scores:
+    the reference feeds raw logits).  Returns the `nbest` best hypotheses, best first, as (tokens int64, timesteps int32, score float).
 
     State of a hypothesis = (token history, last token, last-was-blank); per frame every hypothesis is extended by every token (the
     `beam_size_token` best of the frame when given): a non-blank token that differs from the last one, or follows a blank, EXTENDS
@@ -261,14 +262,29 @@ def ctc_beam_search(emissions: np.ndarray, blank: int, sil: int, beam_size: int 
                          state (whose back-pointer survives).  inf when no such pair exists.
       revived_histories  survivors that extend into a history which existed before the frame, is held by no hypothesis of the beam
                          it is extended from, and has a descendant in that beam
-      max_merge          the largest number of candidates merged into one state"""
+      max_merge          the largest number of candidates merged into one state
+
+    `lm` (an ngram.NGramLM; only its tables W = lm_weight * score, next, Wf = lm_weight * final and start are used) adds
+    W[state(history)][n] to every candidate that EXTENDS its history: sc = ((score + em) + sil bonus) + W, in that order; blanks
+    and repeats take no term.  The state of a new history is next[state(parent)][n], the empty history holds `start`; the closing
+    silence adds Wf[state(history)].  The frame floor is the maximum over all candidates, LM term included, - beam_threshold; merge
+    rule, tie rule and read-out are unchanged (flashlight keeps its LM states in a trie over the whole history: equal token
+    sequences still merge).  With an LM `stats` also receives
+      best_not_from_slot0  the number of frames whose best candidate does not descend from the first hypothesis of the beam"""
     em = np.asarray(emissions, dtype=np.float64)
     T, N = em.shape
+    if lm is not None:
+        if lm.n_tokens != N:
+            raise ValueError(f"ctc_beam_search: the language model has {lm.n_tokens} tokens, the emissions {N}")
+        lm_w, lm_next, lm_wf, lm_start = lm.host_tables(lm_weight)
+        state_of = {0: lm_start}                   # history id -> LM state
     k_tok = N if beam_size_token is None else min(int(beam_size_token), N)
     trie = {}                                      # (history id, token) -> history id (the ZeroLM state tree)
     parent_of = {0: None}                          # history id -> parent history id
     if stats is not None:
         stats.update(min_decision_gap=float("inf"), revived_histories=0, max_merge=0)
+        if lm is not None:
+            stats["best_not_from_slot0"] = 0
 
     def gap(d):
         if stats is not None and d == d:
@@ -279,7 +295,15 @@ def ctc_beam_search(emissions: np.ndarray, blank: int, sil: int, beam_size: int 
         if key not in trie:
             trie[key] = len(trie) + 1
             parent_of[trie[key]] = hist
+            if lm is not None:
+                state_of[trie[key]] = int(lm_next[state_of[hist], tok])
         return trie[key]
+
+    def score_of(h, n):
+        sc = h[0] + em[t, n] + (sil_score if n == sil else 0.0)
+        if lm is not None and n != blank and (n != h[3] or h[4]):
+            sc = sc + lm_w[state_of[h[1]], n]
+        return sc
 
     # a hypothesis: (score, history id, parent hypothesis or None, token, last-was-blank)
     hyps = [(0.0, 0, None, sil, False)]
@@ -302,7 +326,7 @@ def ctc_beam_search(emissions: np.ndarray, blank: int, sil: int, beam_size: int 
             hs, hist, _, prev, prev_blank = h
             for n in order:
                 n = int(n)
-                sc = hs + em[t, n] + (sil_score if n == sil else 0.0)
+                sc = score_of(h, n)
                 if n != blank and (n != prev or prev_blank):
                     c = (sc, child(hist, n), h, n, False)
                 elif n == blank:
@@ -315,14 +339,16 @@ def ctc_beam_search(emissions: np.ndarray, blank: int, sil: int, beam_size: int 
         if stats is not None:                  # every candidate against the floor, those the running maximum dropped included;
             for h in hyps:                     # the maximum itself passes by construction (threshold >= 0): not a decision
                 for n in order:
-                    sc = h[0] + em[t, int(n)] + (sil_score if int(n) == sil else 0.0)
+                    sc = score_of(h, int(n))
                     if sc != best:
                         gap(sc - (best - beam_threshold))
+            if lm is not None and max(score_of(hyps[0], int(n)) for n in order) < best:
+                stats["best_not_from_slot0"] += 1
         hyps = _merge_and_prune(cands, best - beam_threshold, beam_size, log_add, stats)
         if stats is not None:
             stats["revived_histories"] += sum(1 for h in hyps if h[1] != h[2][1] and h[1] <= known and h[1] not in held
                                               and h[1] in ancestors)
-    cands = [(h[0], h[1], h, sil, False) for h in hyps]
+    cands = [(h[0] if lm is None else h[0] + lm_wf[state_of[h[1]]], h[1], h, sil, False) for h in hyps]
     best = max(c[0] for c in cands)
     floor = best - beam_threshold
     if stats is not None:

@@ -5,6 +5,7 @@ All wrappers raise (no fallback) when the tensors are not on a HIP device.
 from __future__ import annotations
 
 import ctypes
+import math
 from typing import Optional
 
 import numpy as np
@@ -973,13 +974,22 @@ BEAM_MAX_V = _C["APTAI_BEAM_MAX_V"]
 
 
 def ctc_beam_search(logits, ldl, rows_per_b, B, T, V, blank, sil, *, input_lens_i32=None, beam_size=10, beam_size_token=None,
-                    beam_threshold=50.0, log_add=False, sil_score=0.0, nbest=1, max_n=None):
+                    beam_threshold=50.0, log_add=False, sil_score=0.0, nbest=1, max_n=None, lm=None, lm_weight=1.0):
     """Lexicon-free CTC beam search on the device (aptai_ctc_beam_search, which states the semantics and the tie rule):
     (tokens int32 [B][nbest][max_n], timesteps int32 [B][nbest][max_n], n_tok int32 [B][nbest], score fp64 [B][nbest],
     n_hyp int32 [B]), best hypothesis first.  `logits` is read like ctc_greedy_decode reads it; input_lens_i32 = None decodes all T
     frames of every row; beam_size_token = None uses all V tokens; max_n defaults to T + 2, the longest a hypothesis can be.
-    Nothing here synchronises host and device."""
+    lm = an ngram.NGramLM over the V tokens fuses it into the search with weight lm_weight (aptai_ctc_beam_search_lm; the tables
+    are multiplied by the weight once on the host and cached on the model).  Nothing here synchronises host and device."""
     _dev(logits, input_lens_i32)
+    if lm is not None:
+        from .ngram import NGramLM
+        if not isinstance(lm, NGramLM):
+            raise ValueError(f"ctc_beam_search: lm must be an ngram.NGramLM or None, not {type(lm).__name__}")
+        if lm.n_tokens != V:
+            raise ValueError(f"ctc_beam_search: the language model has {lm.n_tokens} tokens, the logits V = {V}")
+        if not math.isfinite(lm_weight):
+            raise ValueError(f"ctc_beam_search: lm_weight must be finite, not {lm_weight}")
     max_n = T + 2 if max_n is None else int(max_n)
     k_tok = 0 if beam_size_token is None else int(beam_size_token)
     if not 1 <= beam_size <= BEAM_MAX:
@@ -1006,9 +1016,14 @@ def ctc_beam_search(logits, ldl, rows_per_b, B, T, V, blank, sil, *, input_lens_
     n_tok = torch.empty((B, nbest), device=dev, dtype=torch.int32)
     score = torch.empty((B, nbest), device=dev, dtype=torch.float64)
     n_hyp = torch.empty(B, device=dev, dtype=torch.int32)
-    _lib.call("aptai_ctc_beam_search", logits.data_ptr(), ldl, rows_per_b, _ptr(input_lens_i32), B, T, V, blank, sil, beam_size, k_tok,
-              float(beam_threshold), int(bool(log_add)), float(sil_score), nbest, max_n, ws.data_ptr(), tokens.data_ptr(),
-              timesteps.data_ptr(), n_tok.data_ptr(), score.data_ptr(), n_hyp.data_ptr(), _stream())
+    args = (logits.data_ptr(), ldl, rows_per_b, _ptr(input_lens_i32), B, T, V, blank, sil, beam_size, k_tok, float(beam_threshold),
+            int(bool(log_add)), float(sil_score), nbest, max_n, ws.data_ptr(), tokens.data_ptr(), timesteps.data_ptr(),
+            n_tok.data_ptr(), score.data_ptr(), n_hyp.data_ptr())
+    if lm is None:
+        _lib.call("aptai_ctc_beam_search", *args, _stream())
+    else:
+        w, nxt, wf, n_states, start = lm.device_tables(lm_weight, dev)
+        _lib.call("aptai_ctc_beam_search_lm", *args, w.data_ptr(), nxt.data_ptr(), wf.data_ptr(), n_states, start, _stream())
     return tokens, timesteps, n_tok, score, n_hyp
 
 

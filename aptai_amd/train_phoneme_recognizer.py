@@ -6,7 +6,9 @@ batches per epoch (:406,413), LambdaLR schedule, PER metric, and the three check
 Decoding for the PER is the best path by default.  The torchaudio package behind the beam decoder of utility.py:448-471 is absent,
 so parity with torchaudio itself stays unpinned; `--decoder beam` (cfg.decoder, with cfg.beam_size / cfg.beam_log_add) runs that
 decoder's published algorithm on the device instead (aptai_ctc_beam_search, pinned against hostlogic.ctc_beam_search), and
-`--decoder flashlight` its closed form for the reference's settings.
+`--decoder flashlight` its closed form for the reference's settings.  With `--decoder beam`, `--lm_arpa PATH` or `--lm_order N`
+(a phoneme n-gram estimated from the training set's labels before the first epoch) and `--lm_weight W` fuse a token language
+model into that search (ngram.NGramLM, aptai_ctc_beam_search_lm): what the reference's decoder call leaves at lm=None.
 The CommonPhone reader, wandb and resume-from-hub are out of scope; `SyntheticCommonPhone` yields items
 with the fields `_collator` consumes.  The shipped script's stale imports / constructor arity are not
 reproduced: the model is `aptai_amd.w2v2_pr.Wav2Vec2_PR(pretrain_cfg, cache_dir, huggingface_model_id, vocab)`.
@@ -216,7 +218,21 @@ def default_cfg(**kw):
                              num_hidden_layers=None, freeze_feature_extractor=False, save_all_epochs=False, cache_dir=None)
 
 
-def main(argv=None):
+def language_model(args, vocab, train_dataset):
+    """The n-gram of --lm_arpa / --lm_order (ngram.NGramLM) over the vocabulary in id order, or None: read from an ARPA file, or
+    estimated once, on the host, from the `phoneme_label` of every training item (interpolated Witten-Bell)."""
+    from .ngram import NGramLM
+    tokens = sorted(vocab, key=vocab.get)
+    blank = int(vocab.get("(blank)", 0))
+    if args.lm_arpa is not None:
+        return NGramLM.from_arpa(args.lm_arpa, tokens, blank=blank)
+    if args.lm_order is not None:
+        return NGramLM.estimate((train_dataset[i]["phoneme_label"] for i in range(len(train_dataset))), tokens, order=args.lm_order,
+                                blank=blank)
+    return None
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--model_dir", default=None, help="local wav2vec2 checkpoint directory (config.json + weights)")
     ap.add_argument("--random_init", default="base", choices=["base", "large"])
@@ -235,8 +251,24 @@ def main(argv=None):
     ap.add_argument("--beam_size", type=int, default=None, help="with --decoder beam: hypotheses kept per frame, 1..32 (default 10)")
     ap.add_argument("--beam_log_add", action="store_true", default=None,
                     help="with --decoder beam: sum the scores of hypotheses with equal history (true prefix scores) instead of the maximum")
+    ap.add_argument("--lm_arpa", default=None, metavar="PATH",
+                    help="with --decoder beam: fuse the token n-gram of this ARPA file into the search (words = the vocabulary's tokens)")
+    ap.add_argument("--lm_order", type=int, default=None, metavar="N",
+                    help="with --decoder beam: estimate an N-gram (1..5) from the training set's phoneme labels before the first epoch")
+    ap.add_argument("--lm_weight", type=float, default=None, metavar="W", help="with an LM: its weight in the search (default 1.0)")
     ap.add_argument("--out", default="pr_exp")
     a = ap.parse_args(argv)
+    if (a.lm_arpa is not None or a.lm_order is not None or a.lm_weight is not None) and a.decoder != "beam":
+        ap.error("--lm_arpa / --lm_order / --lm_weight need --decoder beam")
+    if a.lm_arpa is not None and a.lm_order is not None:
+        ap.error("--lm_arpa and --lm_order exclude each other")
+    if a.lm_weight is not None and a.lm_arpa is None and a.lm_order is None:
+        ap.error("--lm_weight needs --lm_arpa or --lm_order")
+    return a
+
+
+def main(argv=None):
+    a = parse_args(argv)
     vocab = default_vocab()
     w2v = W2V2Config.base() if a.random_init == "base" else W2V2Config.large()
     loops.apply_mask_feature_arguments(w2v, a)
@@ -256,6 +288,9 @@ def main(argv=None):
                                      batch_size=a.batch_size, shuffle=True, drop_last=True, collate_fn=collate)
     va = torch.utils.data.DataLoader(SyntheticCommonPhone(a.val_items, a.seconds, len(vocab), seed=2, source_rate=a.source_rate),
                                      batch_size=1, collate_fn=collate)
+    lm = language_model(a, vocab, tr.dataset)
+    if lm is not None:          # validate() / test() decode with it: Wav2Vec2_PR.beam_options reaches ops.ctc_beam_search
+        model.beam_options = dict(model.beam_options, lm=lm, lm_weight=1.0 if a.lm_weight is None else a.lm_weight)
     out = Path(a.out)
     return train(cfg, model, optimizer, lr_scheduler, vocab, tr, va, out / "best-model-ckpt", out / "last-model-ckpt", out / "model-ckpts")
 

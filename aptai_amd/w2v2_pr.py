@@ -161,7 +161,9 @@ class Wav2Vec2_PR(nn.Module):
 
     decoder = "best_path"           # or "flashlight": framed like the reference's torchaudio decoder call; or "beam": the search
     #                                 itself on the device (module docstring)
-    # keywords of ops.ctc_beam_search for decoder = "beam"; the defaults are the reference's decoder call (models/w2v2_pr.py:144-153)
+    # keywords of ops.ctc_beam_search for decoder = "beam"; the defaults are the reference's decoder call (models/w2v2_pr.py:144-153).
+    # An instance's own dict may add "lm" (an ngram.NGramLM over the vocabulary) and "lm_weight": the token n-gram the reference
+    # leaves at lm=None, fused into the search on the device; every decode of the model then uses it.
     beam_options = {"beam_size": 10, "beam_threshold": 50.0, "log_add": False, "nbest": 1}
 
     def _sil(self):
@@ -245,7 +247,8 @@ class Wav2Vec2_PR(nn.Module):
 
     def decode_nbest(self, audio_inputs, audio_lengths, **options):
         """n-best lists of the batch from the device beam search, whatever `decoder` is set to: `beam_options` overridden by
-        `options` (beam_size, beam_size_token, beam_threshold, log_add, sil_score, nbest, max_n: ops.ctc_beam_search).  Runs in eval
+        `options` (beam_size, beam_size_token, beam_threshold, log_add, sil_score, nbest, max_n, lm, lm_weight:
+        ops.ctc_beam_search).  Runs in eval
         mode without gradients.  Returns DEVICE tensors and never synchronises:
           tokens, timesteps int32 [B][nbest][max_n]  zero-padded; a timestep is the position in the framed token row (frame t -> t + 1)
           n_tok             int32 [B][nbest]         length of each hypothesis (0: the row has fewer hypotheses)

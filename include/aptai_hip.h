@@ -546,6 +546,28 @@ int aptai_ctc_beam_search(const float* logits, int64_t ldl, int64_t rows_per_b, 
                           int32_t* n_tok, double* score, int32_t* n_hyp, void* stream);
 /* 0 for arguments outside the limits above */
 int64_t aptai_ctc_beam_search_workspace_bytes(int64_t B, int64_t T, int64_t beam_size, int64_t nbest);
+/* The same search with a token-level n-gram language model fused in (flashlight's lm= / lm_weight= of the LexiconFreeDecoder; the
+ * reference passes lm=None, torchaudio and KenLM are not available to this project: parity with them is unpinned).  Arguments,
+ * workspace (aptai_ctc_beam_search_workspace_bytes), outputs, tie rule and determinism are those of aptai_ctc_beam_search; the
+ * oracle is the same hostlogic.ctc_beam_search with lm=.  The model arrives as a dense automaton over lm_states contexts
+ * (aptai_amd/ngram.py NGramLM.device_tables), ALREADY MULTIPLIED by the LM weight on the host, no multiply happens on the device:
+ *   lm_w      fp64  [lm_states][V]  weight * ln P(n | state)          lm_next  int32 [lm_states][V]  state after token n
+ *   lm_wfinal fp64  [lm_states]     weight * ln P(</s> | state)       lm_start the state of the empty history
+ * A candidate that EXTENDS its history (a non-blank n that differs from the last token or follows a blank) scores
+ * sc = ((score + (double)x[t][n]) + (n == sil ? sil_score : 0)) + lm_w[state(history)][n], fp64 adds in that order; blanks and
+ * repeats take no term.  The new history's state is lm_next[state(parent history)][n]; a history has one state for the whole
+ * utterance, so "equal token sequences merge" is unchanged.  The frame floor is (maximum over ALL candidates, LM term included)
+ * - beam_threshold.  The closing silence adds lm_wfinal[state(history)] before its floor, whose maximum is over all hypotheses.
+ * T_b == 0 gives [sil] at timestep 0 with score 0 + lm_wfinal[lm_start].  The silence token is an ordinary LM word; the blank
+ * column of the tables is never read.  An all-zero model gives the bits of aptai_ctc_beam_search.
+ * Refused with a message, launching nothing: null tables, lm_states < 1, lm_start outside [0, lm_states), lm_states * V > 2^24.
+ * NOT checked on the device: entries of lm_next outside [0, lm_states) and non-finite scores (NGramLM checks both when it builds
+ * its tables). */
+int aptai_ctc_beam_search_lm(const float* logits, int64_t ldl, int64_t rows_per_b, const int32_t* input_lens, int64_t B, int64_t T,
+                             int64_t V, int blank, int sil, int beam_size, int beam_size_token, double beam_threshold, int log_add,
+                             double sil_score, int nbest, int64_t max_n, void* workspace, int32_t* tokens, int32_t* timesteps,
+                             int32_t* n_tok, double* score, int32_t* n_hyp, const double* lm_w, const int32_t* lm_next,
+                             const double* lm_wfinal, int64_t lm_states, int lm_start, void* stream);
 
 /* ------------------------------------------------------------------------------------------------ Force_APTAI heads (fp32)
  * Small layers behind the frozen encoder of models/force_aptai.py:108-161.  fp32 because they feed an argmax whose

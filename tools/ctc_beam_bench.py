@@ -7,8 +7,11 @@ point on preallocated buffers, warmed up, the entry points alternating round by 
   aptai_ctc_beam_search, beam 10   the reference's settings (threshold 50, max-merge, 1-best)
   aptai_ctc_beam_search, beam 32   the widest beam, log-add, 32-best
   aptai_ctc_greedy_decode          frame argmax, for scale
+  aptai_ctc_beam_search_lm         with --lm ORDER (repeatable): both beams again with a random back-off n-gram of that order
+                                   over the 46 tokens fused in (weight 0.8), figures beam10_lmN / beam32_lmN
 The decode runs once per evaluation utterance, not in the train step: the figures say what `decoder = "beam"` costs validate().
 One line per figure and a JSON summary line."""
+import argparse
 import json
 import os
 import sys
@@ -29,7 +32,28 @@ def _time(fn, iters):
     return e0.elapsed_time(e1) * 1e3 / iters
 
 
-def main(B=16, T=499, V=46, ldl=64, rounds=7, iters=20):
+def random_lm(order, V, seed=0, keep=(1.0, 0.5, 0.2, 0.1, 0.05)):
+    """A random back-off model read from generated ARPA text: every unigram, a `keep` share of the longer n-grams of listed
+    contexts, back-off weights on three contexts in four; token 0 is the blank, 1 the silence."""
+    import numpy as np
+    from aptai_amd.ngram import NGramLM
+    rs = np.random.RandomState(seed + order)
+    names = ["(blank)", "(...)"] + [f"p{i}" for i in range(2, V)]
+    level = [("<s>",)] + [(w,) for w in names[1:]] + [("</s>",)]
+    text = ["\\data\\"]
+    for k in range(order):
+        text += ["", f"\\{k + 1}-grams:"]
+        for g in level:
+            row = f"{-99.0 if g[-1] == '<s>' else -(0.1 + 2.9 * rs.rand()):.6f}\t" + " ".join(g)
+            if k + 1 < order and g[-1] != "</s>" and rs.rand() < 0.75:
+                row += f"\t{-1.5 * rs.rand():.6f}"
+            text.append(row)
+        if k + 1 < order:
+            level = [g + (w,) for g in level if g[-1] != "</s>" for w in names[1:] + ["</s>"] if rs.rand() < keep[k + 1]]
+    return NGramLM.from_arpa("\n".join(text + ["", "\\end\\", ""]), names)
+
+
+def main(B=16, T=499, V=46, ldl=64, rounds=7, iters=20, lm_orders=()):
     dev = "cuda"
     g = torch.Generator().manual_seed(1)
     logits = torch.zeros(B * T, ldl)
@@ -51,6 +75,17 @@ def main(B=16, T=499, V=46, ldl=64, rounds=7, iters=20):
             _lib.call("aptai_ctc_beam_search", logits.data_ptr(), ldl, T, None, B, T, V, 0, 1, beam, 0, 50.0, log_add, 0.0, nbest, max_n,
                       o[0].data_ptr(), o[1].data_ptr(), o[2].data_ptr(), o[3].data_ptr(), o[4].data_ptr(), o[5].data_ptr(), stream)
         fns[name] = beam_search
+        for order in lm_orders:
+            w, nxt, wf, n_states, start = random_lm(order, V).device_tables(0.8, dev)
+            o = tuple(torch.empty_like(x) for x in outs[name])
+            outs[f"{name}_lm{order}"] = o + (w, nxt, wf)            # the tables stay alive with the buffers
+
+            def beam_search_lm(beam=beam, log_add=log_add, nbest=nbest, o=o, w=w, nxt=nxt, wf=wf, n_states=n_states, start=start):
+                _lib.call("aptai_ctc_beam_search_lm", logits.data_ptr(), ldl, T, None, B, T, V, 0, 1, beam, 0, 50.0, log_add, 0.0, nbest,
+                          max_n, o[0].data_ptr(), o[1].data_ptr(), o[2].data_ptr(), o[3].data_ptr(), o[4].data_ptr(), o[5].data_ptr(),
+                          w.data_ptr(), nxt.data_ptr(), wf.data_ptr(), n_states, start, stream)
+            fns[f"{name}_lm{order}"] = beam_search_lm
+            print(f"{name}_lm{order}: {n_states} states, tables {(w.numel() * 12 + wf.numel() * 8) / 1024:.0f} KiB")
     ids = torch.empty((B, max_n), device=dev, dtype=torch.int32)
     n = torch.empty(B, device=dev, dtype=torch.int32)
     fns["greedy"] = lambda: _lib.call("aptai_ctc_greedy_decode", logits.data_ptr(), ldl, T, B, T, V, 0, ids.data_ptr(), max_n, n.data_ptr(),
@@ -59,7 +94,9 @@ def main(B=16, T=499, V=46, ldl=64, rounds=7, iters=20):
         for _ in range(3):
             fn()
     torch.cuda.synchronize()
-    assert all(torch.isfinite(outs[k][4]).all() and (outs[k][5] >= 1).all() for k in outs)
+    # every row has a best hypothesis; with an LM the floor may leave fewer than nbest of them (their ranks score -inf)
+    assert all(torch.isfinite(outs[k][4][:, 0]).all() and (outs[k][5] >= 1).all() for k in outs)
+    assert all(torch.isfinite(outs[k][4]).all() for k in outs if "_lm" not in k)
     t = {k: [] for k in fns}
     for _ in range(rounds):
         for k, fn in fns.items():
@@ -73,4 +110,7 @@ def main(B=16, T=499, V=46, ldl=64, rounds=7, iters=20):
 
 
 if __name__ == "__main__":
-    main()
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--lm", type=int, action="append", default=[], metavar="ORDER",
+                    help="also time aptai_ctc_beam_search_lm with a random n-gram of this order, 1..5 (repeatable)")
+    main(lm_orders=tuple(ap.parse_args().lm))
