@@ -285,18 +285,27 @@ __global__ __launch_bounds__(256) void ctc_grad_kernel(CtcArgs a, const float* _
 }
 
 // ---- best-path (greedy) CTC decode on the device: frame argmax (first maximum, like torch.argmax) -> collapse repeats -> drop
-// blank, over ALL T frames of every row of the padded batch (the reference's decoder call passes no lengths,
-// models/w2v2_pr.py:155).  One wave per utterance, 64 frames per round: ballot + prefix popcount compacts the kept labels.
-// ids_out int32 [B][max_n] zero-padded; n_out int32 [B] = decoded length (may exceed max_n: the caller checks).
-__global__ __launch_bounds__(64) void ctc_greedy_decode_kernel(const float* __restrict__ logits, long ldl, long rows_per_b, int T, int V,
-                                                               int blank, int* __restrict__ ids_out, int max_n, int* __restrict__ n_out) {
+// blank, over the first T_b = clamp(input_lens[b], 0, T) frames of row b (null: all T); frames at or past T_b are not read.
+// sil >= 0 frames the row: the opening silence stands where the label before frame 0 would (`carry`), the closing one follows the
+// last round, a frame t is reported as timestep t + 1.  Contract and oracle: include/aptai_hip.h.  One wave per utterance, 64
+// frames per round: ballot + prefix popcount compacts the kept labels; every output element is written once, by one lane.
+__global__ __launch_bounds__(64) void ctc_greedy_decode_kernel(const float* __restrict__ logits, long ldl, long rows_per_b,
+                                                               const int* __restrict__ input_lens, int T, int V, int blank, int sil,
+                                                               int* __restrict__ ids_out, int* __restrict__ ts_out, int max_n,
+                                                               int* __restrict__ n_out) {
     const int b = blockIdx.x, lane = threadIdx.x;
-    int count = 0, carry = -1;                                   // label of the last frame of the previous round
-    for (int l = lane; l < max_n; l += 64) ids_out[(long)b * max_n + l] = 0;
-    for (int t0 = 0; t0 < T; t0 += 64) {
+    const int Tb = input_lens ? min(max(input_lens[b], 0), T) : T;
+    const int framed = sil >= 0 ? 1 : 0;
+    auto put = [&](int pos, int id, int ts) {
+        if (pos < max_n) ids_out[(long)b * max_n + pos] = id;
+        if (pos < max_n && ts_out) ts_out[(long)b * max_n + pos] = ts;
+    };
+    int count = framed, carry = framed ? sil : -1;               // label of the last frame of the previous round
+    if (framed && lane == 0) put(0, sil, 0);
+    for (int t0 = 0; t0 < Tb; t0 += 64) {
         const int t = t0 + lane;
         int arg = -1;
-        if (t < T) {
+        if (t < Tb) {
             const float* row = logits + ((long)b * rows_per_b + t) * ldl;
             float best = row[0];
             arg = 0;
@@ -307,13 +316,17 @@ __global__ __launch_bounds__(64) void ctc_greedy_decode_kernel(const float* __re
         }
         int prev = __shfl_up(arg, 1, 64);
         if (lane == 0) prev = carry;
-        const bool keep = t < T && arg != prev && arg != blank;
+        const bool keep = t < Tb && arg != prev && arg != blank;
         const unsigned long long m = __ballot(keep);
-        const int pos = count + __popcll(m & ((1ull << lane) - 1ull));
-        if (keep && pos < max_n) ids_out[(long)b * max_n + pos] = arg;
+        if (keep) put(count + __popcll(m & ((1ull << lane) - 1ull)), arg, t + framed);
         count += __popcll(m);
-        carry = __shfl(arg, 63, 64);
+        carry = __shfl(arg, min(63, Tb - 1 - t0), 64);           // the row's last own frame, in its last round
     }
+    if (framed && carry != sil) {                                // wave-uniform
+        if (lane == 0) put(count, sil, Tb + 1);
+        ++count;
+    }
+    for (int l = count + lane; l < max_n; l += 64) put(l, 0, 0);
     if (lane == 0) n_out[b] = count;
 }
 
@@ -400,12 +413,15 @@ extern "C" int aptai_ctc_bwd(const float* logits, int64_t ldl, int64_t rows_per_
     return APTAI_OK;
 }
 
-extern "C" int aptai_ctc_greedy_decode(const float* logits, int64_t ldl, int64_t rows_per_b, int64_t B, int64_t T, int64_t V, int blank,
-                                       int32_t* ids_out, int64_t max_n, int32_t* n_out, void* stream) {
+extern "C" int aptai_ctc_greedy_decode(const float* logits, int64_t ldl, int64_t rows_per_b, const int32_t* input_lens, int64_t B,
+                                       int64_t T, int64_t V, int blank, int sil, int32_t* ids_out, int32_t* timesteps_out,
+                                       int64_t max_n, int32_t* n_out, void* stream) {
     APTAI_REQUIRE(logits && ids_out && n_out && B > 0 && T > 0 && V > 0 && ldl >= V && rows_per_b >= T && max_n > 0,
                   "aptai_ctc_greedy_decode: bad arguments");
-    APTAI_LAUNCH(ctc_greedy_decode_kernel, dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream, logits, (long)ldl, (long)rows_per_b, (int)T,
-                 (int)V, blank, ids_out, (int)max_n, n_out);
+    APTAI_REQUIRE(sil < 0 || (sil < V && sil != blank), "aptai_ctc_greedy_decode: sil (%d) must be below V = %ld and differ from blank (%d)", sil,
+                  (long)V, blank);
+    APTAI_LAUNCH(ctc_greedy_decode_kernel, dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream, logits, (long)ldl, (long)rows_per_b,
+                 input_lens, (int)T, (int)V, blank, sil, ids_out, timesteps_out, (int)max_n, n_out);
     APTAI_CHECK_LAUNCH("ctc_greedy_decode_kernel");
     return APTAI_OK;
 }

@@ -278,7 +278,8 @@ class Force_APTAI(nn.Module):
             if phn_pred_list is None and labels is not None:
                 ids, nlen, nlen_full = self._label_slots(labels, dev)
             elif phn_pred_list is None:
-                ids, nlen = pr._decode_device(out, self.max_phn_seq_len)      # int32 [B][slots] zero-padded, int32 [B]
+                ids, nlen_full = pr._decode_device(out, self.max_phn_seq_len)  # int32 [B][slots] zero-padded, int32 [B] full length
+                nlen = nlen_full.clamp(max=self.max_phn_seq_len - 1)           # as _label_slots: the kernels never leave a row
             else:
                 padded = []
                 for lst in phn_pred_list:
@@ -326,7 +327,7 @@ class Force_APTAI(nn.Module):
                 o = ge.out
                 # the graph's outputs are overwritten by the next replay: hand out copies (13 MB, 4 us)
                 enc = SimpleNamespace(g=o.g, ac=o.ac.clone(), ids=o.ids.clone(), nlen=o.nlen.clone(), frame_lens=o.frame_lens.clone(),
-                                      step=self.w2v2_pr.wav2vec2._step)
+                                      nlen_full=o.nlen_full.clone(), step=self.w2v2_pr.wav2vec2._step)
             else:
                 enc = self._encode(audio_inputs, audio_lengths)
                 self._enc_seen[key] = self._enc_seen.get(key, 0) + 1
@@ -364,7 +365,7 @@ class Force_APTAI(nn.Module):
         enc = pf[2]
         cur = torch.cuda.current_stream(audio_inputs.device)
         cur.wait_event(enc.event)
-        for t in (enc.ac, enc.ids, enc.nlen, enc.frame_lens):         # allocated on the side stream, consumed on this one
+        for t in (enc.ac, enc.ids, enc.nlen, enc.nlen_full, enc.frame_lens):      # allocated on the side stream, consumed on this one
             t.record_stream(cur)
         return enc
 

@@ -662,6 +662,7 @@ class GraphedForceStep(_CapturingRunner):
         # ---- heads graph: its own copies of the encoder outputs (the next encoder replay overwrites enc.*)
         e = self.enc
         self.h_ac, self.h_ids, self.h_nlen, self.h_fl = (torch.empty_like(t) for t in (e.ac, e.ids, e.nlen, e.frame_lens))
+        self.h_nfull = torch.empty_like(e.nlen_full)          # the uncut decoded length: what lists() checks
         self.st, self.P = model._heads_state(g, self.h_ids, self.h_nlen, self.h_fl, self.tv_tgt, 0xF0)
         self.st.readout = "argmax"
         self.g_heads = torch.cuda.CUDAGraph()
@@ -708,6 +709,7 @@ class GraphedForceStep(_CapturingRunner):
         e = self.enc
         self.h_ac.copy_(e.ac, non_blocking=True); self.h_ids.copy_(e.ids, non_blocking=True)
         self.h_nlen.copy_(e.nlen, non_blocking=True); self.h_fl.copy_(e.frame_lens, non_blocking=True)
+        self.h_nfull.copy_(e.nlen_full, non_blocking=True)
         self._launch_encoder(next_batch if next_batch is not None else batch)      # waits for the four copies above
         self._next_salt()
         self.g_heads.replay()
@@ -717,7 +719,7 @@ class GraphedForceStep(_CapturingRunner):
         self.opt.step()
         loss, tv_loss, align_loss, tvs, frame_phns = self.outs[:5]
         return {"loss": loss, "tv_loss": tv_loss, "align_loss": align_loss, "tvs_pred": tvs, "frame_phns": frame_phns,
-                "ids": self.h_ids, "n_ids": self.h_nlen, "frame_lens": self.h_fl}
+                "ids": self.h_ids, "n_ids": self.h_nfull, "frame_lens": self.h_fl}
 
     def lists(self, out) -> Dict[str, list]:
         """The Python lists of Force_APTAI.forward (pred_frame_phns, pred_ctc_phn_seq) for a step() result: the only transfers."""

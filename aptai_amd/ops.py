@@ -960,13 +960,20 @@ def ctc_bwd(logits, ldl, rows_per_b, targets_i32, input_lens_i32, target_lens_i3
     return d
 
 
-def ctc_greedy_decode(logits, ldl, rows_per_b, B, T, V, blank, max_n):
-    """Device best-path decode: (ids int32 [B][max_n] zero-padded, n int32 [B]) - see aptai_ctc_greedy_decode."""
-    _dev(logits)
+def ctc_greedy_decode(logits, ldl, rows_per_b, B, T, V, blank, max_n, *, input_lens_i32=None, sil=None, want_timesteps=False):
+    """Device best-path decode: (ids int32 [B][max_n] zero-padded, n int32 [B] = full length), with want_timesteps
+    (ids, timesteps int32 [B][max_n], n) - see aptai_ctc_greedy_decode.  input_lens_i32 = None decodes all T frames of every row;
+    sil = a token id frames every row with it like the beam search does."""
+    _dev(logits, input_lens_i32)
+    if input_lens_i32 is not None and (input_lens_i32.dtype != torch.int32 or input_lens_i32.numel() != B
+                                       or not input_lens_i32.is_contiguous()):
+        raise ValueError(f"ctc_greedy_decode: input_lens_i32 must be a contiguous int32 vector of {B} entries")
     ids = torch.empty((B, max_n), device=logits.device, dtype=torch.int32)
+    ts = torch.empty((B, max_n), device=logits.device, dtype=torch.int32) if want_timesteps else None
     n = torch.empty(B, device=logits.device, dtype=torch.int32)
-    _lib.call("aptai_ctc_greedy_decode", logits.data_ptr(), ldl, rows_per_b, B, T, V, blank, ids.data_ptr(), max_n, n.data_ptr(), _stream())
-    return ids, n
+    _lib.call("aptai_ctc_greedy_decode", logits.data_ptr(), ldl, rows_per_b, _ptr(input_lens_i32), B, T, V, blank,
+              -1 if sil is None else int(sil), ids.data_ptr(), _ptr(ts), max_n, n.data_ptr(), _stream())
+    return (ids, ts, n) if want_timesteps else (ids, n)
 
 
 BEAM_MAX = _C["APTAI_BEAM_MAX"]

@@ -3,19 +3,20 @@
 Same constructor ``(pretrain_cfg, cache_dir, huggingface_model_id, vocab)``, ``forward(input_values, input_lengths,
 phoneme_labels)`` dict, inference helpers and state-dict keys (``wav2vec2.*``, ``pr_head.*``).  The torchaudio package whose
 flashlight beam-search decoder the reference calls (models/w2v2_pr.py:143-159) is not in the image, so parity with torchaudio
-itself stays *unpinned* (SURVEY.md §8c); the default decoding is the best path (frame argmax on the device, collapse + blank
-removal on the host).
+itself stays *unpinned* (SURVEY.md §8c).  Every decoder answers through one read-out (``_read_out``: tokens, timesteps and full
+lengths per row, on the device, each row stopping at its own last frame under ``batch_invariant``); the default
+``model.decoder = "best_path"`` is the frame argmax, repeats collapsed, blanks dropped (aptai_ctc_greedy_decode, csrc/ctc.hip).
+
+``model.decoder = "flashlight"`` (opt-in) is the same kernel given the silence token ``'(...)'``: what the published decoder
+sources say that call returns for the reference's settings, the best path FRAMED by the decoder's opening / closing silence,
+timesteps as positions in the framed token row (oracle: hostlogic.ctc_bracketed_best_path; hostlogic.ctc_beam_search restates the
+search itself and the CPU tests check the two against each other).  It is not the default because nothing in this image can pin
+it and the reference-generated fixtures under tests/golden were made with a plain best-path stand-in.
 
 ``model.decoder = "beam"`` (opt-in) runs the published algorithm of that decoder on the device (aptai_ctc_beam_search,
 csrc/decode.hip), pinned against its Python restatement hostlogic.ctc_beam_search: ``beam_options`` default to the reference's
 call (beam 10, threshold 50, max-merge, 1-best) and also give what no closed form can: true prefix scores (``log_add``), token
 beams, and through ``decode_nbest`` / ``predict_nbest`` n-best lists with per-token timesteps.
-
-``model.decoder = "flashlight"`` (opt-in) returns what the published decoder sources say that call returns for the
-reference's settings: the same best path FRAMED by the decoder's opening / closing silence token ``'(...)'``, timesteps as
-positions in the framed token row (hostlogic.ctc_bracketed_best_path; hostlogic.ctc_beam_search restates the search itself
-and the CPU tests check the two against each other).  It is not the default because nothing in this image can pin it and
-the reference-generated fixtures under tests/golden were made with a plain best-path stand-in.
 """
 from __future__ import annotations
 
@@ -83,7 +84,7 @@ class Wav2Vec2_PR(nn.Module):
     """Wav2Vec2 model used as a phoneme recognizer."""
 
     # opt-in: eval-mode calls (forward in eval mode, force_align, get_embeddings, get_ctc_logits, ...) return for every row what the
-    # utterance gets at batch size 1 - Wav2Vec2Model.batch_invariant for the encoder, and the best-path decode stops at each row's
+    # utterance gets at batch size 1 - Wav2Vec2Model.batch_invariant for the encoder, and every decoder stops at each row's
     # own last frame.  Training-mode forwards are what they were.
     batch_invariant = False
 
@@ -122,8 +123,9 @@ class Wav2Vec2_PR(nn.Module):
                 'hidden_states': hd.view(g.B, g.Tp, -1)[:, :g.T]}
 
     # ------------------------------------------------------------------ inference helpers
-    def _logits_eval(self, audio_inputs, lengths_2d):
-        """eval-mode encoder + pr_head (fp32 logits (B,T,V)); shared by every helper below."""
+    def _logits_eval(self, audio_inputs, audio_lengths):
+        """eval-mode encoder + pr_head (fp32 logits (B,T,V)); shared by every helper below.  Lengths as (B,) or (B, 1)."""
+        lengths_2d = audio_lengths[:, None] if audio_lengths.dim() == 1 else audio_lengths
         with batch_invariant_scope(self.wav2vec2, self.batch_invariant and not self.training):
             out = self.wav2vec2(audio_inputs, attention_mask=lengths_2d, return_dict=True, output_hidden_states=True)
         g, h = out._geom, out._flat_last
@@ -159,87 +161,70 @@ class Wav2Vec2_PR(nn.Module):
     def _blank(self) -> int:
         return int(self.vocab.get('(blank)', 0)) if isinstance(self.vocab, dict) else 0
 
-    decoder = "best_path"           # or "flashlight": framed like the reference's torchaudio decoder call; or "beam": the search
-    #                                 itself on the device (module docstring)
+    decoder = "best_path"           # or "flashlight" (framed like the reference's decoder call) or "beam": module docstring
     # keywords of ops.ctc_beam_search for decoder = "beam"; the defaults are the reference's decoder call (models/w2v2_pr.py:144-153).
     # An instance's own dict may add "lm" (an ngram.NGramLM over the vocabulary) and "lm_weight": the token n-gram the reference
     # leaves at lm=None, fused into the search on the device; every decode of the model then uses it.
     beam_options = {"beam_size": 10, "beam_threshold": 50.0, "log_add": False, "nbest": 1}
 
-    def _sil(self):
-        if self.decoder == "best_path":
-            return None
-        if self.decoder not in ("flashlight", "beam"):
-            raise ValueError(f"Wav2Vec2_PR.decoder must be 'best_path', 'flashlight' or 'beam', not {self.decoder!r}")
+    def _sil(self) -> int:
         if not (isinstance(self.vocab, dict) and '(...)' in self.vocab):
-            raise ValueError(f"decoder = {self.decoder!r} needs the silence token '(...)' in the vocabulary (models/w2v2_pr.py:153)")
+            raise ValueError("'flashlight', 'beam' and the n-best lists need the silence token '(...)' in the vocabulary (models/w2v2_pr.py:153)")
         return int(self.vocab['(...)'])
 
     def _beam_search(self, out, **options):
         """ops.ctc_beam_search over the logits of `out`, `beam_options` overridden by `options`: the five device tensors.  All
         frames of the padded batch are decoded, like the reference's decoder call; with batch_invariant each row stops at its own
         frame count (`input_lens`), which is what the utterance gets alone.  Nothing here synchronises host and device."""
-        if not (isinstance(self.vocab, dict) and '(...)' in self.vocab):
-            raise ValueError("the beam search needs the silence token '(...)' in the vocabulary (models/w2v2_pr.py:153)")
         g, full = out._geom, out._logits_full
         opts = dict(self.beam_options)
         opts.update(options)
-        own = getattr(g, "fir_lens", None)
-        lens = None if own is None else own.to(torch.int32).contiguous()
-        return ops.ctc_beam_search(full, full.shape[1], g.Tp, g.B, g.T, self.pr_head.weight.shape[0], self._blank(),
-                                   int(self.vocab['(...)']), input_lens_i32=lens, **opts)
+        return ops.ctc_beam_search(full, full.shape[1], g.Tp, g.B, g.T, self.pr_head.weight.shape[0], self._blank(), self._sil(),
+                                   input_lens_i32=getattr(g, "fir_lens", None), **opts)
+
+    def _read_out(self, out, max_n: int):
+        """The decode of `decoder`, on the device: (tokens, timesteps int32 [B][max_n] zero-padded, n int32 [B] = full length, which
+        may exceed max_n).  "best_path" / "flashlight": aptai_ctc_greedy_decode without / with the silence token (oracle:
+        hostlogic.ctc_bracketed_best_path); "beam": the top hypothesis of `_beam_search`, whose rows and row lengths all three read."""
+        if self.decoder == "beam":
+            tokens, timesteps, n_tok, _, _ = self._beam_search(out, max_n=max_n)
+            return tokens[:, 0].contiguous(), timesteps[:, 0].contiguous(), n_tok[:, 0].contiguous()
+        if self.decoder not in ("best_path", "flashlight"):
+            raise ValueError(f"Wav2Vec2_PR.decoder must be 'best_path', 'flashlight' or 'beam', not {self.decoder!r}")
+        g, full = out._geom, out._logits_full
+        return ops.ctc_greedy_decode(full, full.shape[1], g.Tp, g.B, g.T, self.pr_head.weight.shape[0], self._blank(), max_n,
+                                     input_lens_i32=getattr(g, "fir_lens", None), want_timesteps=True,
+                                     sil=self._sil() if self.decoder == "flashlight" else None)
 
     def _decode_device(self, out, max_n: int):
-        """Best-path decode on the device (aptai_ctc_greedy_decode): (ids int32 [B][max_n] zero-padded, n int32 [B]) over ALL
-        frames of the padded batch, like the reference's decoder call (models/w2v2_pr.py:155 passes no lengths).  Nothing
-        here synchronises host and device.  decoder = "flashlight": the sequence is framed by the silence token on the device
-        (hostlogic.ctc_bracketed_best_path: prepended / appended unless the first / last frame's own token is the silence).
-        decoder = "beam": the top hypothesis of the device beam search (aptai_ctc_beam_search), n = its full length."""
-        if self.decoder == "beam":
-            tokens, _, n_tok, _, _ = self._beam_search(out, max_n=max_n)
-            return tokens[:, 0].contiguous(), n_tok[:, 0].contiguous()
-        g, full = out._geom, out._logits_full
-        V = self.pr_head.weight.shape[0]
-        own = getattr(g, "fir_lens", None)
-        last = None
-        if own is not None:
-            # batch-invariant: the frames past a row's own length do not exist at batch size 1, so they decode as blank here (a
-            # copy of the small logit block with those frames' rows put on the blank; `_logits_full` itself stays as computed)
-            rows = full.view(g.B, g.Tp, -1)
-            pad = torch.arange(g.Tp, device=full.device)[None, :, None] >= own[:, None, None]
-            blank_row = torch.zeros(rows.shape[-1], device=full.device, dtype=full.dtype)
-            blank_row[self._blank()] = 1.0
-            full = torch.where(pad, blank_row, rows).view(full.shape).contiguous()
-            last = (own.long() - 1).clamp(min=0)
-        ids, n = ops.ctc_greedy_decode(full, full.shape[1], g.Tp, g.B, g.T, V, self._blank(), max_n)
-        sil = self._sil()
-        if sil is None:
-            return ids, n
-        if last is None:
-            ends = full.view(g.B, g.Tp, -1)[:, [0, g.T - 1], :V].argmax(dim=-1)
-        else:
-            rows = full.view(g.B, g.Tp, -1)[:, :, :V]
-            ends = torch.stack([rows[:, 0].argmax(dim=-1), rows[torch.arange(g.B, device=full.device), last].argmax(dim=-1)], dim=1)
-        front, back = (ends[:, :1] != sil).to(torch.int32), (ends[:, 1:] != sil).to(torch.int32)          # [B][1]
-        pos = torch.arange(max_n, device=ids.device, dtype=torch.int32)[None]
-        n1 = n[:, None]
-        framed = torch.gather(ids, 1, (pos - front).clamp(min=0).long())
-        framed = torch.where(pos < front, sil, framed)
-        framed = torch.where((pos == n1 + front) & (back == 1), sil, framed)
-        total = n1 + front + back
-        framed = torch.where(pos >= total, 0, framed).to(torch.int32)
-        return framed.contiguous(), total.clamp(max=max_n).view(-1).to(torch.int32)
+        """(tokens, n) of `_read_out`: the seam of Force_APTAI and the training script."""
+        tokens, _, n = self._read_out(out, max_n)
+        return tokens, n
+
+    @staticmethod
+    def _rows(tokens, timesteps, n, score=None):
+        """Host view of decoded rows [R][max_n] with lengths [R] (and scores [R]): [(ids int64, timesteps int32, score | None)] in
+        ONE device->host transfer (int32 values are exact in fp64)."""
+        max_n = tokens.shape[1]
+        packed = torch.cat([tokens.double(), timesteps.double(), n[:, None].double()] + ([] if score is None else [score[:, None]]),
+                           dim=1).cpu().numpy()
+        keep = np.minimum(packed[:, 2 * max_n].astype(np.int64), max_n)
+        return [(r[:k].astype(np.int64), r[max_n:max_n + k].astype(np.int32), None if score is None else float(r[-1]))
+                for r, k in zip(packed, keep)]
+
+    @staticmethod
+    def _ipa(vocab, idx):
+        inv = {v: k for k, v in vocab.items()}
+        return [inv.get(int(i), '?') for i in idx]
 
     def _decode(self, out):
         """Decoded id lists of the batch: the device decode + ONE host transfer."""
-        ids, n = self._decode_device(out, out._geom.T + 2)
-        ids, n = ids.cpu().numpy(), n.cpu().numpy()
-        return [ids[b, :n[b]].astype(np.int64) for b in range(len(n))]
+        return [idx for idx, _, _ in self._rows(*self._read_out(out, out._geom.T + 2))]
 
     def _nbest(self, audio_inputs, audio_lengths, options):
         self.eval()
         with torch.no_grad():
-            out, _ = self._logits_eval(audio_inputs, audio_lengths[:, None] if audio_lengths.dim() == 1 else audio_lengths)
+            out, _ = self._logits_eval(audio_inputs, audio_lengths)
             tokens, timesteps, n_tok, score, n_hyp = self._beam_search(out, **options)
             frame_lens = self.wav2vec2._get_feat_extract_output_lengths(audio_lengths.reshape(-1).to(tokens.device)).to(torch.int32)
             return {'tokens': tokens, 'timesteps': timesteps, 'n_tok': n_tok, 'score': score, 'n_hyp': n_hyp,
@@ -248,8 +233,7 @@ class Wav2Vec2_PR(nn.Module):
     def decode_nbest(self, audio_inputs, audio_lengths, **options):
         """n-best lists of the batch from the device beam search, whatever `decoder` is set to: `beam_options` overridden by
         `options` (beam_size, beam_size_token, beam_threshold, log_add, sil_score, nbest, max_n, lm, lm_weight:
-        ops.ctc_beam_search).  Runs in eval
-        mode without gradients.  Returns DEVICE tensors and never synchronises:
+        ops.ctc_beam_search).  Runs in eval mode without gradients.  Returns DEVICE tensors and never synchronises:
           tokens, timesteps int32 [B][nbest][max_n]  zero-padded; a timestep is the position in the framed token row (frame t -> t + 1)
           n_tok             int32 [B][nbest]         length of each hypothesis (0: the row has fewer hypotheses)
           score             fp64  [B][nbest]         best first; -inf where the row has fewer hypotheses
@@ -259,21 +243,13 @@ class Wav2Vec2_PR(nn.Module):
 
     def predict_nbest(self, wav, vocab, **options):
         """`predict_phonemes_durations` for every hypothesis of the n-best list of ONE utterance, best first: a list of
-        {'phn_seq_idx', 'phn_seq_ipa', 'phn_seq_dur', 'score'}.  One device->host transfer (int32 values are exact in fp64)."""
+        {'phn_seq_idx', 'phn_seq_ipa', 'phn_seq_dur', 'score'}.  One device->host transfer; a rank without hypothesis has no tokens."""
         wav, wav_input, wav_len = self._wav(wav)
         res, n_frames = self._nbest(wav_input, wav_len, options)
-        nb, max_n = res['tokens'].shape[1:]
-        packed = torch.cat([res['tokens'][0].double(), res['timesteps'][0].double(), res['n_tok'][0, :, None].double(),
-                            res['score'][0, :, None], res['n_hyp'][:1, None].expand(nb, 1).double()], dim=1).cpu().numpy()
         frame_sec_ratio = len(wav) / n_frames / 16000
-        inv = {v: k for k, v in vocab.items()}
-        hyps = []
-        for r in packed[:int(packed[0, -1])]:
-            n = min(int(r[2 * max_n]), max_n)
-            idx = r[:n].astype(np.int64)
-            hyps.append({'phn_seq_idx': idx, 'phn_seq_ipa': [inv.get(int(i), '?') for i in idx],
-                         'phn_seq_dur': [int(t) * frame_sec_ratio for t in r[max_n:max_n + n]], 'score': float(r[2 * max_n + 1])})
-        return hyps
+        return [{'phn_seq_idx': idx, 'phn_seq_ipa': self._ipa(vocab, idx), 'phn_seq_dur': [int(t) * frame_sec_ratio for t in ts],
+                 'score': score}
+                for idx, ts, score in self._rows(res['tokens'][0], res['timesteps'][0], res['n_tok'][0], res['score'][0]) if len(idx)]
 
     def get_embeddings_grad(self, audio_inputs, audio_lengths, vocab, intermediate_hidden, latter_hidden):
         """models/w2v2_pr.py:91-122: the encoder in whatever mode the module is in, WITH gradients (probing / saliency use):
@@ -301,7 +277,7 @@ class Wav2Vec2_PR(nn.Module):
         produced 'features_hidden', which no caller reads; it is returned as None)."""
         self.eval()
         with torch.no_grad():
-            out, logits = self._logits_eval(audio_inputs, audio_lengths[:, None] if audio_lengths.dim() == 1 else audio_lengths)
+            out, logits = self._logits_eval(audio_inputs, audio_lengths)
             frame_seq_lens = self.wav2vec2._get_feat_extract_output_lengths(audio_lengths)
             return {'features_hidden': None, 'last_transf_hidden': out.last_hidden_state.permute(0, 2, 1),
                     'phoneme_logits': logits.cpu().numpy().transpose(0, 2, 1), 'phn_pred_seq_idx': self._decode(out),
@@ -328,8 +304,7 @@ class Wav2Vec2_PR(nn.Module):
             _, wav_input, wav_len = self._wav(wav)
             out, logits = self._logits_eval(wav_input, wav_len)
             idx = self._decode(out)[0]
-            inv = {v: k for k, v in vocab.items()}
-            return {'phn_seq_idx': idx, 'phn_seq_ipa': [inv.get(int(i), '?') for i in idx]}
+            return {'phn_seq_idx': idx, 'phn_seq_ipa': self._ipa(vocab, idx)}
 
     def predict_phonemes_durations(self, wav, vocab):
         """models/w2v2_pr.py:191-235; timesteps = first frame of each emitted (non-blank, de-duplicated) label."""
@@ -338,16 +313,8 @@ class Wav2Vec2_PR(nn.Module):
             wav, wav_input, wav_len = self._wav(wav)
             out, logits = self._logits_eval(wav_input, wav_len)
             frame_sec_ratio = len(wav) / logits.size(1) / 16000
-            if self.decoder == "beam":      # tokens AND timesteps of the device search's top hypothesis, one transfer
-                tokens, timesteps, n_tok, _, _ = self._beam_search(out)
-                row = torch.cat([n_tok[0, :1], tokens[0, 0], timesteps[0, 0]]).cpu().numpy()
-                n = min(int(row[0]), tokens.shape[2])
-                idx, ts = row[1:1 + n].astype(np.int64), row[1 + tokens.shape[2]:1 + tokens.shape[2] + n].astype(np.int32)
-            else:
-                idx, ts = hostlogic.ctc_bracketed_best_path(logits[0].cpu().numpy(), logits.size(1), self._blank(), self._sil())
-            inv = {v: k for k, v in vocab.items()}
-            return {'phn_seq_idx': idx, 'phn_seq_ipa': [inv.get(int(i), '?') for i in idx],
-                    'phn_seq_dur': [t * frame_sec_ratio for t in ts]}
+            (idx, ts, _), = self._rows(*self._read_out(out, logits.size(1) + 2))       # tokens AND timesteps in one transfer
+            return {'phn_seq_idx': idx, 'phn_seq_ipa': self._ipa(vocab, idx), 'phn_seq_dur': [t * frame_sec_ratio for t in ts]}
 
     # ------------------------------------------------------------------ forced alignment of a known transcript
     def force_align(self, audio_inputs, audio_lengths, phoneme_labels):
@@ -364,7 +331,7 @@ class Wav2Vec2_PR(nn.Module):
         Tie rule and limits: include/aptai_hip.h; hostlogic.ctc_forced_align is the same contract in numpy."""
         self.eval()
         with torch.no_grad():
-            out, _ = self._logits_eval(audio_inputs, audio_lengths[:, None] if audio_lengths.dim() == 1 else audio_lengths)
+            out, _ = self._logits_eval(audio_inputs, audio_lengths)
             g, full = out._geom, out._logits_full                     # [B*Tp][Np] fp32 with its padded pitches
             dev = full.device
             V = self.pr_head.weight.shape[0]
@@ -402,8 +369,7 @@ class Wav2Vec2_PR(nn.Module):
             spans = res['spans'][0, :len(idx)].cpu().numpy()
             ft = res['frame_token'][0, :int(res['frame_seq_lens'][0].cpu())].cpu().numpy()
             filled = hostlogic.fill_blank_frames(ft)
-            inv = {v: k for k, v in vocab.items()}
-            return {'phn_seq_idx': idx, 'phn_seq_ipa': [inv.get(int(i), '?') for i in idx],
+            return {'phn_seq_idx': idx, 'phn_seq_ipa': self._ipa(vocab, idx),
                     'phn_start': [int(a) * frame_sec_ratio for a in spans[:, 0]],
                     'phn_end': [int(b) * frame_sec_ratio for b in spans[:, 1]],
                     'phn_score': res['token_score'][0, :len(idx)].cpu().numpy().tolist(), 'score': score,

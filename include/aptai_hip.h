@@ -509,11 +509,18 @@ int aptai_ctc_viterbi(const float* logits, int64_t ldl, int64_t rows_per_b, cons
                       float* token_score, void* stream);
 int64_t aptai_ctc_viterbi_workspace_bytes(int64_t B, int64_t T, int64_t ldt);
 /* Best-path CTC decode on the device (stand-in for the torchaudio beam decoder the reference calls at models/w2v2_pr.py:143-159,
- * which is absent here: parity unpinned): per utterance, frame argmax (first maximum) over ALL T rows, repeats collapsed, blank
- * dropped.  ids_out int32 [B][max_n] zero-padded (the aligner's phoneme slots, models/force_aptai.py:109-115), n_out int32 [B] =
- * decoded length, which the caller compares with max_n (models/force_aptai.py:111). */
-int aptai_ctc_greedy_decode(const float* logits, int64_t ldl, int64_t rows_per_b, int64_t B, int64_t T, int64_t V, int blank,
-                            int32_t* ids_out, int64_t max_n, int32_t* n_out, void* stream);
+ * which is absent here: parity unpinned).  Row b is exactly hostlogic.ctc_bracketed_best_path(logits[b], T_b, blank, sil)
+ * (aptai_amd/hostlogic.py, the oracle of the tests): frame argmax (first maximum) over the first T_b = clamp(input_lens[b], 0, T)
+ * frames (input_lens null: all T; frames at or past T_b are not read), repeats collapsed, blank dropped.  sil < 0: no framing, the
+ * timestep of a kept label is its frame t.  sil >= 0 (sil < V, sil != blank): the row is framed as the beam search below frames
+ * it - sil at timestep 0, frame t at timestep t + 1, sil at timestep T_b + 1, repeats collapsed over that T_b + 2 long row, so a
+ * silence on the first or last own frame merges with the framing one and a blank in between keeps both; T_b == 0 gives [sil] at 0.
+ * ids_out and timesteps_out (may be null) int32 [B][max_n] hold the first max_n entries, zero-padded (the aligner's phoneme slots,
+ * models/force_aptai.py:109-115); n_out int32 [B] = full decoded length, which the caller compares with max_n
+ * (models/force_aptai.py:111).  One wave per utterance, no atomics: same inputs -> same bits.  Non-finite logits are not supported. */
+int aptai_ctc_greedy_decode(const float* logits, int64_t ldl, int64_t rows_per_b, const int32_t* input_lens, int64_t B, int64_t T,
+                            int64_t V, int blank, int sil, int32_t* ids_out, int32_t* timesteps_out, int64_t max_n, int32_t* n_out,
+                            void* stream);
 /* Lexicon-free CTC beam search without a language model, on the device: the decoder the reference calls through torchaudio
  * (models/w2v2_pr.py:143-159, flashlight's LexiconFreeDecoder with a zero LM) as its published sources state it, with n-best
  * lists, true prefix scores (log_add) and per-token timesteps.  aptai_amd/hostlogic.py ctc_beam_search restates the same search

@@ -317,3 +317,16 @@ def test_reference_decoder_settings_return_the_framed_best_path():
     assert np.array_equal(tok, hostlogic.ctc_best_path(em, 5, blank=0))
     tok, ts = hostlogic.ctc_bracketed_best_path(em, 5, blank=0, sil=1)
     assert tok.tolist() == [1, 2, 1] and ts.tolist() == [0, 4, 6]          # the emitted 1 at frame 0 merged with the opening silence
+
+
+@pytest.mark.parametrize("blank", [0, 2])
+def test_best_path_decode_cases_hold_the_situations_they_are_there_for(blank):
+    """tests/greedy_cases.py (what tests/test_gpu_ctc_ops.py decodes on the device): every situation is in the inputs, and the
+    entry refuses a silence token outside the vocabulary or equal to the blank before any launch."""
+    import greedy_cases
+    from aptai_amd import _lib
+    assert blank in greedy_cases.BLANKS
+    greedy_cases.assert_situations(blank)
+    for sil in (greedy_cases.V, blank):
+        with pytest.raises(_lib.AptaiHipError, match="aptai_ctc_greedy_decode: sil"):
+            _lib.call("aptai_ctc_greedy_decode", 16, 64, 133, None, 6, 130, greedy_cases.V, blank, sil, 16, None, 5, 16, None)

@@ -278,3 +278,27 @@ def test_batch_invariant_beam_rows_equal_the_utterance_alone(pr):
     finally:
         model.batch_invariant = False
         model.decoder = "best_path"
+
+
+def test_batch_invariant_framed_rows_equal_the_utterance_alone(pr):
+    """batch_invariant with decoder = "flashlight": the closing silence meets each row's own last frame, so every row of the padded
+    batch decodes as the utterance does alone, and the shorter clip alone is the oracle on its own logits, ids and durations."""
+    from aptai_amd import hostlogic
+    model, wav, x, lens = pr
+    try:
+        model.batch_invariant = True
+        model.decoder = "flashlight"
+        ids = model.get_embeddings(x, lens)["phn_pred_seq_idx"]
+        for b in range(2):
+            n_audio = int(lens[b])
+            alone = model.get_embeddings(x[b:b + 1, :n_audio], lens[b:b + 1])["phn_pred_seq_idx"][0]
+            assert list(ids[b]) == list(alone) and len(alone) >= 3
+        short = x[1, :int(lens[1])].cpu().numpy()
+        dur = model.predict_phonemes_durations(short, model.vocab)
+        lg = model.get_ctc_logits(short)
+        want, ts = hostlogic.ctc_bracketed_best_path(lg, lg.shape[0], 0, 5)
+        assert list(dur["phn_seq_idx"]) == list(want) == list(ids[1])
+        assert np.array_equal(np.asarray(dur["phn_seq_dur"]), ts * (len(short) / lg.shape[0] / 16000))
+    finally:
+        model.batch_invariant = False
+        model.decoder = "best_path"

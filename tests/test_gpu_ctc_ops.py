@@ -10,6 +10,7 @@ summation order) - never the kernel's figure."""
 import functools
 from types import SimpleNamespace
 
+import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
@@ -384,6 +385,46 @@ def test_greedy_decode_against_best_path(T, V):
             k = min(len(w), m)
             assert n[b].item() == len(w), (names[b], blank, "max_n", m)
             assert ids[b, :k].tolist() == w[:k].tolist() and (ids[b, k:] == 0).all(), (names[b], blank, "max_n", m)
+
+
+@functools.lru_cache(maxsize=None)
+def _greedy_device_batch(blank):
+    import greedy_cases
+    return torch.from_numpy(greedy_cases.padded(blank)).cuda()
+
+
+@pytest.mark.parametrize("max_n", [132, 5])
+@pytest.mark.parametrize("own_lens", [True, False])
+@pytest.mark.parametrize("blank", [0, 2])
+@pytest.mark.parametrize("sil", [None, 1])
+def test_greedy_decode_contract_lengths_framing_timesteps(sil, blank, own_lens, max_n):
+    """aptai_ctc_greedy_decode = hostlogic.ctc_bracketed_best_path row by row on the batch of tests/greedy_cases.py: tokens,
+    timesteps and the full length, with and without the silence framing, per-row lengths (None = all T frames, where the frames
+    past a row's length are decoded too), max_n = T + 2 and a max_n that cuts rows.  Integers: equality, no tolerance."""
+    import greedy_cases as gc
+    from aptai_amd import ops
+    gc.assert_situations(blank)
+    dev = _greedy_device_batch(blank)
+    lens = torch.tensor(gc.LENS, dtype=torch.int32).cuda() if own_lens else None
+    want = gc.oracle(blank, sil, own_lens)
+
+    def run():
+        return [x.cpu().numpy() for x in ops.ctc_greedy_decode(dev, gc.LDL, gc.ROWS_PER_B, gc.B, gc.T, gc.V, blank, max_n,
+                                                               input_lens_i32=lens, sil=sil, want_timesteps=True)]
+    ids, ts, n = run()
+    assert ids.shape == ts.shape == (gc.B, max_n) and ids.dtype == ts.dtype == n.dtype == np.int32
+    for b, (tok, pos) in enumerate(want):
+        k = min(len(tok), max_n)
+        assert n[b] == len(tok), (b, n[b], len(tok))
+        assert ids[b, :k].tolist() == tok[:k].tolist() and ts[b, :k].tolist() == pos[:k].tolist(), b
+        assert not ids[b, k:].any() and not ts[b, k:].any(), b
+    assert [x.tobytes() for x in run()] == [x.tobytes() for x in (ids, ts, n)]
+    if not own_lens:                                             # None is all-T lengths, and the two-value form is the same decode
+        full = torch.full((gc.B,), gc.T, dtype=torch.int32).cuda()
+        same = ops.ctc_greedy_decode(dev, gc.LDL, gc.ROWS_PER_B, gc.B, gc.T, gc.V, blank, max_n, input_lens_i32=full, sil=sil)
+        assert len(same) == 2 and np.array_equal(same[0].cpu().numpy(), ids) and np.array_equal(same[1].cpu().numpy(), n)
+    with pytest.raises(ValueError, match="input_lens_i32"):
+        ops.ctc_greedy_decode(dev, gc.LDL, gc.ROWS_PER_B, gc.B, gc.T, gc.V, blank, max_n, input_lens_i32=torch.zeros(gc.B).cuda())
 
 
 def test_decode_rows_cover_the_round_boundary():

@@ -88,8 +88,8 @@ def main(B=16, T=499, V=46, ldl=64, rounds=7, iters=20, lm_orders=()):
             print(f"{name}_lm{order}: {n_states} states, tables {(w.numel() * 12 + wf.numel() * 8) / 1024:.0f} KiB")
     ids = torch.empty((B, max_n), device=dev, dtype=torch.int32)
     n = torch.empty(B, device=dev, dtype=torch.int32)
-    fns["greedy"] = lambda: _lib.call("aptai_ctc_greedy_decode", logits.data_ptr(), ldl, T, B, T, V, 0, ids.data_ptr(), max_n, n.data_ptr(),
-                                      stream)
+    fns["greedy"] = lambda: _lib.call("aptai_ctc_greedy_decode", logits.data_ptr(), ldl, T, None, B, T, V, 0, -1, ids.data_ptr(), None, max_n,
+                                      n.data_ptr(), stream)
     for fn in fns.values():
         for _ in range(3):
             fn()
