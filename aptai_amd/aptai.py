@@ -9,88 +9,19 @@ are arguments so BASELINE.json's 12-track variant can be benchmarked.
 """
 from __future__ import annotations
 
-from types import SimpleNamespace
-
 import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import ops
-from .config import W2V2Config
-from . import hostlogic
+from . import hostlogic, task_heads
 from .hostlogic import TV_NAMES
 from .modules import LowPassFilterLayer
-from .wav2vec2 import _APTAI_HEADS_STREAM, Wav2Vec2Model, _seed, batch_invariant_scope
-
-_PADN = 64      # head Linears run on the MFMA GEMM with N padded to 64
-
-
-def heads_fwd(h, tv_w, tv_b, ph_w, ph_b, st):
-    """tanh/leaky-relu -> Linear(H, n) x2 -> FIR -> masked MSE + masked CE (+ argmax), models/aptai.py:83-106.
-    Returns ((loss, mse, ce, tvs, pred, logits), saved)."""
-    g, M, H = st.g, st.g.M, h.shape[1]
-    dev = h.device
-    n_tv, n_phn = tv_w.shape[0], ph_w.shape[0]
-    a_tv, a_ph = ops.head_act_fwd(h, st.p_tv, st.p_ph, st.seed)
-
-    def pad_w(w, b):
-        wp = torch.zeros((_PADN, H), device=dev, dtype=torch.bfloat16)
-        ops.cast_bf16(w.detach(), wp[:w.shape[0]])
-        bp = torch.zeros(_PADN, device=dev, dtype=torch.float32)
-        bp[:b.shape[0]] = b.detach()
-        return wp, bp
-    wtv, btv = pad_w(tv_w, tv_b)
-    wph, bph = pad_w(ph_w, ph_b)
-    tv_raw = ops.gemm(a_tv, wtv, M, _PADN, H, bias=btv, out_f32=True)
-    logits = ops.gemm(a_ph, wph, M, _PADN, H, bias=bph, out_f32=True)
-    tvs = torch.empty((g.B, g.T, n_tv), device=dev, dtype=torch.float32)
-    # batch-invariant inference (Wav2Vec2Model.batch_invariant): the filter's zero padding starts at each row's own length
-    ops.lowpass_fir(tv_raw, _PADN, g.Tp, st.taps, tvs, n_tv, g.T, g.B, g.T, g.T, n_tv, n_tv, frame_lens=getattr(g, "fir_lens", None))
-    scalars, pred = ops.aptai_loss_fwd(tvs, st.tv_tgt, logits, _PADN, g.Tp, st.phn_tgt, g.B, g.T, n_tv, n_phn, st.w_mse, st.w_ce)
-    saved = SimpleNamespace(h=h, a_tv=a_tv, a_ph=a_ph, wtv=wtv, wph=wph, tvs=tvs, logits=logits, scalars=scalars, n_tv=n_tv,
-                            n_phn=n_phn)
-    return (scalars[0], scalars[1], scalars[2], tvs, pred, logits), saved
-
-
-def heads_bwd(s, st, gl):
-    """Returns (dh, dW_tv, db_tv, dW_ph, db_ph); ``gl`` = device scalar gradient of the loss (or None = 1)."""
-    g, M, H = st.g, st.g.M, s.h.shape[1]
-    # data parallel: normalise by the GLOBAL valid counts / world (dp.GlobalLossNorm) instead of this shard's own counts
-    norm = getattr(st, "norm_scalars", None)
-    d_tvs, d_logits = ops.aptai_loss_bwd(s.tvs, st.tv_tgt, s.logits, _PADN, g.Tp, st.phn_tgt, g.B, g.T, s.n_tv, s.n_phn, st.w_mse,
-                                         st.w_ce, norm() if callable(norm) else (norm if norm is not None else s.scalars), gl,
-                                         ldd=_PADN)
-    d_tvraw = torch.empty((M, _PADN), device=s.h.device, dtype=torch.bfloat16)
-    ops.lowpass_fir(d_tvs, s.n_tv, g.T, st.taps, d_tvraw, _PADN, g.Tp, g.B, g.T, g.Tp, s.n_tv, _PADN)
-    da_tv = ops.gemm(d_tvraw, s.wtv, M, H, _PADN, b_kmajor=True)
-    da_ph = ops.gemm(d_logits, s.wph, M, H, _PADN, b_kmajor=True)
-    sk = max(1, min(16, M // 1024))
-    dwtv = ops.gemm(d_tvraw, s.a_tv, _PADN, H, M, a_kmajor=True, b_kmajor=True, out_f32=True, split_k=sk)
-    dwph = ops.gemm(d_logits, s.a_ph, _PADN, H, M, a_kmajor=True, b_kmajor=True, out_f32=True, split_k=sk)
-    dbtv = ops.colsum(d_tvraw, M, _PADN)
-    dbph = ops.colsum(d_logits, M, _PADN)
-    dh = ops.head_act_bwd(s.h, da_tv, da_ph, st.p_tv, st.p_ph, st.seed)
-    return dh, dwtv[:s.n_tv], dbtv[:s.n_tv], dwph[:s.n_phn], dbph[:s.n_phn]
-
-
-class _HeadsFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, h, tv_w, tv_b, ph_w, ph_b, st):
-        (loss, mse, ce, tvs, pred, logits), ctx.saved = heads_fwd(h, tv_w, tv_b, ph_w, ph_b, st)
-        ctx.st = st
-        loss, mse, ce = loss.clone(), mse.clone(), ce.clone()
-        ctx.mark_non_differentiable(mse, ce, tvs, pred, logits)
-        return loss, mse, ce, tvs, pred, logits
-
-    @staticmethod
-    def backward(ctx, gloss, *_):
-        out = heads_bwd(ctx.saved, ctx.st, gloss.float().reshape(1).contiguous())
-        ctx.saved = None
-        return out + (None,)
+from .wav2vec2 import Wav2Vec2Model, batch_invariant_scope
 
 
 class APTAI(nn.Module):
+    task_head = task_heads.AptaiHead()       # everything after the encoder, for this class and the graph runners (task_heads.py)
     # opt-in: eval-mode calls return for every row what the utterance gets at batch size 1 (Wav2Vec2Model.batch_invariant for the
     # encoder, the low-pass filter padded at each row's own length); training-mode calls are what they were
     batch_invariant = False
@@ -103,7 +34,7 @@ class APTAI(nn.Module):
         self.huggingface_model_id = huggingface_model_id
         self.pretrain_cfg = pretrain_cfg
         self.n_tv, self.n_phn = n_tv, n_phn
-        if n_tv > _PADN or n_phn > _PADN:
+        if n_tv > task_heads._PADN or n_phn > task_heads._PADN:
             raise ValueError("head widths above 64 are not built")
 
         self.wav2vec2 = Wav2Vec2Model.from_pretrained(huggingface_model_id, config=pretrain_cfg, cache_dir=cache_dir).to(device)
@@ -120,19 +51,11 @@ class APTAI(nn.Module):
     def _heads(self, w2v2_out, tv_targets, phn_targets):
         g = w2v2_out._geom
         h = w2v2_out._flat_last                       # hidden_states[-1] == hidden_states[24] for the large backbone
-        dev = h.device
-        if tv_targets is None:
-            tv_targets = torch.full((g.B, g.T, self.n_tv), -100.0, device=dev)
-            phn_targets = torch.zeros((g.B, g.T), device=dev, dtype=torch.long)
-        tr = self.training
-        st = SimpleNamespace(g=g, p_tv=self.tv_head[0].p if tr else 0.0, p_ph=self.phn_head[0].p if tr else 0.0,
-                             seed=_seed(self.wav2vec2.base_seed, self.wav2vec2._step, _APTAI_HEADS_STREAM), taps=self.tv_lowpass.taps(),
-                             tv_tgt=tv_targets.contiguous(), phn_tgt=phn_targets.contiguous(), w_mse=0.5, w_ce=0.5)
-        if self.dp_loss_norm is not None and tr:
+        st = self.task_head.state(self, g, (self.wav2vec2.base_seed, self.wav2vec2._step), self.training, tv_targets, phn_targets)
+        if self.dp_loss_norm is not None and self.training:
             self.dp_loss_norm.begin(st.tv_tgt, st.phn_tgt)       # 2-scalar all-reduce under the head GEMMs
             st.norm_scalars = self.dp_loss_norm.scalars           # resolved (waited for) in the backward
-        return _HeadsFn.apply(h, self.tv_head[2].weight, self.tv_head[2].bias, self.phn_head[2].weight,
-                              self.phn_head[2].bias, st)
+        return task_heads.HeadFn.apply(self.task_head, h, st, *self.task_head.params(self))
 
     def forward(self, epoch, audio_inputs, audio_lengths, phn_frames_49hz, LA=None, LP=None, JA=None, TTCL=None,
                 TTCD=None, TMCL=None, TMCD=None, TBCL=None, TBCD=None, **extra_tvs):
@@ -144,8 +67,7 @@ class APTAI(nn.Module):
         with batch_invariant_scope(self.wav2vec2, self.batch_invariant and not self.training):
             w2v2_out = self.wav2vec2(audio_inputs, attention_mask=audio_lengths[:, None], return_dict=True,
                                      output_hidden_states=True)
-        loss, mse, ce, tvs, pred, _ = self._heads(w2v2_out, tv_targets, phn_frames_49hz)
-        return {'loss': loss, 'mse_loss': mse, 'ce_loss': ce, 'tvs_pred': tvs, 'phn_fc_pred': pred}
+        return self.task_head.result(self._heads(w2v2_out, tv_targets, phn_frames_49hz), w2v2_out._geom, None)
 
     def get_config(self):
         return {'device': self.device, 'vocab': self.vocab, 'huggingface_model_id': self.huggingface_model_id,

@@ -20,12 +20,12 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import ops
-from .config import W2V2Config, load_model_cfg
+from . import ops, task_heads
+from .config import load_model_cfg
 from .hostlogic import TV_NAMES
-from .modules import CrossAttention, ForwardSumLoss, LowPassFilterLayer, PositionalEncoding, RNN
+from .modules import CrossAttention, ForwardSumLoss, LowPassFilterLayer, PositionalEncoding, RNN, fwd_sum_targets
 from .w2v2_pr import Wav2Vec2_PR
-from .wav2vec2 import _FORCE_HEADS_STREAM, _seed, batch_invariant_scope
+from .wav2vec2 import batch_invariant_scope
 
 _NPHN = 60                              # the reference's max_phn_seq_len (models/force_aptai.py:36): the default slot count
 MAX_PHN_SLOTS = ops.XATTN_MAX_SLOTS     # 255: what the wide softmax pair and the CTC kernels (256 classes, 511 states) hold
@@ -42,150 +42,9 @@ def labels_to_slots(labels, cap):
     return ids.contiguous(), valid.sum(dim=1).to(torch.int32)
 
 
-def force_heads_fwd(ac, st, P):
-    """Everything of Force_APTAI.forward after the encoder, fp32 on the device (csrc/force.hip, lstm.hip, ctc.hip).  Returns
-    ((loss, tv_loss, align_loss, tvs, frame_phns, att_log, att_out, hout, align), saved) - shared by the autograd path
-    (_ForceHeadsFn) and the hipGraph runner (graphed.GraphedForceStep)."""
-    (fl_w, fl_b, emb_w, q_w, q_b, k_w, k_b, ln_w, ln_b, wih0, whh0, bih0, bhh0, wih1, whh1, bih1, bhh1, l0_w, l0_b, l3_w,
-     l3_b) = P
-    g = st.g
-    B, Tp, T, M, H = g.B, g.Tp, g.T, g.M, ac.shape[1]
-    dev = ac.device
-    N = st.nphn                                        # phoneme slots per utterance (Force_APTAI.max_phn_seq_len, 60 by default)
-    ld = ops.fs_row_pitch(N)                           # floats per forward-sum row: 64 up to 63 slots, 256 at 255
-    s = SimpleNamespace()
-    s.phn = ops.embed_pe_fwd(st.ids, emb_w, st.pe, N, st.p_hid, _seed(st.seed, 1))                        # [B*N][128]
-    fh = ops.linear_f32(ac, fl_w, fl_b, rows=M)                                                           # [M][128]
-    s.fhd = ops.dropout_f32(fh, st.p_hid, _seed(st.seed, 2))
-    s.cat = torch.empty((M, 256), device=dev, dtype=torch.float32)
-    q = s.cat[:, 128:]
-    ops.linear_f32(s.fhd, q_w, q_b, out=q, ldc=256)
-    s.k = ops.linear_f32(s.phn, k_w, k_b)                                                                  # [B*N][128]
-    raw = ops.sgemm(q, 256, 1, s.k, 1, 128, Tp, N, 128, batch=B, bsa=Tp * 256, bsb=N * 128, bsc=Tp * N)
-    # forward-sum (CTC) input rows [blank = -1 | att_log | 0], written by the same kernel
-    s.pad = torch.empty((M, ld), device=dev, dtype=torch.float32)
-    s.energy, s.att, s.att_log, s.align = ops.xattn_softmax_fwd(raw, st.ids, B, Tp, N, fs_rows=s.pad)
-    ops.sgemm(s.att, N, 1, s.k, 128, 1, Tp, 128, N, out=s.cat, ldc=256, batch=B, bsa=Tp * N, bsb=N * 128, bsc=Tp * 256)
-    s.att_out, s.lm, s.lr = ops.layernorm_f32_fwd(s.cat, ln_w, ln_b)
-    # rows in the LSTM kernels' gate-interleaved order (csrc/lstm.hip: column dir * 1024 + unit * 4 + gate of xproj / gates / dgates)
-    perm = ops.lstm_gate_perm(dev)[0]
-    s.wih = torch.cat([wih0, wih1])[perm].contiguous()                                                    # [2048][256]
-    bsum = torch.cat([bih0 + bhh0, bih1 + bhh1])[perm].contiguous()
-    xproj = ops.linear_f32(s.att_out, s.wih, bsum)                                                         # [M][2048]
-    s.whh = torch.stack([whh0, whh1]).contiguous()                                                         # [2][1024][256]
-    s.hout, s.gates, s.cst = ops.lstm_fwd(xproj, s.whh, st.rnn_lens, B, Tp, T)
-    h1 = ops.linear_f32(s.hout, l0_w, l0_b)
-    s.h1a = ops.tanh_dropout_fwd(h1, st.p_rnn, _seed(st.seed, 3))
-    tv_raw = ops.linear_f32(s.h1a, l3_w, l3_b)                                                             # [M][9]
-    n_tv = l3_w.shape[0]
-    s.tvs = torch.empty((B, T, n_tv), device=dev, dtype=torch.float32)
-    # batch-invariant inference (Wav2Vec2Model.batch_invariant): the filter's zero padding starts at each row's own length
-    ops.lowpass_fir(tv_raw, n_tv, Tp, st.taps, s.tvs, n_tv, T, B, T, T, n_tv, n_tv, frame_lens=getattr(g, "fir_lens", None))
-    s.dummy_logits = torch.zeros((M, 1), device=dev, dtype=torch.float32)
-    s.dummy_phn = torch.zeros((B, T), device=dev, dtype=torch.int64)
-    s.sc, _ = ops.aptai_loss_fwd(s.tvs, st.tv_tgt, s.dummy_logits, 1, Tp, s.dummy_phn, B, T, n_tv, 1, 1.0, 0.0, want_pred=False)
-    # forward-sum (CTC) alignment loss on [blank=-1 | att_log]
-    s.fs_loss, s.nll, _, s.alpha = ops.ctc_fwd(s.pad, ld, Tp, st.fs_targets, st.frame_lens, st.text_lens, B, T, N + 1,
-                                               blank=0, reduction="mean", zero_infinity=True, vocab_sizes_i32=st.vocab_sizes,
-                                               want_log_probs=False)
-    tv_loss = s.sc[1].clone()
-    align_loss = s.fs_loss.reshape(()).clone()
-    loss = 0.4 * tv_loss + 0.6 * align_loss
-    align = s.align
-    if getattr(st, "readout", "argmax") == "monotonic":
-        # Viterbi read-out of the trellis the forward-sum loss trains (topology 1: every phoneme owns >= 1 frame, no jumps back):
-        # the att_log rows sit at column 1 of the forward-sum rows.  More phonemes than frames -> the argmax indices stay.
-        ft, _, score, _ = ops.ctc_viterbi(s.pad[:, 1:], ld, Tp, st.mono_targets, st.frame_lens, st.text_lens, B, T, N,
-                                          topology="monotonic", vocab_sizes_i32=st.text_lens, want_token_score=False)
-        align = s.align.clone()
-        align[:, :T] = torch.where((ft >= 0) & torch.isfinite(score)[:, None], ft.long(), s.align[:, :T])
-    frame_phns = ops.gather_alignment(st.ids, align, st.frame_lens, B, Tp, N)
-    return (loss, tv_loss, align_loss, s.tvs, frame_phns, s.att_log, s.att_out, s.hout, align), s
-
-
-def force_heads_bwd(s, st, P, ac, gloss=None):
-    """Gradients of the 21 head parameters (order of P) for dLoss = gloss (None = 1)."""
-    (fl_w, fl_b, emb_w, q_w, q_b, k_w, k_b, ln_w, ln_b, wih0, whh0, bih0, bhh0, wih1, whh1, bih1, bhh1, l0_w, l0_b, l3_w,
-     l3_b) = P
-    g = st.g
-    B, Tp, T, M, H = g.B, g.Tp, g.T, g.M, ac.shape[1]
-    dev = ac.device
-    n_tv = l3_w.shape[0]
-    N = st.nphn
-    ld = ops.fs_row_pitch(N)
-    if B * N > 8192:
-        raise ValueError(f"Force_APTAI backward: batch {B} x max_phn_seq_len {N} = {B * N} phoneme rows, the embedding gradient "
-                         "kernel (aptai_embed_bwd) takes 8192 at most")
-    gl = torch.ones(1, device=ac.device, dtype=torch.float32) if gloss is None else gloss.float().reshape(1)
-    # ---- TV branch
-    norm = getattr(st, "norm_scalars", None)             # data parallel: global valid TV count / world (dp.GlobalLossNorm)
-    d_tvs, _ = ops.aptai_loss_bwd(s.tvs, st.tv_tgt, s.dummy_logits, 1, Tp, s.dummy_phn, B, T, n_tv, 1, 1.0, 0.0,
-                                  norm() if norm is not None else s.sc, (0.4 * gl).contiguous(), ldd=8)
-    d_tvraw = torch.empty((M, n_tv), device=dev, dtype=torch.float32)
-    ops.lowpass_fir(d_tvs, n_tv, T, st.taps, d_tvraw, n_tv, Tp, B, T, Tp, n_tv, n_tv)
-    dl3_w = ops.sgemm(d_tvraw, 1, n_tv, s.h1a, 256, 1, n_tv, 256, M)
-    dl3_b = ops.colsum_f32(d_tvraw, M, n_tv)
-    dh1a = ops.sgemm(d_tvraw, n_tv, 1, l3_w, 256, 1, M, 256, n_tv)
-    dh1 = ops.tanh_dropout_bwd(s.h1a, dh1a, st.p_rnn, _seed(st.seed, 3))
-    dl0_w = ops.sgemm(dh1, 1, 256, s.hout, 512, 1, 256, 512, M)
-    dl0_b = ops.colsum_f32(dh1, M, 256)
-    dhout = ops.sgemm(dh1, 256, 1, l0_w, 512, 1, M, 512, 256)
-    dgates = ops.lstm_bwd(dhout, s.whh, st.rnn_lens, s.gates, s.cst, B, Tp, T)                              # [M][2048]
-    dwih = ops.sgemm(dgates, 1, 2048, s.att_out, 256, 1, 2048, 256, M)
-    dbg = ops.colsum_f32(dgates, M, 2048)
-    # dW_hh[dir] = sum_t dgates[t][dir]^T h_prev[t][dir]  (h_prev = previous VISITED frame: t-1 forward, t+1 reverse;
-    # the rows in between utterances hold zeros in hout / dgates, so one shifted GEMM over all rows is exact)
-    dwhh0 = ops.sgemm(dgates[1:], 1, 2048, s.hout, 512, 1, 1024, 256, M - 1)
-    dwhh1 = ops.sgemm(dgates[:, 1024:], 1, 2048, s.hout[1:, 256:], 512, 1, 1024, 256, M - 1)
-    datt_out = ops.sgemm(dgates, 2048, 1, s.wih, 256, 1, M, 256, 2048)
-    # the four products above have the gate axis in the kernels' interleaved order: back to torch's gate-major rows
-    inv = ops.lstm_gate_perm(dev)[1]
-    dwih, dbg = dwih[inv], dbg[inv]
-    dwhh0, dwhh1 = dwhh0[inv[:1024]], dwhh1[inv[:1024]]
-    dcat, dln_w, dln_b = ops.layernorm_f32_bwd(datt_out, s.cat, s.lm, s.lr, ln_w)
-    # ---- cross attention
-    d_att = ops.sgemm(dcat, 256, 1, s.k, 1, 128, Tp, N, 128, batch=B, bsa=Tp * 256, bsb=N * 128, bsc=Tp * N)
-    dk = ops.sgemm(s.att, 1, N, dcat, 256, 1, N, 128, Tp, batch=B, bsa=Tp * N, bsb=Tp * 256, bsc=N * 128)
-    dpad = ops.ctc_bwd(s.pad, ld, Tp, st.fs_targets, st.frame_lens, st.text_lens, B, T, N + 1, s.alpha, s.nll,
-                       (0.6 * gl).contiguous(), blank=0, reduction="mean", zero_infinity=True, vocab_sizes_i32=st.vocab_sizes,
-                       ldd=ld, out_dtype=torch.float32)
-    d_raw = ops.xattn_softmax_bwd(s.att, s.att_log, d_att, dpad[:, 1:], ld_dattlog=ld)     # columns 1..N of the forward-sum rows, in place
-    dq = dcat[:, 128:].contiguous()
-    ops.sgemm(d_raw, N, 1, s.k, 128, 1, Tp, 128, N, out=dq, ldc=128, accumulate=True, batch=B, bsa=Tp * N, bsb=N * 128, bsc=Tp * 128)
-    ops.sgemm(d_raw, 1, N, s.cat[:, 128:], 256, 1, N, 128, Tp, out=dk, ldc=128, accumulate=True, batch=B, bsa=Tp * N, bsb=Tp * 256,
-              bsc=N * 128)
-    dq_w = ops.sgemm(dq, 1, 128, s.fhd, 128, 1, 128, 128, M)
-    dq_b = ops.colsum_f32(dq, M, 128)
-    dfhd = ops.sgemm(dq, 128, 1, q_w, 128, 1, M, 128, 128)
-    dk_w = ops.sgemm(dk, 1, 128, s.phn, 128, 1, 128, 128, B * N)
-    dk_b = ops.colsum_f32(dk, B * N, 128)
-    dphn = ops.sgemm(dk, 128, 1, k_w, 128, 1, B * N, 128, 128)
-    demb = ops.embed_bwd(st.ids, dphn, emb_w.shape[0], st.p_hid, _seed(st.seed, 1))
-    dfh = ops.dropout_f32(dfhd, st.p_hid, _seed(st.seed, 2))
-    dfl_wT = ops.sgemm(ac, 1, H, dfh, 128, 1, H, 128, M)                                                    # [H][128]
-    dfl_b = ops.colsum_f32(dfh, M, 128)
-    return (dfl_wT.t().contiguous(), dfl_b, demb, dq_w, dq_b, dk_w, dk_b, dln_w, dln_b,
-            dwih[:1024], dwhh0, dbg[:1024], dbg[:1024], dwih[1024:], dwhh1, dbg[1024:], dbg[1024:], dl0_w, dl0_b, dl3_w, dl3_b)
-
-
-class _ForceHeadsFn(torch.autograd.Function):
-    """force_heads_fwd / force_heads_bwd behind autograd (the eager drop-in path)."""
-
-    @staticmethod
-    def forward(ctx, ac, st, *P):
-        outs, s = force_heads_fwd(ac, st, P)
-        ctx.st, ctx.saved, ctx.P, ctx.ac = st, s, P, ac
-        ctx.mark_non_differentiable(*outs[1:])
-        return outs
-
-    @staticmethod
-    def backward(ctx, gloss, *_):
-        grads = force_heads_bwd(ctx.saved, ctx.st, ctx.P, ctx.ac, gloss)
-        ctx.saved = None
-        return (None, None) + tuple(grads)
-
-
 class Force_APTAI(nn.Module):
+    task_head = task_heads.ForceHead()       # everything after the frozen encoder, for this class and GraphedForceStep (task_heads.py)
+
     def __init__(self, pr_model_path, device, vocab, max_phn_seq_len=_NPHN):
         super().__init__()
         assert os.path.exists(pr_model_path)
@@ -370,41 +229,21 @@ class Force_APTAI(nn.Module):
         return enc
 
     def _heads_state(self, g, ids, nlen, frame_lens, tv_targets, step):
-        """(st, P) of force_heads_fwd / force_heads_bwd for one encoded batch (all device tensors; no synchronisation)."""
-        pr = self.w2v2_pr
-        dev = ids.device
-        tr = self.training
-        n_tv = self.rnn.linear[3].weight.shape[0]
-        if tv_targets is None:
-            tv_targets = torch.full((g.B, g.T, n_tv), -100.0, device=dev)
-        consts = self._consts(g.B, dev)
-        # models/modules.py:209-212: the batch-1 branch runs the LSTM unpacked over ALL frames
-        rnn_lens = consts["full_T"](g.T) if g.B == 1 else frame_lens
-        st = SimpleNamespace(g=g, ids=ids, nphn=self.max_phn_seq_len, pe=self.pe_phn.pe.reshape(self.max_phn_seq_len, -1).contiguous(),
-                             taps=self.tv_lowpass.taps(),
-                             p_hid=self.hidden_drop if tr else 0.0, p_rnn=self.rnn_drop if tr else 0.0,
-                             seed=_seed(pr.wav2vec2.base_seed, step, _FORCE_HEADS_STREAM),
-                             tv_tgt=tv_targets.contiguous(), fs_targets=consts["fs_targets"], frame_lens=frame_lens, rnn_lens=rnn_lens,
-                             text_lens=nlen, vocab_sizes=nlen + 1, readout=self._readout(), mono_targets=consts["mono_targets"])
-        if getattr(self, "dp_loss_norm", None) is not None and tr:
+        """(st, P) of the task head for one encoded batch: its state and the named parameters (task_heads.ForceParams)."""
+        head = self.task_head
+        st = head.state(self, g, (self.w2v2_pr.wav2vec2.base_seed, step), self.training, ids, nlen, frame_lens, tv_targets)
+        if getattr(self, "dp_loss_norm", None) is not None and self.training:
             # the TV loss is a masked mean over the batch (models/force_aptai.py:137-141); the alignment and CTC terms are
             # means over utterances, which equal-sized shards already average exactly
             self.dp_loss_norm.begin(st.tv_tgt, None)
             st.norm_scalars = self.dp_loss_norm.scalars
-        lstm = self.rnn.lstm
-        P = (self.frame_lin.weight, self.frame_lin.bias, self.phn_emb_layer.weight, self.xatt.q.weight, self.xatt.q.bias,
-             self.xatt.k.weight, self.xatt.k.bias, self.xatt.layer_norm.weight, self.xatt.layer_norm.bias,
-             lstm.weight_ih_l0, lstm.weight_hh_l0, lstm.bias_ih_l0, lstm.bias_hh_l0, lstm.weight_ih_l0_reverse,
-             lstm.weight_hh_l0_reverse, lstm.bias_ih_l0_reverse, lstm.bias_hh_l0_reverse, self.rnn.linear[0].weight,
-             self.rnn.linear[0].bias, self.rnn.linear[3].weight, self.rnn.linear[3].bias)
-        return st, P
+        return st, head.params(self)
 
     def _run(self, audio_inputs, audio_lengths, tv_targets=None, phn_pred_list=None, _ac_override=None, _prefetch_next=None,
              labels=None):
         """Encoder (inference) -> decode -> heads.  Nothing in here synchronises host and device: the best-path decode, the
         phoneme slots, every length vector and the alignment read-out stay on the device; `_lists` makes the Python lists the
         reference returns with one round of transfers at the very end."""
-        pr = self.w2v2_pr
         enc = self._take_prefetched(audio_inputs, audio_lengths) if phn_pred_list is None else None
         if enc is None:
             enc = self._encode(audio_inputs, audio_lengths, phn_pred_list, labels)
@@ -413,10 +252,9 @@ class Force_APTAI(nn.Module):
         if _prefetch_next is not None:                                 # the NEXT batch's encoder pass goes out before this batch's heads
             self.prefetch(*_prefetch_next)
         g, ids, nlen, frame_lens = enc.g, enc.ids, enc.nlen, enc.frame_lens
-        dev = enc.ac.device
         ac = enc.ac if _ac_override is None else _ac_override          # test hook: heads on given embeddings
         st, P = self._heads_state(g, ids, nlen, frame_lens, tv_targets, enc.step)
-        res = _ForceHeadsFn.apply(ac, st, *P)
+        res = task_heads.HeadFn.apply(self.task_head, ac, st, *P)
         nlen_full = getattr(enc, "nlen_full", None)
         return res, g, (ids, nlen if nlen_full is None else nlen_full, frame_lens, phn_pred_list)
 
@@ -432,7 +270,7 @@ class Force_APTAI(nn.Module):
                 if T not in full:
                     full[T] = torch.full((B,), T, dtype=torch.int32, device=dev)
                 return full[T]
-            c = {"fs_targets": torch.arange(1, N + 1, dtype=torch.int32, device=dev)[None, :].repeat(B, 1).contiguous(),
+            c = {"fs_targets": fwd_sum_targets(B, N, dev),
                  "mono_targets": torch.arange(N, dtype=torch.int32, device=dev)[None, :].repeat(B, 1).contiguous(),
                  "full_T": full_T}
             self._const_cache = dict(getattr(self, "_const_cache", {}))
@@ -467,18 +305,15 @@ class Force_APTAI(nn.Module):
         tv_targets = torch.stack([LA, LP, JA, TTCL, TTCD, TMCL, TMCD, TBCL, TBCD], dim=-1).float()
         labels = phoneme_labels if (self._transcript() == "labels" and _phn_pred_list is None) else None
         res, g, dec = self._run(audio_inputs, audio_lengths, tv_targets, _phn_pred_list, _ac_override, _prefetch_next, labels)
-        loss, tv_loss, align_loss, tvs, frame_phns = res[:5]
+        out = self.task_head.result(res, g, None)
         if _device_outputs:
             # private route of the device-resident evaluation (train_force_aptai._device_eval): the tensors `_run` already holds,
             # no lists and no transfer; the caller folds the checks of `_lists` into its own single read
             ids, nlen, frame_lens, _ = dec
-            return {'loss': loss, 'tv_loss': tv_loss, 'align_loss': align_loss, 'tvs_pred': tvs, 'frame_phns': frame_phns,
-                    'ctc_ids': ids, 'ctc_lens': nlen, 'frame_lens': frame_lens}
+            return dict(out, ctc_ids=ids, ctc_lens=nlen, frame_lens=frame_lens)
         phn_pred_list, frame_seq_lens, _, _ = self._lists(dec)
-        fp = frame_phns.cpu().numpy()                                  # ONE transfer (reference: B*T .cpu() calls)
-        pred_frame_phns = [fp[b, :frame_seq_lens[b]].tolist() for b in range(g.B)]
-        return {'loss': loss, 'tv_loss': tv_loss, 'align_loss': align_loss, 'tvs_pred': tvs,
-                'pred_frame_phns': pred_frame_phns, 'pred_ctc_phn_seq': phn_pred_list}
+        fp = out.pop('frame_phns').cpu().numpy()                       # ONE transfer (reference: B*T .cpu() calls)
+        return dict(out, pred_frame_phns=[fp[b, :frame_seq_lens[b]].tolist() for b in range(g.B)], pred_ctc_phn_seq=phn_pred_list)
 
     def load_state_dict(self, state_dict, *args, **kwargs):
         # the captured encoder passes of prefetch() hold the addresses of the recogniser's bf16 weight copies, which are rebuilt

@@ -29,11 +29,8 @@ from typing import Dict, List, Optional
 import numpy as np
 import torch
 
-from . import _lib, hostlogic, ops
-from .aptai import APTAI, heads_bwd, heads_fwd
-from .w2v2_pr import Wav2Vec2_PR, pr_head_bwd, pr_head_fwd
-from .wav2vec2 import (_APTAI_HEADS_STREAM, _FEATURE_MASK_STREAM, _LAYER_STREAM_BASE, _PR_HEAD_STREAM, _TIME_MASK_STREAM, _FinalLNImpl,
-                       _FrontImpl, _LayerImpl, _seed)
+from . import _lib, ops
+from .wav2vec2 import _FEATURE_MASK_STREAM, _LAYER_STREAM_BASE, _TIME_MASK_STREAM, _FinalLNImpl, _FrontImpl, _LayerImpl, _seed
 
 
 # thread-local capture: under data parallelism the process group's watchdog thread polls its events while this thread captures,
@@ -122,14 +119,13 @@ class GraphedAPTAIStep(_CapturingRunner):
         cfg = self.cfg
         dev = next(model.parameters()).device
         self.dev = dev
-        # two model kinds share the segments: APTAI (regression + frame classification heads, models/aptai.py) and Wav2Vec2_PR
-        # (CTC head, models/w2v2_pr.py).  A trainable feature encoder (the recogniser's fine-tuning,
+        # the models share the segments and differ in their task head (task_heads.py): APTAI (regression + frame classification heads,
+        # models/aptai.py) and Wav2Vec2_PR (CTC head, models/w2v2_pr.py).  A trainable feature encoder (the recogniser's fine-tuning,
         # train/train_phoneme_recognizer.py) adds its backward to the front-backward segment.
-        self.kind = "pr" if isinstance(model, Wav2Vec2_PR) else "aptai"
+        self.head = model.task_head
         self.train_conv = any(p.requires_grad for p in w.feature_extractor.parameters())
         # ---- static inputs
-        audio_key = "input_values" if self.kind == "pr" else "audio_inputs"
-        self.audio = batch[audio_key].float().contiguous().clone()
+        self.audio = batch[self.head.audio_key].float().contiguous().clone()
         B, S = self.audio.shape
         self.g = w._geometry(B, S)
         g = self.g
@@ -142,19 +138,14 @@ class GraphedAPTAIStep(_CapturingRunner):
             ops.feature_mask_span_check(cfg.hidden_size, cfg.mask_feature_prob, cfg.mask_feature_length, cfg.mask_feature_min_masks)
             self.feat = torch.zeros((B, cfg.hidden_size), device=dev, dtype=torch.uint8)
             self.feat_lens = torch.full((B,), cfg.hidden_size, device=dev, dtype=torch.int32)
-        if self.kind == "pr":
-            self.labels = torch.full(tuple(batch["phoneme_labels"].shape), -100, device=dev, dtype=torch.int32)
-            self.state_lens = torch.zeros(B, device=dev, dtype=torch.int32)
-            self.target_lens = torch.zeros(B, device=dev, dtype=torch.int32)
-        else:
-            self.tv_tgt = torch.zeros((B, g.T, model.n_tv), device=dev, dtype=torch.float32)
-            self.phn_tgt = torch.zeros((B, g.T), device=dev, dtype=torch.int64)
+        self.targets = self.head.static_targets(model, g, batch, dev)         # name -> static buffer: the target arguments of head.state
         self._init_capture(dev, 0xC0FFEE + w.base_seed)
         # frame bounds of the batch inside the captured shape (BucketedGraphedStep feeds shorter batches): by default the shape itself
         self.bounds = torch.tensor([g.Tl[0], g.T], device=dev, dtype=torch.int32)
         self._bounds_ring = ops.PinnedRing((self.bounds,), 4)
         self._bounds_host = (g.Tl[0], g.T)
-        self._stage_ring = None                                  # pinned staging of host batches: made on the first one (set_batch)
+        # what head.set_batch writes; ring: pinned staging of host batches, made on the first one
+        self.static = SimpleNamespace(cfg=cfg, g=g, audio=self.audio, lens=self.lens_i32, targets=self.targets, ring=None)
         _bind_bounds(self._cap_stream.cuda_stream, self.bounds)
         self.set_batch(batch)
         # one eager step first: allocates every persistent scratch buffer, loads the code objects and sets the kernel
@@ -162,7 +153,7 @@ class GraphedAPTAIStep(_CapturingRunner):
         if w._cache_mode == "frozen":                            # another runner of this model froze the cache: the eager step rebuilds
             w._cache_mode = None
         model.zero_grad(set_to_none=True)
-        (model(**batch) if self.kind == "pr" else model(0, **batch))["loss"].backward()
+        model(*self.head.forward_args, **batch)["loss"].backward()
         model.zero_grad(set_to_none=True)
         try:
             self._capture()
@@ -171,34 +162,8 @@ class GraphedAPTAIStep(_CapturingRunner):
 
     # ------------------------------------------------------------------ inputs
     def set_batch(self, batch: Dict[str, torch.Tensor]) -> None:
-        """Copies a batch (the collate_fn's dict, host or device tensors) into the static input buffers of the graphs.
-        Host tensors go through a two-slot ring of pinned staging buffers and asynchronous copies on the step's stream:
-        10.7 ms/step against 10.3 with the batch resident (pageable copies, which block the host until the GPU has drained:
-        34 ms/step)."""
-        cfg, g = self.cfg, self.g
-        if self.kind == "pr":
-            return self._set_batch_pr(batch)
-        lens_cpu = batch["audio_lengths"].detach().cpu().long()
-        fl = hostlogic.feat_extract_output_lengths(lens_cpu, cfg.conv_kernel, cfg.conv_stride).clamp(min=1, max=g.T)
-        self.frame_lens_cpu = fl
-        tracks = [batch[k] for k in batch if k not in ("audio_inputs", "audio_lengths", "phn_frames_49hz", "phoneme_labels")]
-        if batch["audio_inputs"].device.type == "cpu":
-            # staging copies through numpy: single-threaded memcpy / cast.  torch's copy_ goes parallel above 32 K elements
-            # and the OpenMP workers then spin on the cores the launching thread needs (host time per step 8 -> 19 ms).
-            if self._stage_ring is None:
-                self._stage_ring = ops.PinnedRing((self.audio, self.lens_i32, self.tv_tgt, self.phn_tgt), 2)
-            audio, lens, tv, phn = self._stage_ring.next()
-            np.copyto(audio, batch["audio_inputs"].detach().numpy(), casting="same_kind")
-            np.copyto(lens, fl.numpy(), casting="same_kind")
-            for j, t in enumerate(tracks):                       # f64 (B, T) tracks -> one (B, T, n_tv) f32 block
-                tv[:, :, j] = t.detach().numpy()
-            np.copyto(phn, batch["phn_frames_49hz"].numpy(), casting="same_kind")
-            self._stage_ring.send()
-            return
-        self.audio.copy_(batch["audio_inputs"].float())
-        self.lens_i32.copy_(fl.to(torch.int32))
-        self.tv_tgt.copy_(torch.stack(tracks, dim=-1).float())
-        self.phn_tgt.copy_(batch["phn_frames_49hz"])
+        """Copies a batch (the collate_fn's dict, host or device tensors) into the static input buffers of the graphs."""
+        self.head.set_batch(self.static, batch)
 
     def set_bounds(self, conv0_frames: int, frames: int) -> None:
         """Frame bounds of the NEXT step's batch inside the captured shape (see aptai_set_frame_bounds): how many first-conv-layer
@@ -210,25 +175,6 @@ class GraphedAPTAIStep(_CapturingRunner):
         buf[0], buf[1] = int(conv0_frames), int(frames)
         self._bounds_ring.send()
         self._bounds_host = (conv0_frames, frames)
-
-    def _set_batch_pr(self, batch: Dict[str, torch.Tensor]) -> None:
-        """Wav2Vec2_PR batch (input_values, input_lengths, phoneme_labels with -100 padding, models/w2v2_pr.py:40-70).  The label
-        block may be narrower than the one the graphs were captured with (padded with -100), never wider."""
-        cfg, g = self.cfg, self.g
-        lens_cpu = batch["input_lengths"].detach().cpu().long().reshape(-1)
-        sl = hostlogic.feat_extract_output_lengths(lens_cpu, cfg.conv_kernel, cfg.conv_stride)
-        self.frame_lens_cpu = sl.clamp(min=1, max=g.T)
-        lab = batch["phoneme_labels"]
-        if lab.shape[0] != self.labels.shape[0] or lab.shape[1] > self.labels.shape[1]:
-            raise ValueError(f"label block {tuple(lab.shape)} does not fit the captured {tuple(self.labels.shape)}")
-        dev = self.dev
-        self.audio.copy_(batch["input_values"].float(), non_blocking=True)
-        self.lens_i32.copy_(self.frame_lens_cpu.to(torch.int32), non_blocking=True)
-        self.state_lens.copy_(sl.to(torch.int32), non_blocking=True)
-        self.target_lens.copy_(hostlogic.ctc_target_lengths(lab).to(torch.int32), non_blocking=True)
-        if lab.shape[1] < self.labels.shape[1]:
-            self.labels.fill_(-100)
-        self.labels[:, :lab.shape[1]].copy_(lab.to(torch.int32), non_blocking=True)
 
     def _host_randomness(self):
         """A fresh salt for the step (the SpecAugment mask is sampled by a kernel inside the front segment from the same salt) and
@@ -307,20 +253,12 @@ class GraphedAPTAIStep(_CapturingRunner):
 
         # -- tail: [final LN] + heads forward + loss + heads backward + [final LN backward]
         self.fin = _FinalLNImpl(cfg, g) if cfg.do_stable_layer_norm else None
-        self.loss_norm = None
-        if self.kind == "pr":
-            self.hparams = [model.pr_head.weight, model.pr_head.bias]
-            self.st_heads = SimpleNamespace(g=g, p_final=model.dropout.p, seed=_seed(seed, _PR_HEAD_STREAM), targets=self.labels,
-                                            state_lens=self.state_lens, target_lens=self.target_lens, blank=getattr(cfg, "blank", 0),
-                                            reduction=cfg.ctc_loss_reduction, zero_infinity=cfg.ctc_zero_infinity)
-        else:
-            self.hparams = [model.tv_head[2].weight, model.tv_head[2].bias, model.phn_head[2].weight, model.phn_head[2].bias]
-            self.st_heads = SimpleNamespace(g=g, p_tv=model.tv_head[0].p, p_ph=model.phn_head[0].p, seed=_seed(seed, _APTAI_HEADS_STREAM),
-                                            taps=model.tv_lowpass.taps(), tv_tgt=self.tv_tgt, phn_tgt=self.phn_tgt, w_mse=0.5, w_ce=0.5)
-            # data parallel: the loss backward inside the tail graph reads the global valid counts / world from this static buffer
-            self.loss_norm = getattr(model, "dp_loss_norm", None)
-            if self.loss_norm is not None:
-                self.st_heads.norm_scalars = self.loss_norm.buffer(self.dev)
+        self.hparams = self.head.params(model)
+        self.st_heads = self.head.state(model, g, (seed,), True, **self.targets)
+        # data parallel: the loss backward inside the tail graph reads the global valid counts / world from this static buffer
+        self.loss_norm = getattr(model, "dp_loss_norm", None) if self.head.global_loss_norm else None
+        if self.loss_norm is not None:
+            self.st_heads.norm_scalars = self.loss_norm.buffer(self.dev)
         # single GPU: the ~24 LayerNorm parameter-gradient reductions of the backward pass (one 4.8 us launch + a kernel boundary each)
         # are collected here and replayed as ONE launch behind the front-end backward; nothing reads them before the optimiser.
         # Data parallel keeps them per call: a layer's gradients leave for the all-reduce right after its segment.
@@ -330,12 +268,8 @@ class GraphedAPTAIStep(_CapturingRunner):
             hl = self.X[L]
             if self.fin is not None:
                 (hl,), s_fin = self.fin.fwd(hl, [w.encoder.layer_norm.weight, w.encoder.layer_norm.bias], True)
-            if self.kind == "pr":
-                self.outs, s_heads = pr_head_fwd(hl, *self.hparams, self.st_heads)
-                dh, *hgrads = pr_head_bwd(s_heads, self.st_heads, None)
-            else:
-                self.outs, s_heads = heads_fwd(hl, *self.hparams, self.st_heads)
-                dh, *hgrads = heads_bwd(s_heads, self.st_heads, None)
+            self.outs, s_heads = self.head.fwd(hl, self.hparams, self.st_heads)
+            dh, *hgrads = self.head.bwd(s_heads, self.st_heads, self.hparams, hl, None)
             fin_grads = []
             if self.fin is not None:
                 dh, fin_grads = self.fin.bwd(s_fin, (dh,), True)
@@ -415,7 +349,7 @@ class GraphedAPTAIStep(_CapturingRunner):
         L = self.cfg.num_hidden_layers
         self.w._train_marker += 1                                # eval-mode weight copies built before this step are stale
         if self.loss_norm is not None:
-            self.loss_norm.begin(self.tv_tgt, self.phn_tgt)      # travels under the encoder forward
+            self.loss_norm.begin(self.st_heads.tv_tgt, self.st_heads.phn_tgt)      # travels under the encoder forward
         # Optimiser under the backward pass (APTAI_ADAM_OVERLAP=1; experiment, OFF by default; single GPU, aptai_amd.optim.Adam): a
         # layer's six weight / bias pairs are updated on a side stream as soon as its backward segment has finished - an HBM-bound
         # launch beside the next layers' matrix-bound ones.  Adam is element-wise per parameter, so WHEN a parameter is updated
@@ -464,13 +398,7 @@ class GraphedAPTAIStep(_CapturingRunner):
             self.opt.finish()
         else:
             self.opt.step()
-        if self.kind == "pr":
-            loss, logits, log_probs, hd = self.outs
-            g, V = self.g, self.hparams[0].shape[0]
-            return {"loss": loss, "phoneme_logits": logits.view(g.B, g.Tp, -1)[:, :g.T, :V], "log_probs": log_probs,
-                    "hidden_states": hd.view(g.B, g.Tp, -1)[:, :g.T]}
-        loss, mse, ce, tvs, pred, _ = self.outs
-        return {"loss": loss, "mse_loss": mse, "ce_loss": ce, "tvs_pred": tvs, "phn_fc_pred": pred}
+        return self.head.result(self.outs, self.g, self.hparams)
 
     def plan_groups(self):
         """[(name, gradient elements)] of the per-segment gradient groups in the order step() hands them to dp.GradGroupReducer
@@ -531,7 +459,7 @@ class BucketedGraphedStep:
         # saved activations and graph pools; a real corpus spans 13 length buckets x several label widths (+ a short last batch), so the
         # cache is bounded: beyond `max_runners` the least recently used runner is closed (its graphs are re-captured if its shape returns).
         self.max_runners, self.log, self.evictions = max(1, int(max_runners)), log, 0
-        self.kind = "pr" if isinstance(model, Wav2Vec2_PR) else "aptai"
+        self.head = model.task_head
         self.buckets = sorted(bucket_samples) if bucket_samples else [16000 * s for s in self.DEFAULT_SECONDS]
         self.label_bucket = label_bucket
         self.runners: Dict[tuple, GraphedAPTAIStep] = {}
@@ -543,34 +471,12 @@ class BucketedGraphedStep:
                 return b
         return -(-S // 16000) * 16000                      # longer than every bucket: whole seconds
 
-    def _padded(self, batch, Sb: int, Tb: int):
-        akey = "input_values" if self.kind == "pr" else "audio_inputs"
-        out = {}
-        for k, v in batch.items():
-            if k == akey:
-                if v.shape[1] < Sb:
-                    v = torch.nn.functional.pad(v, (0, Sb - v.shape[1]))
-            elif k == "phoneme_labels" and self.kind == "pr":
-                wl = -(-v.shape[1] // self.label_bucket) * self.label_bucket
-                if v.shape[1] < wl:
-                    v = torch.nn.functional.pad(v, (0, wl - v.shape[1]), value=-100)
-            elif k in ("audio_lengths", "input_lengths", "phoneme_labels"):
-                pass
-            elif v.dim() == 2 and self.kind == "aptai":            # frame-rate targets (B, T): -100.0 / 0 = the collate's own padding values
-                if v.shape[1] < Tb:
-                    v = torch.nn.functional.pad(v, (0, Tb - v.shape[1]), value=0 if k == "phn_frames_49hz" else -100.0)
-                elif v.shape[1] > Tb:
-                    v = v[:, :Tb]
-            out[k] = v
-        return out
-
     def step(self, batch: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
-        akey = "input_values" if self.kind == "pr" else "audio_inputs"
-        B, S = batch[akey].shape
+        B, S = batch[self.head.audio_key].shape
         Sb = self.bucket_of(S)
         g_s, g_b = self.w._geometry(B, S), self.w._geometry(B, Sb)
-        padded = self._padded(batch, Sb, g_b.T)
-        key = (B, Sb) + ((padded["phoneme_labels"].shape[1],) if self.kind == "pr" else ())
+        padded = self.head.pad_batch(batch, Sb, g_b.T, self.label_bucket)
+        key = (B, Sb) + self.head.cache_key(padded)
         r = self.runners.pop(key, None)
         if r is None:
             while len(self.runners) >= self.max_runners:
@@ -586,13 +492,7 @@ class BucketedGraphedStep:
                          f"{torch.cuda.memory_allocated(dev) / 2 ** 30:.1f} GiB allocated")
         self.runners[key] = r                                   # (re-)inserted last = most recently used
         r.set_bounds(g_s.Tl[0], g_s.T)
-        out = r.step(padded)
-        T = g_s.T
-        if self.kind == "pr":
-            return {"loss": out["loss"], "phoneme_logits": out["phoneme_logits"][:, :T], "log_probs": out["log_probs"][:T],
-                    "hidden_states": out["hidden_states"][:, :T]}
-        return {"loss": out["loss"], "mse_loss": out["mse_loss"], "ce_loss": out["ce_loss"], "tvs_pred": out["tvs_pred"][:, :T],
-                "phn_fc_pred": out["phn_fc_pred"][:, :T]}
+        return self.head.cut(r.step(padded), g_s.T)
 
     def suspend(self) -> None:
         """Before an EAGER phase on the same model (validation between epochs): un-freeze the model's compute-copy cache so that
@@ -621,13 +521,13 @@ class GraphedForceStep(_CapturingRunner):
 
     replayed one batch apart: while the heads of batch n replay on the caller's stream, the encoder of batch n+1 (handed to
     step() as `next_batch`, or the same batch again) replays on the side stream.  Same kernels and the same two Python functions
-    (force_heads_fwd / force_heads_bwd) as the eager autograd path; dropout draws fresh masks per replay through the per-stream
+    (task_heads.ForceHead.fwd / .bwd) as the eager autograd path; dropout draws fresh masks per replay through the per-stream
     salt; nothing synchronises host and device (`lists()` makes the Python lists of the reference's return value on demand).
     The optimiser step is issued eagerly after the heads graph.  The captured heads keep the ARGMAX read-out of `pred_frame_phns`
     whatever `Force_APTAI.alignment_readout` says (the monotonic read-out is an eager-path option)."""
 
     def __init__(self, model, optimizer, batch: Dict[str, torch.Tensor]):
-        from .force_aptai import Force_APTAI, force_heads_bwd, force_heads_fwd
+        from .force_aptai import Force_APTAI
         assert isinstance(model, Force_APTAI) and model.training, "a Force_APTAI model in train() mode"
         if getattr(model, "dp_loss_norm", None) is not None:
             raise NotImplementedError("GraphedForceStep is single-process (the eager step carries the DP loss normalisation)")
@@ -663,13 +563,15 @@ class GraphedForceStep(_CapturingRunner):
         e = self.enc
         self.h_ac, self.h_ids, self.h_nlen, self.h_fl = (torch.empty_like(t) for t in (e.ac, e.ids, e.nlen, e.frame_lens))
         self.h_nfull = torch.empty_like(e.nlen_full)          # the uncut decoded length: what lists() checks
-        self.st, self.P = model._heads_state(g, self.h_ids, self.h_nlen, self.h_fl, self.tv_tgt, 0xF0)
+        self.head = model.task_head
+        self.P = self.head.params(model)
+        self.st = self.head.state(model, g, (w.base_seed, 0xF0), True, self.h_ids, self.h_nlen, self.h_fl, self.tv_tgt)
         self.st.readout = "argmax"
         self.g_heads = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.g_heads, pool=pool, stream=self._cap_stream, capture_error_mode=_CAPTURE_MODE):
             self.st.vocab_sizes = self.h_nlen + 1             # derived from a static input: recomputed on every replay
-            self.outs, saved = force_heads_fwd(self.h_ac, self.st, self.P)
-            self.pgrads = force_heads_bwd(saved, self.st, self.P, self.h_ac, None)
+            self.outs, saved = self.head.fwd(self.h_ac, self.P, self.st)
+            self.pgrads = self.head.bwd(saved, self.st, self.P, self.h_ac, None)[1:]
         torch.cuda.synchronize()
         self._have_enc = False
         self._enc_done = None
@@ -717,9 +619,7 @@ class GraphedForceStep(_CapturingRunner):
             if p.requires_grad:
                 p.grad = gt                                    # (bias_ih / bias_hh of a direction share one gradient buffer)
         self.opt.step()
-        loss, tv_loss, align_loss, tvs, frame_phns = self.outs[:5]
-        return {"loss": loss, "tv_loss": tv_loss, "align_loss": align_loss, "tvs_pred": tvs, "frame_phns": frame_phns,
-                "ids": self.h_ids, "n_ids": self.h_nfull, "frame_lens": self.h_fl}
+        return dict(self.head.result(self.outs, self.g, self.P), ids=self.h_ids, n_ids=self.h_nfull, frame_lens=self.h_fl)
 
     def lists(self, out) -> Dict[str, list]:
         """The Python lists of Force_APTAI.forward (pred_frame_phns, pred_ctc_phn_seq) for a step() result: the only transfers."""

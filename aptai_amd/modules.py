@@ -49,8 +49,8 @@ class LowPassFilterLayer(nn.Module):
 
 
 # ------------------------------------------------------------------------------------- Force_APTAI building blocks
-# Each block works on its own (the reference's `forward` signatures and return values, differentiable, fp32 HIP kernels behind
-# small autograd Functions).  Force_APTAI.forward itself runs the fused chain in force_aptai._ForceHeadsFn over the same kernels.
+# Each block works on its own (the reference's `forward` signatures and return values, differentiable, fp32 HIP kernels behind small autograd
+# Functions); its arithmetic is a plain function with explicit pitches that the fused chain of Force_APTAI.forward (task_heads.ForceHead) calls too.
 def _seed_of(module) -> int:
     """Fresh dropout seed per call of a stand-alone block (forward and backward of one call share it)."""
     module._calls = getattr(module, "_calls", 0) + 1
@@ -72,14 +72,10 @@ class _LinearFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x2, w = ctx.saved_tensors
-        N, K = w.shape
         M = x2.shape[0]
-        dy2 = dy.reshape(-1, N).float().contiguous()
-        wc = w.detach().float().contiguous()
-        dx = ops.sgemm(dy2, N, 1, wc, K, 1, M, K, N).view(ctx.shape)
-        dw = ops.sgemm(dy2, 1, N, x2, K, 1, N, K, M)
-        db = ops.colsum_f32(dy2, M, N) if ctx.has_b else None
-        return dx, dw, db
+        dy2 = dy.reshape(-1, w.shape[0]).float().contiguous()
+        dx = ops.linear_f32_dx(dy2, w.detach().float().contiguous(), M).view(ctx.shape)
+        return (dx,) + ops.linear_f32_dwdb(dy2, x2, M, ctx.has_b)
 
 
 class _LayerNormFn(torch.autograd.Function):
@@ -98,18 +94,37 @@ class _LayerNormFn(torch.autograd.Function):
         return dx.view(ctx.shape), dg, db, None
 
 
+def xatt_core_fwd(q, ldq, k, mask_i32, B, T, N, A, cat, fs_rows=None):
+    """energy = q k^T + mask; att = softmax(energy); cat[:, :A] = att k  (models/modules.py:143-151): ops.xattn_softmax_fwd's result.
+    q: rows of A floats at pitch ldq (dense, or already in place in cat[:, A:]); k [B*N][A]; cat [B*T][2A]."""
+    raw = ops.sgemm(q, ldq, 1, k, 1, A, T, N, A, batch=B, bsa=T * ldq, bsb=N * A, bsc=T * N)
+    sm = ops.xattn_softmax_fwd(raw, mask_i32, B, T, N, fs_rows=fs_rows)
+    ops.sgemm(sm[1], N, 1, k, A, 1, T, A, N, out=cat, ldc=2 * A, batch=B, bsa=T * N, bsb=N * A, bsc=T * 2 * A)
+    return sm
+
+
+def xatt_core_bwd(dcat, q, ldq, k, att, B, T, N, A, d_raw_of):
+    """(dq, dk) from dcat [B*T][2A].  d_raw_of(d_att) -> the gradient of the raw energies (ops.xattn_softmax_bwd with whatever else
+    reaches att_log or the energies); it runs between the two pairs of products."""
+    d_att = ops.sgemm(dcat, 2 * A, 1, k, 1, A, T, N, A, batch=B, bsa=T * 2 * A, bsb=N * A, bsc=T * N)
+    dk = ops.sgemm(att, 1, N, dcat, 2 * A, 1, N, A, T, batch=B, bsa=T * N, bsb=T * 2 * A, bsc=N * A)
+    d_raw = d_raw_of(d_att)
+    dq = dcat[..., A:].contiguous()
+    ops.sgemm(d_raw, N, 1, k, A, 1, T, A, N, out=dq, ldc=A, accumulate=True, batch=B, bsa=T * N, bsb=N * A, bsc=T * A)
+    ops.sgemm(d_raw, 1, N, q, ldq, 1, N, A, T, out=dk, ldc=A, accumulate=True, batch=B, bsa=T * N, bsb=T * ldq, bsc=N * A)
+    return dq, dk
+
+
 class _XattCoreFn(torch.autograd.Function):
-    """energy = q k^T + mask; att = softmax(energy); out = [att k | q]  (models/modules.py:143-151)."""
+    """The cross-attention core on dense q (B,T,A), k (B,N,A): out = [att k | q]."""
 
     @staticmethod
     def forward(ctx, q, k, mask_i32):
         B, T, A = q.shape
         N = k.shape[1]
         qc, kc = q.float().contiguous(), k.float().contiguous()
-        raw = ops.sgemm(qc, A, 1, kc, 1, A, T, N, A, batch=B, bsa=T * A, bsb=N * A, bsc=T * N)
-        energy, att, att_log, _ = ops.xattn_softmax_fwd(raw, mask_i32, B, T, N)
         cat = torch.empty((B, T, 2 * A), device=q.device, dtype=torch.float32)
-        ops.sgemm(att, N, 1, kc, A, 1, T, A, N, out=cat, ldc=2 * A, batch=B, bsa=T * N, bsb=N * A, bsc=T * 2 * A)
+        energy, att, att_log, _ = xatt_core_fwd(qc, A, kc, mask_i32, B, T, N, A, cat)
         cat[:, :, A:] = qc
         ctx.save_for_backward(qc, kc, att, att_log)
         return cat, energy.view(B, T, N)
@@ -119,15 +134,11 @@ class _XattCoreFn(torch.autograd.Function):
         qc, kc, att, att_log = ctx.saved_tensors
         B, T, A = qc.shape
         N = kc.shape[1]
-        dcat = dcat.float().contiguous()
-        d_att = ops.sgemm(dcat, 2 * A, 1, kc, 1, A, T, N, A, batch=B, bsa=T * 2 * A, bsb=N * A, bsc=T * N)
-        dk = ops.sgemm(att, 1, N, dcat, 2 * A, 1, N, A, T, batch=B, bsa=T * N, bsb=T * 2 * A, bsc=N * A)
-        d_raw = ops.xattn_softmax_bwd(att, att_log, d_att, None)
-        if denergy is not None:
-            d_raw = d_raw + denergy.reshape(d_raw.shape).float()
-        dq = dcat[:, :, A:].contiguous()
-        ops.sgemm(d_raw, N, 1, kc, A, 1, T, A, N, out=dq, ldc=A, accumulate=True, batch=B, bsa=T * N, bsb=N * A, bsc=T * A)
-        ops.sgemm(d_raw, 1, N, qc, A, 1, N, A, T, out=dk, ldc=A, accumulate=True, batch=B, bsa=T * N, bsb=T * A, bsc=N * A)
+
+        def d_raw_of(d_att):
+            d_raw = ops.xattn_softmax_bwd(att, att_log, d_att, None)
+            return d_raw if denergy is None else d_raw + denergy.reshape(d_raw.shape).float()
+        dq, dk = xatt_core_bwd(dcat.float().contiguous(), qc, A, kc, att, B, T, N, A, d_raw_of)
         return dq, dk.view(B, N, A), None
 
 
@@ -150,13 +161,21 @@ class CrossAttention(nn.Module):
         return att_out, energy
 
 
+def lstm_whh_grads(dgates, hout, M):
+    """dW_hh[dir] = sum_t dgates[t][dir]^T h_prev[t][dir], forward and reverse (h_prev = previous VISITED frame: t-1 forward, t+1
+    reverse; the rows in between utterances hold zeros in hout / dgates, so one shifted GEMM over all rows is exact).  The rows
+    are in the kernels' gate-interleaved order like dgates' columns: lstm_gate_perm's inverse takes them to torch's gate-major one."""
+    return (ops.sgemm(dgates[1:], 1, 2048, hout, 512, 1, 1024, 256, M - 1),
+            ops.sgemm(dgates[:, 1024:], 1, 2048, hout[1:, 256:], 512, 1, 1024, 256, M - 1))
+
+
 class _LstmCoreFn(torch.autograd.Function):
-    """Bidirectional LSTM recurrence over packed sequences on precomputed input projections (csrc/lstm.hip)."""
+    """Bidirectional LSTM recurrence over packed sequences on precomputed input projections (csrc/lstm.hip); xproj in the kernels'
+    gate-interleaved column order (the caller permuted W_ih's rows)."""
 
     @staticmethod
     def forward(ctx, xproj, whh0, whh1, lens_i32, B, Tp, T):
         whh = torch.stack([whh0.detach(), whh1.detach()]).float().contiguous()
-        need = torch.is_grad_enabled()
         hout, gates, cst = ops.lstm_fwd(xproj.contiguous(), whh, lens_i32, B, Tp, T, save=True)
         ctx.save_for_backward(whh, lens_i32, gates, cst, hout)
         ctx.dims = (B, Tp, T)
@@ -166,13 +185,8 @@ class _LstmCoreFn(torch.autograd.Function):
     def backward(ctx, dhout):
         whh, lens_i32, gates, cst, hout = ctx.saved_tensors
         B, Tp, T = ctx.dims
-        M = B * Tp
         dgates = ops.lstm_bwd(dhout.float().contiguous(), whh, lens_i32, gates, cst, B, Tp, T)
-        # dW_hh[dir] = sum_t dgates[t][dir]^T h_prev[t][dir]: the zero rows between utterances make one shifted product exact
-        dwhh0 = ops.sgemm(dgates[1:], 1, 2048, hout, 512, 1, 1024, 256, M - 1)
-        dwhh1 = ops.sgemm(dgates[:, 1024:], 1, 2048, hout[1:, 256:], 512, 1, 1024, 256, M - 1)
-        # dgates is in the kernels' gate-interleaved column order, like xproj (the caller permuted W_ih's rows): the rows of the two
-        # products come out in that order and go back to weight_hh's gate-major one
+        dwhh0, dwhh1 = lstm_whh_grads(dgates, hout, B * Tp)
         inv = ops.lstm_gate_perm(dgates.device)[1][:1024]
         return dgates, dwhh0[inv], dwhh1[inv], None, None, None, None
 
@@ -210,7 +224,7 @@ class RNN(nn.Module):
         dev = embeddings.device
         lens_l = [int(v) for v in (lens.tolist() if torch.is_tensor(lens) else lens)]
         run_lens = [T] if B == 1 else lens_l
-        Tp = T + 1                                          # one zero row between utterances (see _LstmCoreFn.backward)
+        Tp = T + 1                                          # one zero row between utterances (see lstm_whh_grads)
         xp = torch.zeros((B, Tp, D), device=dev, dtype=torch.float32)
         xp[:, :T] = embeddings
         l = self.lstm
@@ -266,28 +280,38 @@ class PositionalEncoding(nn.Module):
         return _PeFn.apply(x, self.pe, self.dropout.p if self.training else 0.0, _seed_of(self))
 
 
+def fwd_sum_targets(B, N, dev):
+    """The monotonic CTC targets 1..N of every utterance, int32 [B][N]."""
+    return torch.arange(1, N + 1, dtype=torch.int32, device=dev)[None, :].repeat(B, 1).contiguous()
+
+
+def fwd_sum_ctc(rows, rows_per_b, targets, frame_lens, text_lens, vocab_sizes, B, T, N, grad=None):
+    """The forward-sum loss: CTC over rows [blank | att_log | zeros] at pitch rows.shape[1] (ops.fs_row_pitch), each utterance's softmax
+    over its own text_len + 1 classes.  ops.ctc_fwd's (loss, nll, None, workspace); with grad = (workspace, nll, dLoss) the fp32
+    gradient of the rows at the same pitch (att_log's share: columns 1..N)."""
+    args = (rows, rows.shape[1], rows_per_b, targets, frame_lens, text_lens, B, T, N + 1)
+    kw = dict(blank=0, reduction="mean", zero_infinity=True, vocab_sizes_i32=vocab_sizes)
+    if grad is None:
+        return ops.ctc_fwd(*args, want_log_probs=False, **kw)
+    return ops.ctc_bwd(*args, *grad, ldd=rows.shape[1], out_dtype=torch.float32, **kw)
+
+
 class _FwdSumFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, att, text_lens_i32, mel_lens_i32, blank_logprob):
         B, _, T, N = att.shape
-        dev = att.device
-        ld = ops.fs_row_pitch(N)                               # [blank | att | zeros] at the pitch the CTC kernels read the rows with
-        rows = torch.zeros((B * T, ld), device=dev, dtype=torch.float32)
+        rows = torch.zeros((B * T, ops.fs_row_pitch(N)), device=att.device, dtype=torch.float32)
         rows[:, 0] = blank_logprob
         rows[:, 1:1 + N] = att.reshape(B * T, N)
-        targets = torch.arange(1, N + 1, dtype=torch.int32, device=dev)[None, :].repeat(B, 1).contiguous()
-        vs = (text_lens_i32 + 1).contiguous()
-        loss, nll, _, ws = ops.ctc_fwd(rows, ld, T, targets, mel_lens_i32, text_lens_i32, B, T, N + 1, blank=0, reduction="mean",
-                                       zero_infinity=True, vocab_sizes_i32=vs, want_log_probs=False)
-        ctx.saved = (rows, targets, mel_lens_i32, text_lens_i32, vs, ws, nll, (B, T, N))
+        ctx.fs = (rows, T, fwd_sum_targets(B, N, att.device), mel_lens_i32, text_lens_i32, (text_lens_i32 + 1).contiguous(), B, T, N)
+        loss, ctx.nll, _, ctx.ws = fwd_sum_ctc(*ctx.fs)
+        ctx.dims = (B, T, N)
         return loss.reshape(())
 
     @staticmethod
     def backward(ctx, g):
-        rows, targets, mel, txt, vs, ws, nll, (B, T, N) = ctx.saved
-        ld = rows.shape[1]
-        d = ops.ctc_bwd(rows, ld, T, targets, mel, txt, B, T, N + 1, ws, nll, g.float().reshape(1).contiguous(), blank=0, reduction="mean",
-                        zero_infinity=True, vocab_sizes_i32=vs, ldd=ld, out_dtype=torch.float32)
+        B, T, N = ctx.dims
+        d = fwd_sum_ctc(*ctx.fs, grad=(ctx.ws, ctx.nll, g.float().reshape(1).contiguous()))
         return d[:, 1:1 + N].reshape(B, 1, T, N), None, None, None
 
 

@@ -1281,6 +1281,18 @@ def linear_f32(x, w, bias=None, *, rows=None, out=None, ldc=None, ldx=None):
     return sgemm(x, ldx if ldx else x.stride(0), 1, w, 1, K, M, N, K, out=out, ldc=ldc, bias=bias)
 
 
+def linear_f32_dx(dy, w, M):
+    """dx [M][K] = dy [M][N] W [N][K] of linear_f32."""
+    N, K = w.shape
+    return sgemm(dy, N, 1, w, K, 1, M, K, N)
+
+
+def linear_f32_dwdb(dy, x, M, bias=True):
+    """(dW [N][K], db [N] | None) of linear_f32 from dense fp32 dy [M][N], x [M][K]."""
+    N, K = dy.shape[1], x.shape[1]
+    return sgemm(dy, 1, N, x, K, 1, N, K, M), colsum_f32(dy, M, N) if bias else None
+
+
 def embed_pe_fwd(ids_i32, emb, pe, N, p, seed):
     rows, D = ids_i32.numel(), emb.shape[1]
     out = torch.empty((rows, D), device=emb.device, dtype=torch.float32)

@@ -20,64 +20,13 @@ beams, and through ``decode_nbest`` / ``predict_nbest`` n-best lists with per-to
 """
 from __future__ import annotations
 
-from types import SimpleNamespace
-
 import numpy as np
 import torch
 import torch.nn as nn
 
-from . import hostlogic, ops
+from . import hostlogic, ops, task_heads
 from .modules import _LinearFn
-from .wav2vec2 import _PR_HEAD_STREAM, Wav2Vec2Model, _round_up, _seed, batch_invariant_scope
-
-
-def pr_head_fwd(h, w, b, st):
-    """dropout -> Linear(H, V) -> log_softmax -> CTC (models/w2v2_pr.py:54-81).  Returns ((loss, logits, log_probs, hd), saved)."""
-    g, M, H = st.g, st.g.M, h.shape[1]
-    dev = h.device
-    V = w.shape[0]
-    Np = _round_up(V, 64)
-    hd = ops.dropout(h, st.p_final, st.seed) if st.p_final > 0 else h
-    wp = torch.zeros((Np, H), device=dev, dtype=torch.bfloat16)
-    ops.cast_bf16(w.detach(), wp[:V])
-    bp = torch.zeros(Np, device=dev, dtype=torch.float32)
-    bp[:V] = b.detach()
-    logits = ops.gemm(hd, wp, M, Np, H, bias=bp, out_f32=True)
-    loss, nll, lp, alpha = ops.ctc_fwd(logits, Np, g.Tp, st.targets, st.state_lens, st.target_lens, g.B, g.T, V,
-                                       blank=st.blank, reduction=st.reduction, zero_infinity=st.zero_infinity)
-    return (loss.reshape(()), logits, lp, hd), SimpleNamespace(hd=hd, wp=wp, logits=logits, alpha=alpha, nll=nll, V=V, Np=Np)
-
-
-def pr_head_bwd(s, st, gloss):
-    """Fused CTC gradient -> (dh, dW, db) of the head; gloss = dLoss (None = 1)."""
-    g, M, H = st.g, st.g.M, s.hd.shape[1]
-    gl = torch.ones(1, device=s.hd.device, dtype=torch.float32) if gloss is None else gloss.float().reshape(1).contiguous()
-    dlog = ops.ctc_bwd(s.logits, s.Np, g.Tp, st.targets, st.state_lens, st.target_lens, g.B, g.T, s.V, s.alpha, s.nll, gl,
-                       blank=st.blank, reduction=st.reduction, zero_infinity=st.zero_infinity, ldd=s.Np)
-    dh = ops.gemm(dlog, s.wp, M, H, s.Np, b_kmajor=True)
-    sk = max(1, min(16, M // 1024))
-    dw = ops.gemm(dlog, s.hd, s.Np, H, M, a_kmajor=True, b_kmajor=True, out_f32=True, split_k=sk)
-    db = ops.colsum(dlog, M, s.Np)
-    if st.p_final > 0:
-        dh = ops.dropout(dh, st.p_final, st.seed)
-    return dh, dw[:s.V], db[:s.V]
-
-
-class _CtcHeadFn(torch.autograd.Function):
-    """pr_head_fwd / pr_head_bwd behind autograd (the eager drop-in path)."""
-
-    @staticmethod
-    def forward(ctx, h, w, b, st):
-        outs, saved = pr_head_fwd(h, w, b, st)
-        ctx.st, ctx.saved = st, saved
-        ctx.mark_non_differentiable(*outs[1:])
-        return outs
-
-    @staticmethod
-    def backward(ctx, gloss, *_):
-        dh, dw, db = pr_head_bwd(ctx.saved, ctx.st, gloss)
-        ctx.saved = None
-        return dh, dw, db, None
+from .wav2vec2 import Wav2Vec2Model, _round_up, batch_invariant_scope
 
 
 class Wav2Vec2_PR(nn.Module):
@@ -87,6 +36,7 @@ class Wav2Vec2_PR(nn.Module):
     # utterance gets at batch size 1 - Wav2Vec2Model.batch_invariant for the encoder, and every decoder stops at each row's
     # own last frame.  Training-mode forwards are what they were.
     batch_invariant = False
+    task_head = task_heads.CtcHead()         # everything after the encoder, for this class and the graph runners (task_heads.py)
 
     def __init__(self, pretrain_cfg, cache_dir, huggingface_model_id, vocab):
         super().__init__()
@@ -104,23 +54,13 @@ class Wav2Vec2_PR(nn.Module):
     def forward(self, input_values, input_lengths, phoneme_labels):
         """A row with fewer frames than its labels need (speed perturbation shortens the audio, not the transcript) has an infinite
         CTC loss; with `ctc_zero_infinity` (the training loop sets it) it counts as zero, loss and gradient."""
-        cfg = self.wav2vec2.config
         with batch_invariant_scope(self.wav2vec2, self.batch_invariant and not self.training):
             outputs = self.wav2vec2(input_values, attention_mask=input_lengths[:, None], return_dict=True, output_hidden_states=True)
-        g = outputs._geom
-        dev = outputs._flat_last.device
-        state_lens = self.wav2vec2._get_feat_extract_output_lengths(input_lengths)
-        target_lengths = hostlogic.ctc_target_lengths(phoneme_labels)          # count of labels >= 0 (:62-70)
-        st = SimpleNamespace(g=g, p_final=self.dropout.p if self.training else 0.0,
-                             seed=_seed(self.wav2vec2.base_seed, self.wav2vec2._step, _PR_HEAD_STREAM),
-                             targets=phoneme_labels.to(dev).to(torch.int32).contiguous(),
-                             state_lens=state_lens.to(dev).to(torch.int32).contiguous(),
-                             target_lens=target_lengths.to(dev).to(torch.int32).contiguous(), blank=getattr(cfg, "blank", 0),
-                             reduction=cfg.ctc_loss_reduction, zero_infinity=cfg.ctc_zero_infinity)
-        loss, logits, log_probs, hd = _CtcHeadFn.apply(outputs._flat_last, self.pr_head.weight, self.pr_head.bias, st)
-        V = self.pr_head.weight.shape[0]
-        return {'loss': loss, 'phoneme_logits': logits.view(g.B, g.Tp, -1)[:, :g.T, :V], 'log_probs': log_probs,
-                'hidden_states': hd.view(g.B, g.Tp, -1)[:, :g.T]}
+        w, head = self.wav2vec2, self.task_head
+        st = head.state(self, outputs._geom, (w.base_seed, w._step), self.training, phoneme_labels,              # lengths as models/w2v2_pr.py:62-70
+                        w._get_feat_extract_output_lengths(input_lengths), hostlogic.ctc_target_lengths(phoneme_labels))
+        params = head.params(self)
+        return head.result(task_heads.HeadFn.apply(head, outputs._flat_last, st, *params), outputs._geom, params)
 
     # ------------------------------------------------------------------ inference helpers
     def _logits_eval(self, audio_inputs, audio_lengths):
@@ -132,12 +72,6 @@ class Wav2Vec2_PR(nn.Module):
         V, H = self.pr_head.weight.shape
         Np = _round_up(V, 64)
 
-        def build():
-            wp = torch.zeros((Np, H), device=h.device, dtype=torch.bfloat16)
-            ops.cast_bf16(self.pr_head.weight.detach(), wp[:V])
-            bp = torch.zeros(Np, device=h.device, dtype=torch.float32)
-            bp[:V] = self.pr_head.bias.detach()
-            return wp, bp
         # padded bf16 head weight: rebuilt only when the parameters moved (eval mode trusts Tensor._version, see _cached)
         h32 = out._flat_last_f32
         if h32 is not None and self.wav2vec2.encoder_precision in ("f32x3", "f32x6"):
@@ -153,7 +87,8 @@ class Wav2Vec2_PR(nn.Module):
             full = ops.linear_f32(h32, w32, b32)
             out._logits_full = full
             return out, full.view(g.B, g.Tp, Np)[:, :g.T, :V]
-        wp, bp = self.wav2vec2._cached(("pr_head_eval",), [self.pr_head.weight, self.pr_head.bias], build)
+        wp, bp = self.wav2vec2._cached(("pr_head_eval",), [self.pr_head.weight, self.pr_head.bias],
+                                       lambda: task_heads.padded_head_weight(self.pr_head.weight, self.pr_head.bias, Np))
         full = ops.gemm(h, wp, g.M, Np, H, bias=bp, out_f32=True)
         out._logits_full = full                                   # [B*Tp][Np] fp32: what the device decode reads
         return out, full.view(g.B, g.Tp, Np)[:, :g.T, :V]

@@ -6,7 +6,6 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import argparse
 import torch
 import bench
-from aptai_amd import force_aptai as fa
 from aptai_amd.optim import Adam
 
 
@@ -34,7 +33,6 @@ def main():
     def enc(*a, **k):
         mark("enc_begin"); r = enc0(*a, **k); mark("enc_end"); return r
     model._encode = enc
-    apply0 = fa._ForceHeadsFn.apply
     nxt = (batch["audio_inputs"], batch["audio_lengths"])
     pipelined = os.environ.get("PIPE", "1") == "1"
     for i in range(8):
