@@ -42,8 +42,112 @@ def labels_to_slots(labels, cap):
     return ids.contiguous(), valid.sum(dim=1).to(torch.int32)
 
 
+class EncoderAhead:
+    """The frozen recogniser's pass (`Force_APTAI._encode`) one batch ahead on a side stream: the ONE owner of that stream, of the captured
+    passes and of the hand-over, for the eager loop (`Force_APTAI.prefetch`) and for `GraphedForceStep`.  The recogniser is frozen and runs
+    in eval mode, so WHEN it runs changes no result; beside the heads of batch n, the pass of batch n+1 fills the CUs the cooperating LSTM
+    kernels (32 workgroups for 3.5 ms) leave idle.  Each step still does one encoder pass and one heads pass.  From the second launch of a
+    batch shape on the pass is ONE hipGraph launch (no trainable state, no host-dependent control flow): the step was otherwise bound by the
+    host's ~350 launches.  The hand-over rule: take() copies graph-owned outputs out on the CONSUMER stream, and every launch() begins with
+    "the side stream waits for the current stream" - so a caller that takes and launches from one stream never has an output overwritten
+    under a copy."""
+    tensors = ("ac", "ids", "nlen", "frame_lens", "nlen_full")         # what `_encode` hands the heads, in the order of take(into=)
+
+    def __init__(self, model):
+        self.model = model
+        self.stream = None             # the side stream, made at the first launch or capture
+        self.entries = {}              # (shapes, dtypes, encoder precision) -> captured pass; None: its capture failed, stay eager
+        self.captures = 0
+        self._seen = set()             # keys that have run eagerly once: captured at the next sight
+        self._launches = self._valid_from = 0
+
+    def _key(self, audio, lengths):
+        return (tuple(audio.shape), tuple(lengths.shape), audio.dtype, lengths.dtype, self.model.w2v2_pr.wav2vec2.encoder_precision)
+
+    def capture(self, audio, lengths):
+        """The captured pass for this batch shape, captured NOW if there is none (an eager pass with this shape has already run:
+        weight copies and scratch buffers exist).  Raises if the capture fails."""
+        key, w = self._key(audio, lengths), self.model.w2v2_pr.wav2vec2
+        e = self.entries.get(key)
+        if e is not None:
+            return e
+        if self.stream is None:
+            self.stream = torch.cuda.Stream(device=audio.device)
+        e = SimpleNamespace(audio=audio.clone(), lengths=lengths.clone(), graph=torch.cuda.CUDAGraph(), out=None, last=0)
+        step0 = w._step
+        torch.cuda.synchronize(audio.device)
+        # APTAI_FORCE_ENC_TILE forces one GEMM tile in the side-stream pass.  128-row tiles were the default while whole-CU workgroups kept the
+        # heads' BiLSTM clusters waiting (12 % of the step).  Since the cluster kernels hold their compute units alone (csrc/lstm.hip, APTAI_LSTM_LDS_KB)
+        # the dispatcher's own rule is the faster one again: 6.36 ms with 128, 6.09 ms with 0, 6.63 ms with 192 (interleaved, one box).
+        with torch.cuda.graph(e.graph, stream=self.stream, capture_error_mode=ops.CAPTURE_MODE), \
+                ops.auto_tile(int(os.environ.get("APTAI_FORCE_ENC_TILE", "0"))):
+            e.out = self.model._encode(e.audio, e.lengths)
+        w._step = step0                                                # capturing issued nothing
+        self.entries[key] = e
+        self.captures += 1
+        return e
+
+    def launch(self, audio, lengths):
+        """Starts the pass for (audio, lengths) on the side stream; returns the handle take() turns into `_encode`'s result.  A
+        replay of the shape's captured pass, or eager launches: at the first sight of a shape, with APTAI_FORCE_ENC_GRAPH=0, in
+        batch-invariant evaluation (the captured pass is a training device) and after a capture that failed."""
+        m, w, dev = self.model, self.model.w2v2_pr.wav2vec2, self.model.frame_lin.weight.device       # (a replay takes a host batch too)
+        if self.stream is None:
+            self.stream = torch.cuda.Stream(device=dev)
+        self.stream.wait_stream(torch.cuda.current_stream(dev))        # the inputs, the previous step's frees, the copies of take()
+        key = self._key(audio, lengths)
+        graphs = os.environ.get("APTAI_FORCE_ENC_GRAPH", "1") != "0" and not (m.batch_invariant and not m.training)
+        self._launches += 1
+        with torch.cuda.stream(self.stream):
+            e = self.entries.get(key) if graphs else None
+            if e is None and graphs and key in self._seen and key not in self.entries:
+                try:
+                    e = self.capture(audio, lengths)
+                except Exception as exc:                               # noqa: BLE001 - keep training, eagerly
+                    import warnings
+                    warnings.warn(f"Force_APTAI: encoder hipGraph capture failed ({exc!r}); the pass ahead stays eager")
+                    torch.cuda.synchronize(dev)
+                    self.entries[key] = None
+            if e is not None:
+                e.audio.copy_(audio, non_blocking=True)
+                e.lengths.copy_(lengths, non_blocking=True)
+                e.graph.replay()
+                w._step += 1                                           # what the eager pass does on the host
+                e.last, out = self._launches, e.out
+            else:
+                out = m._encode(audio, lengths)
+                self._seen.add(key)
+            event = self.stream.record_event()
+        return SimpleNamespace(out=out, entry=e, n=self._launches, step=w._step, event=event)
+
+    def take(self, handle, into=None):
+        """`_encode`'s result for a launch, ready on the CURRENT stream: its tensors copied into `into` (static tensors in the order
+        of `tensors`), into fresh tensors when a graph owns them, or handed over as they are.  None when the handle no longer
+        holds its result: invalidated since, or its captured pass replayed again."""
+        e, o = handle.entry, handle.out
+        if handle.n <= self._valid_from or (e is not None and e.last != handle.n):
+            return None
+        cur = torch.cuda.current_stream(o.ac.device)
+        cur.wait_event(handle.event)
+        ts = [getattr(o, k) for k in self.tensors]
+        if e is None:
+            for t in ts:                                               # allocated on the side stream, consumed on this one
+                t.record_stream(cur)
+        if e is not None or into is not None:
+            into = into if into is not None else [torch.empty_like(t) for t in ts]
+            for d, t in zip(into, ts):
+                d.copy_(t, non_blocking=True)
+            ts = into
+        return SimpleNamespace(g=o.g, step=handle.step, **dict(zip(self.tensors, ts)))
+
+    def invalidate(self):
+        """Drops every captured pass and every pending hand-over: the captured passes hold the addresses of the recogniser's
+        compute copies (bf16 weights, layer copies, the eval head), which are rebuilt as new tensors when the parameters change."""
+        self.entries, self._seen, self._valid_from = {}, set(), self._launches
+
+
 class Force_APTAI(nn.Module):
-    task_head = task_heads.ForceHead()       # everything after the frozen encoder, for this class and GraphedForceStep (task_heads.py)
+    task_head = task_heads.ForceHead()      # everything after the frozen encoder, for this class and GraphedForceStep (task_heads.py)
 
     def __init__(self, pr_model_path, device, vocab, max_phn_seq_len=_NPHN):
         super().__init__()
@@ -86,9 +190,7 @@ class Force_APTAI(nn.Module):
         # the frozen recogniser only ever runs forward here: keep its residual stream in fp32 and hand the heads an fp32 last hidden
         # state (+1.6 % step time, smaller bf16 noise band on the alignment indices; "bf16" restores the plain bf16 stream)
         self.w2v2_pr.wav2vec2.set_encoder_precision("bf16_f32res")
-        self._enc_stream = None        # side stream of prefetch()
-        self._enc_graphs = {}          # batch shape -> captured encoder pass
-        self._enc_seen = {}
+        self.encoder_ahead = EncoderAhead(self)      # the recogniser's pass one batch ahead: prefetch() here, GraphedForceStep
         self._prefetched = None
 
     # how `pred_frame_phns` is read out of the attention: "argmax" (the reference, models/force_aptai.py:148: per-frame argmax, may
@@ -158,75 +260,15 @@ class Force_APTAI(nn.Module):
         return ids, n.clamp(max=self.max_phn_seq_len - 1), n
 
     def prefetch(self, audio_inputs, audio_lengths):
-        """Run the frozen recogniser for a batch on a side stream NOW; the next forward / _run called with these same tensors
-        picks the result up instead of encoding inline.  The recogniser is frozen and runs in eval mode, so WHEN it runs does
-        not change any result; running it for batch n+1 beside the heads of batch n fills the CUs the cooperating LSTM
-        kernels (32 workgroups for 3.5 ms) leave idle.  Each step still does one encoder pass and one heads pass.
-        From the second call with a given batch shape on, the pass is ONE hipGraph launch (the recogniser has no trainable
-        state and no host-dependent control flow): the step was otherwise bound by the host's ~350 launches."""
-        dev = audio_inputs.device
-        if self._enc_stream is None:
-            self._enc_stream = torch.cuda.Stream(device=dev)
-        cur = torch.cuda.current_stream(dev)
-        self._enc_stream.wait_stream(cur)                              # the inputs (and the previous step's frees) are ordered first
-        key = (tuple(audio_inputs.shape), tuple(audio_lengths.shape), audio_inputs.dtype, audio_lengths.dtype,
-               self.w2v2_pr.wav2vec2.encoder_precision)
-        use_graph = os.environ.get("APTAI_FORCE_ENC_GRAPH", "1") != "0"
-        if self.batch_invariant and not self.training:
-            use_graph = False                                          # the captured pass is a training device: batch-invariant evaluation encodes eagerly
-        with torch.cuda.stream(self._enc_stream):
-            ge = self._enc_graphs.get(key) if use_graph else None
-            if ge is None and use_graph and self._enc_seen.get(key, 0) >= 1:
-                ge = self._capture_encoder(key, audio_inputs, audio_lengths)
-            if ge is not None:
-                ge.audio.copy_(audio_inputs, non_blocking=True)
-                ge.lengths.copy_(audio_lengths, non_blocking=True)
-                ge.graph.replay()
-                self.w2v2_pr.wav2vec2._step += 1                       # what the eager pass does on the host
-                o = ge.out
-                # the graph's outputs are overwritten by the next replay: hand out copies (13 MB, 4 us)
-                enc = SimpleNamespace(g=o.g, ac=o.ac.clone(), ids=o.ids.clone(), nlen=o.nlen.clone(), frame_lens=o.frame_lens.clone(),
-                                      nlen_full=o.nlen_full.clone(), step=self.w2v2_pr.wav2vec2._step)
-            else:
-                enc = self._encode(audio_inputs, audio_lengths)
-                self._enc_seen[key] = self._enc_seen.get(key, 0) + 1
-            enc.event = torch.cuda.Event()
-            enc.event.record(self._enc_stream)
-        self._prefetched = (audio_inputs, audio_lengths, enc)
-
-    def _capture_encoder(self, key, audio_inputs, audio_lengths):
-        """hipGraph of _encode for one batch shape, captured on the side stream (an eager pass with this shape has already run:
-        weight copies and scratch buffers exist).  Falls back to eager launches if the capture fails."""
-        ge = SimpleNamespace(audio=audio_inputs.clone(), lengths=audio_lengths.clone(), graph=torch.cuda.CUDAGraph(), out=None)
-        try:
-            step0 = self.w2v2_pr.wav2vec2._step
-            torch.cuda.synchronize(audio_inputs.device)
-            # thread-local capture: under data parallelism the process group's watchdog thread polls its events meanwhile
-            # (APTAI_FORCE_ENC_TILE forces one GEMM tile in the side-stream pass - ops.auto_tile; default 0 = the dispatcher's rule, see aptai_amd/graphed.py)
-            with torch.cuda.graph(ge.graph, stream=self._enc_stream, capture_error_mode="thread_local"), \
-                    ops.auto_tile(int(os.environ.get("APTAI_FORCE_ENC_TILE", "0"))):
-                ge.out = self._encode(ge.audio, ge.lengths)
-            self.w2v2_pr.wav2vec2._step = step0                        # capturing issued nothing
-        except Exception as e:                                         # noqa: BLE001 - keep training, eagerly
-            import warnings
-            warnings.warn(f"Force_APTAI: encoder hipGraph capture failed ({e!r}); the prefetch stays eager")
-            torch.cuda.synchronize(audio_inputs.device)
-            self._enc_graphs[key] = None
-            self._enc_seen[key] = -(1 << 30)
-            return None
-        self._enc_graphs[key] = ge
-        return ge
+        """Run the frozen recogniser for a batch on a side stream NOW (EncoderAhead.launch); the next forward / _run called with
+        these same tensors picks the result up instead of encoding inline."""
+        self._prefetched = (audio_inputs, audio_lengths, self.encoder_ahead.launch(audio_inputs, audio_lengths))
 
     def _take_prefetched(self, audio_inputs, audio_lengths):
         pf, self._prefetched = self._prefetched, None
         if pf is None or pf[0] is not audio_inputs or pf[1] is not audio_lengths:
             return None
-        enc = pf[2]
-        cur = torch.cuda.current_stream(audio_inputs.device)
-        cur.wait_event(enc.event)
-        for t in (enc.ac, enc.ids, enc.nlen, enc.nlen_full, enc.frame_lens):      # allocated on the side stream, consumed on this one
-            t.record_stream(cur)
-        return enc
+        return self.encoder_ahead.take(pf[2])
 
     def _heads_state(self, g, ids, nlen, frame_lens, tv_targets, step):
         """(st, P) of the task head for one encoded batch: its state and the named parameters (task_heads.ForceParams)."""
@@ -316,9 +358,7 @@ class Force_APTAI(nn.Module):
         return dict(out, pred_frame_phns=[fp[b, :frame_seq_lens[b]].tolist() for b in range(g.B)], pred_ctc_phn_seq=phn_pred_list)
 
     def load_state_dict(self, state_dict, *args, **kwargs):
-        # the captured encoder passes of prefetch() hold the addresses of the recogniser's bf16 weight copies, which are rebuilt
-        # when the parameters change: drop the graphs (they are re-captured on the next prefetches)
-        self._enc_graphs, self._enc_seen, self._prefetched = {}, {}, None
+        self.encoder_ahead.invalidate()
         # `pe_phn.pe` is a pure function of (max_phn_seq_len, width) whose rows do not depend on the row count: a checkpoint written
         # at another max_phn_seq_len loads, and this module keeps its own table
         pe, own = state_dict.get("pe_phn.pe"), self.pe_phn.pe

@@ -33,10 +33,6 @@ from . import _lib, ops
 from .wav2vec2 import _FEATURE_MASK_STREAM, _LAYER_STREAM_BASE, _TIME_MASK_STREAM, _FinalLNImpl, _FrontImpl, _LayerImpl, _seed
 
 
-# thread-local capture: under data parallelism the process group's watchdog thread polls its events while this thread captures,
-# and in the default "global" mode a call from ANY thread can invalidate the capture
-_CAPTURE_MODE = "thread_local"
-
 # stream handle -> the device tensor whose two words that stream's kernels XOR into their dropout seeds (kept alive here for
 # as long as the library holds the pointer)
 _SALTS: Dict[int, torch.Tensor] = {}
@@ -212,7 +208,7 @@ class GraphedAPTAIStep(_CapturingRunner):
             w._conv_weights()                                # frozen feature encoder: its bf16 weight copies are built once, here
             torch.cuda.synchronize()
         self.g_prep = mk()
-        with torch.cuda.graph(self.g_prep, pool=pool, stream=self._cap_stream, capture_error_mode=_CAPTURE_MODE):
+        with torch.cuda.graph(self.g_prep, pool=pool, stream=self._cap_stream, capture_error_mode=ops.CAPTURE_MODE):
             if self.train_conv:
                 w._conv_weights()
             if not getattr(self.opt, "publishes_copies", False):     # else the optimiser kernel refreshes the copies itself
@@ -228,7 +224,7 @@ class GraphedAPTAIStep(_CapturingRunner):
         self.front = _FrontImpl(cfg, g, self.lens_i32, self.spec if embed is not None else None, True, _seed(seed, 1), w,
                                 feat=self.feat)
         self.g_front = mk()
-        with torch.cuda.graph(self.g_front, pool=pool, stream=self._cap_stream, capture_error_mode=_CAPTURE_MODE):
+        with torch.cuda.graph(self.g_front, pool=pool, stream=self._cap_stream, capture_error_mode=ops.CAPTURE_MODE):
             if embed is not None and cfg.apply_spec_augment and cfg.mask_time_prob > 0:
                 ops.spec_augment_mask(self.lens_i32, g.B, g.T, cfg.mask_time_prob, cfg.mask_time_length, cfg.mask_time_min_masks,
                                       _seed(seed, _TIME_MASK_STREAM), out=self.spec)        # fresh spans on every replay (salted seed)
@@ -246,7 +242,7 @@ class GraphedAPTAIStep(_CapturingRunner):
             impl = _LayerImpl(cfg, g, self.lens_i32, wt, True, _seed(seed, _LAYER_STREAM_BASE + i))
             params = w._layer_ln_params(i) + lin
             gr = mk()
-            with torch.cuda.graph(gr, pool=pool, stream=self._cap_stream, capture_error_mode=_CAPTURE_MODE):
+            with torch.cuda.graph(gr, pool=pool, stream=self._cap_stream, capture_error_mode=ops.CAPTURE_MODE):
                 (y,), s = impl.fwd(self.X[i], params, True)
             self.impl.append(impl); self.s_layer.append(s); self.g_fwd.append(gr); self.lparams.append(params)
             self.X.append(y)
@@ -264,7 +260,7 @@ class GraphedAPTAIStep(_CapturingRunner):
         # Data parallel keeps them per call: a layer's gradients leave for the all-reduce right after its segment.
         self._ln_jobs = ops.ln_defer_begin() if (self.group_reducer is None and os.environ.get("APTAI_LN_DEFER", "1") != "0") else None
         self.g_tail = mk()
-        with torch.cuda.graph(self.g_tail, pool=pool, stream=self._cap_stream, capture_error_mode=_CAPTURE_MODE):
+        with torch.cuda.graph(self.g_tail, pool=pool, stream=self._cap_stream, capture_error_mode=ops.CAPTURE_MODE):
             hl = self.X[L]
             if self.fin is not None:
                 (hl,), s_fin = self.fin.fwd(hl, [w.encoder.layer_norm.weight, w.encoder.layer_norm.bias], True)
@@ -286,7 +282,7 @@ class GraphedAPTAIStep(_CapturingRunner):
         self.layer_grads = [None] * L
         for i in range(L - 1, -1, -1):
             gr = mk()
-            with torch.cuda.graph(gr, pool=pool, stream=self._cap_stream, capture_error_mode=_CAPTURE_MODE):
+            with torch.cuda.graph(gr, pool=pool, stream=self._cap_stream, capture_error_mode=ops.CAPTURE_MODE):
                 dx, pg = self.impl[i].bwd(self.s_layer[i], (self.dX[i + 1],), True)
             self.g_bwd[i] = gr
             self.dX[i] = dx
@@ -294,7 +290,7 @@ class GraphedAPTAIStep(_CapturingRunner):
 
         # -- front backward
         self.g_front_bwd = mk()
-        with torch.cuda.graph(self.g_front_bwd, pool=pool, stream=self._cap_stream, capture_error_mode=_CAPTURE_MODE):
+        with torch.cuda.graph(self.g_front_bwd, pool=pool, stream=self._cap_stream, capture_error_mode=ops.CAPTURE_MODE):
             dfeats, fg = self.front.bwd(self.s_front, (self.dX[0],), self.train_conv)
             conv_grads = w._conv_backward(self.sv_conv, g, dfeats.contiguous())[1] if self.train_conv else []
         for p, gt in zip(self.fparams, fg):
@@ -310,7 +306,7 @@ class GraphedAPTAIStep(_CapturingRunner):
                 self._ln_table, n_jobs, max_cols = ops.ln_defer_table(self._ln_jobs)        # host-to-device copy: outside capture
                 torch.cuda.synchronize()
                 self.g_ln = mk()
-                with torch.cuda.graph(self.g_ln, pool=pool, stream=self._cap_stream, capture_error_mode=_CAPTURE_MODE):
+                with torch.cuda.graph(self.g_ln, pool=pool, stream=self._cap_stream, capture_error_mode=ops.CAPTURE_MODE):
                     ops.ln_finalize_multi(self._ln_table, n_jobs, max_cols)
         # optimiser under the backward pass (step()): the parameters of layer i whose gradients are final when its backward segment ends
         self.adam_overlap = (self.group_reducer is None and hasattr(self.opt, "launch_early")
@@ -519,12 +515,13 @@ class GraphedForceStep(_CapturingRunner):
 
         encoder (frozen recogniser in inference mode + best-path decode, on a side stream)  |  heads forward + loss + heads backward
 
-    replayed one batch apart: while the heads of batch n replay on the caller's stream, the encoder of batch n+1 (handed to
-    step() as `next_batch`, or the same batch again) replays on the side stream.  Same kernels and the same two Python functions
-    (task_heads.ForceHead.fwd / .bwd) as the eager autograd path; dropout draws fresh masks per replay through the per-stream
-    salt; nothing synchronises host and device (`lists()` makes the Python lists of the reference's return value on demand).
-    The optimiser step is issued eagerly after the heads graph.  The captured heads keep the ARGMAX read-out of `pred_frame_phns`
-    whatever `Force_APTAI.alignment_readout` says (the monotonic read-out is an eager-path option)."""
+    replayed one batch apart: while the heads of batch n replay on the caller's stream, the encoder of batch n+1 (handed to step() as
+    `next_batch`, or the same batch again) replays on the side stream.  The encoder graph, its stream and the hand-over are the model's
+    (force_aptai.EncoderAhead, shared with the eager loop's prefetch; close() leaves them to it).  Same kernels and the same two Python
+    functions (task_heads.ForceHead.fwd / .bwd) as the eager autograd path; dropout draws fresh masks per replay through the per-stream
+    salt; nothing synchronises host and device (`lists()` makes the Python lists of the reference's return value on demand).  The
+    optimiser step is issued eagerly after the heads graph.  The captured heads keep the ARGMAX read-out of `pred_frame_phns` whatever
+    `Force_APTAI.alignment_readout` says (the monotonic read-out is an eager-path option)."""
 
     def __init__(self, model, optimizer, batch: Dict[str, torch.Tensor]):
         from .force_aptai import Force_APTAI
@@ -534,33 +531,22 @@ class GraphedForceStep(_CapturingRunner):
         self.model, self.opt = model, optimizer
         dev = next(model.parameters()).device
         self.dev = dev
-        self.audio = batch["audio_inputs"].float().contiguous().clone()
-        self.lengths = batch["audio_lengths"].clone()
         self._tracks = [k for k in batch if k not in ("audio_inputs", "audio_lengths", "phn_frames_49hz", "phoneme_labels")]
         w = model.w2v2_pr.wav2vec2
-        B, S = self.audio.shape
+        B, S = batch["audio_inputs"].shape
         self.g = w._geometry(B, S)
         g = self.g
         n_tv = model.rnn.linear[3].weight.shape[0]
         self.tv_tgt = torch.zeros((B, g.T, n_tv), device=dev, dtype=torch.float32)
         self._init_capture(dev, 0xF0CE + w.base_seed)
-        self._enc_stream = torch.cuda.Stream(device=dev)
         # one eager step: scratch buffers, code objects, weight copies
         model.zero_grad(set_to_none=True)
         model(0, **batch)["loss"].backward()
         model.zero_grad(set_to_none=True)
         torch.cuda.synchronize()
-        pool = torch.cuda.graph_pool_handle()
-        # ---- encoder graph (side stream): static inputs -> enc.{ac, ids, nlen, frame_lens}
-        self.g_enc = torch.cuda.CUDAGraph()
-        enc_tile = int(os.environ.get("APTAI_FORCE_ENC_TILE", "0"))
-        # ^ ops.auto_tile around the side-stream pass.  Rounds 3-4a forced 128-row tiles here: whole-CU workgroups kept the heads' BiLSTM
-        # clusters waiting (12 % of the step).  Since the cluster kernels hold their compute units alone (csrc/lstm.hip, APTAI_LSTM_LDS_KB)
-        # the dispatcher's own rule is the faster one again: 6.36 ms with 128, 6.09 ms with 0, 6.63 ms with 192 (interleaved, one box).
-        with torch.cuda.graph(self.g_enc, pool=pool, stream=self._enc_stream, capture_error_mode=_CAPTURE_MODE), ops.auto_tile(enc_tile):
-            self.enc = model._encode(self.audio, self.lengths)
-        # ---- heads graph: its own copies of the encoder outputs (the next encoder replay overwrites enc.*)
-        e = self.enc
+        # ---- encoder pass: the model's own (force_aptai.EncoderAhead), captured now for this batch shape
+        e = model.encoder_ahead.capture(batch["audio_inputs"].float(), batch["audio_lengths"]).out
+        # ---- heads graph: its own copies of the encoder outputs (the next encoder replay overwrites the graph-owned ones)
         self.h_ac, self.h_ids, self.h_nlen, self.h_fl = (torch.empty_like(t) for t in (e.ac, e.ids, e.nlen, e.frame_lens))
         self.h_nfull = torch.empty_like(e.nlen_full)          # the uncut decoded length: what lists() checks
         self.head = model.task_head
@@ -568,13 +554,12 @@ class GraphedForceStep(_CapturingRunner):
         self.st = self.head.state(model, g, (w.base_seed, 0xF0), True, self.h_ids, self.h_nlen, self.h_fl, self.tv_tgt)
         self.st.readout = "argmax"
         self.g_heads = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.g_heads, pool=pool, stream=self._cap_stream, capture_error_mode=_CAPTURE_MODE):
+        with torch.cuda.graph(self.g_heads, stream=self._cap_stream, capture_error_mode=ops.CAPTURE_MODE):
             self.st.vocab_sizes = self.h_nlen + 1             # derived from a static input: recomputed on every replay
             self.outs, saved = self.head.fwd(self.h_ac, self.P, self.st)
             self.pgrads = self.head.bwd(saved, self.st, self.P, self.h_ac, None)[1:]
         torch.cuda.synchronize()
-        self._have_enc = False
-        self._enc_done = None
+        self._ahead = None                                    # handle of the pass launched for the next step()
         self._last = batch
         self.set_batch(batch)
 
@@ -583,36 +568,20 @@ class GraphedForceStep(_CapturingRunner):
         """Targets of the batch whose heads run in the next step()."""
         self.tv_tgt.copy_(torch.stack([batch[k] for k in self._tracks], dim=-1).float(), non_blocking=True)
 
-    def _launch_encoder(self, batch: Dict[str, torch.Tensor]) -> None:
-        cur = torch.cuda.current_stream(self.dev)
-        es = self._enc_stream
-        es.wait_stream(cur)                                   # the batch tensors, and the previous copies out of enc.*
-        with torch.cuda.stream(es):
-            self.audio.copy_(batch["audio_inputs"].float(), non_blocking=True)
-            self.lengths.copy_(batch["audio_lengths"], non_blocking=True)
-            self.g_enc.replay()
-            self._enc_done = torch.cuda.Event()
-            self._enc_done.record(es)
-        self.model.w2v2_pr.wav2vec2._step += 1
-        self._have_enc = True
-
     # ------------------------------------------------------------------ one optimiser step
     def step(self, batch: Optional[Dict[str, torch.Tensor]] = None, next_batch: Optional[Dict[str, torch.Tensor]] = None):
         """Heads of `batch` (default: the batch given last) + optimiser step; the encoder pass of `next_batch` (default: `batch`
-        again) goes out on the side stream first.  The very first call encodes `batch` inline."""
+        again) goes out on the side stream first.  The very first call encodes `batch` itself, and so does one whose pass ahead was
+        dropped meanwhile (EncoderAhead.take: the weights were reloaded, or another caller replayed the pass)."""
         if batch is not None:
             self.set_batch(batch)
             self._last = batch
         batch = batch if batch is not None else self._last
-        cur = torch.cuda.current_stream(self.dev)
-        if not self._have_enc:
-            self._launch_encoder(batch)
-        cur.wait_event(self._enc_done)
-        e = self.enc
-        self.h_ac.copy_(e.ac, non_blocking=True); self.h_ids.copy_(e.ids, non_blocking=True)
-        self.h_nlen.copy_(e.nlen, non_blocking=True); self.h_fl.copy_(e.frame_lens, non_blocking=True)
-        self.h_nfull.copy_(e.nlen_full, non_blocking=True)
-        self._launch_encoder(next_batch if next_batch is not None else batch)      # waits for the four copies above
+        ahead, into = self.model.encoder_ahead, (self.h_ac, self.h_ids, self.h_nlen, self.h_fl, self.h_nfull)
+        if self._ahead is None or ahead.take(self._ahead, into) is None:
+            ahead.take(ahead.launch(batch["audio_inputs"].float(), batch["audio_lengths"]), into)
+        nxt = next_batch if next_batch is not None else batch
+        self._ahead = ahead.launch(nxt["audio_inputs"].float(), nxt["audio_lengths"])     # (a host batch is copied in)
         self._next_salt()
         self.g_heads.replay()
         for p, gt in zip(self.P, self.pgrads):

@@ -43,27 +43,43 @@ def gemm_plan(d: GemmDesc) -> GemmPlanInfo:
     return info
 
 
+# thread-local capture for every hipGraph of the package: under data parallelism the process group's watchdog thread polls its events
+# while this thread captures, and in the default "global" mode a call from ANY thread can invalidate the capture
+CAPTURE_MODE = "thread_local"
+
+
+class ScratchPool:
+    """Persistent scratch buffers that NEVER move: a buffer handed out for (purpose, device, stream, dtype, size class) is not
+    replaced and not freed while the pool lives, because captured hipGraphs hold its address (a buffer that grew used to be swapped
+    out from under them: the next replays read freed memory).  The size class is the next power of two at or above the request (at
+    least 16 elements), so a purpose keeps at most a few dozen buffers; `exact` keeps the element count.  `stream` is whatever the
+    caller keys by (the raw handle of the launch stream, or None for one buffer whatever the stream): "every consumer of a scratch
+    runs on the launch stream right after its producer" only holds per stream."""
+
+    def __init__(self):
+        self._bufs = {}
+
+    def get(self, purpose, numel: int, device, stream, dtype=torch.float32, *, exact=False, zero=False) -> torch.Tensor:
+        n = int(numel) if exact else 1 << (max(int(numel), 16) - 1).bit_length()
+        key = (purpose, str(device), stream, dtype, n)
+        t = self._bufs.get(key)
+        if t is None:
+            t = self._bufs[key] = (torch.zeros if zero else torch.empty)(n, device=device, dtype=dtype)
+        return t
+
+    def buffers(self, purpose, device=None):
+        """[(stream, buffer)] of one purpose (on one device), in the order they were made."""
+        return [(k[2], t) for k, t in self._bufs.items() if k[0] == purpose and (device is None or k[1] == str(device))]
+
+
+SCRATCH = ScratchPool()        # the package's own: split-K slabs / column-sum / LayerNorm partials of the fp32 heads, LSTM and stream-K areas
 TILE_STREAMK = 257
-_SK_WS = {}
-
-
-def _sk_workspace(device) -> torch.Tensor:
-    """Stream-K workspace (one 256 x 256 fp32 slab per CU + self-cleaning ready flags + status word) of the CURRENT stream:
-    zeroed once here; launches on one stream are serialised, so they share it; another stream gets its own."""
-    key = (str(device), _stream())
-    ws = _SK_WS.get(key)
-    if ws is None:
-        ws = torch.zeros(int(_lib.lib().aptai_gemm_sk_workspace_bytes()), device=device, dtype=torch.uint8)
-        _SK_WS[key] = ws
-    return ws
 
 
 def gemm_sk_check(device=None) -> None:
     """Raises if a bounded wait of a stream-K GEMM launch gave up since the last check (its output tile was then incomplete).
     Synchronises: call where the host waits for the device anyway (loss logging, end of an epoch, after a timed region)."""
-    for (d, st), ws in list(_SK_WS.items()):
-        if device is not None and d != str(device):
-            continue
+    for st, ws in SCRATCH.buffers("sk", device):
         out = ctypes.c_int(0)
         _lib.call("aptai_gemm_sk_status", ws.data_ptr(), st, ctypes.byref(out))
         if out.value != 0:
@@ -170,7 +186,9 @@ def _gemm_desc(d: "GemmDesc", a: torch.Tensor, b: torch.Tensor, M: int, N: int, 
     d.split_k, d.accumulate = split_k, int(accumulate)
     d.tile = tile if tile else _AUTO_TILE
     if tile == TILE_STREAMK:          # opt-in only: measured slower than the tile rule's choice on every hot-path shape
-        ws_sk = _sk_workspace(a.device)
+        # one 256 x 256 fp32 slab per CU + self-cleaning ready flags + status word, zeroed once, per STREAM: launches on one stream are
+        # serialised, so they share it; another stream gets its own
+        ws_sk = SCRATCH.get("sk", _lib.lib().aptai_gemm_sk_workspace_bytes(), a.device, _stream(), torch.uint8, exact=True, zero=True)
         d.sk_workspace, d.sk_workspace_bytes = ws_sk.data_ptr(), ws_sk.numel()
     if colscale is not None:       # (n_cols, factor): output columns [0, n_cols) *= factor after alpha / bias
         d.colscale_n, d.colscale = int(colscale[0]), float(colscale[1])
@@ -1240,20 +1258,6 @@ def wave_normalize(x, lens_i64, ncols=None):
 
 
 # ----------------------------------------------------------------------------- Force_APTAI heads (fp32)
-_SCRATCH32 = {}
-
-
-def _scratch_f32(key, numel: int, device) -> torch.Tensor:
-    """Persistent fp32 scratch per (purpose, device): split-K slabs and column-sum partials of the fp32 heads (stream-ordered
-    reuse: every consumer of a scratch runs on the launch stream right after its producer)."""
-    k = (key, str(device))
-    t = _SCRATCH32.get(k)
-    if t is None or t.numel() < numel:
-        t = torch.empty(max(int(numel), 16), device=device, dtype=torch.float32)
-        _SCRATCH32[k] = t
-    return t
-
-
 def sgemm(a, sam, sak, b, sbk, sbn, M, N, K, *, out=None, ldc=None, bias=None, alpha=1.0, accumulate=False, batch=1, bsa=0, bsb=0,
           bsc=0, split_k=None):
     """C[m][n] (+)= alpha * sum_k A(m,k) B(k,n) + bias[n] with explicit element strides (see aptai_sgemm_f32).
@@ -1268,7 +1272,7 @@ def sgemm(a, sam, sak, b, sbk, sbn, M, N, K, *, out=None, ldc=None, bias=None, a
         split_k = 1 if (tiles >= 256 or K < 256) else max(1, min(K // 128, 512 // tiles))
     ws = None
     if split_k > 1:
-        ws = _scratch_f32("sgemm", batch * split_k * M * N, a.device)
+        ws = SCRATCH.get("sgemm", batch * split_k * M * N, a.device, _stream())
     _lib.call("aptai_sgemm_f32", a.data_ptr(), int(a.dtype == torch.bfloat16), sam, sak, b.data_ptr(), sbk, sbn, out.data_ptr(),
               ldc if ldc else N, _ptr(bias), alpha, int(accumulate), M, N, K, batch, bsa, bsb, bsc, split_k, _ptr(ws), _stream())
     return out
@@ -1365,31 +1369,16 @@ def layernorm_f32_bwd(dy, x, mean, rstd, gamma):
     dx = torch.empty_like(x)
     dg = torch.empty(cols, device=x.device, dtype=torch.float32)
     db = torch.empty(cols, device=x.device, dtype=torch.float32)
-    ws = _scratch_f32("ln32_bwd", 256 * 2 * cols, x.device)
+    ws = SCRATCH.get("ln32_bwd", 256 * 2 * cols, x.device, _stream())
     _lib.call("aptai_layernorm_f32_bwd", dy.data_ptr(), x.data_ptr(), mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr(),
               dx.data_ptr(), dg.data_ptr(), db.data_ptr(), ws.data_ptr(), rows, cols, _stream())
     return dx, dg, db
 
 
-_LSTM_WS = {}
-
-
-def _lstm_workspace(B: int, device) -> torch.Tensor:
-    """Exchange area of the cooperating LSTM workgroups + status word, one per (device, STREAM): two Force_APTAI models, or one
-    model driven from two streams, never share an exchange area (zeroed once here; every launch re-zeroes what it uses)."""
-    n = _lib.lib().aptai_lstm_workspace_bytes(B)
-    key = (str(device), _stream())
-    ws = _LSTM_WS.get(key)
-    if ws is None or ws.numel() < n:
-        ws = torch.zeros(n, device=device, dtype=torch.uint8)
-        _LSTM_WS[key] = ws
-    return ws
-
-
 def lstm_status_words(device):
     """int32 device tensor with the status word of every LSTM workspace of this device (None if no LSTM has run): lets a caller
     fold the check into a device->host read it makes anyway (Force_APTAI._lists)."""
-    words = [ws[:4].view(torch.int32) for (d, _), ws in _LSTM_WS.items() if d == str(device)]
+    words = [ws[:4].view(torch.int32) for _, ws in SCRATCH.buffers("lstm", device)]
     if not words:
         return None
     return words[0] if len(words) == 1 else torch.cat(words)
@@ -1399,9 +1388,8 @@ def lstm_check(status_host, device) -> None:
     """Raises when a bounded wait of the cooperating LSTM kernels timed out (their output is then incomplete); clears the
     status words so that the next step is judged on its own."""
     if status_host is not None and any(int(v) != 0 for v in status_host):
-        for (d, _), ws in _LSTM_WS.items():
-            if d == str(device):
-                ws[:4].zero_()
+        for _, ws in SCRATCH.buffers("lstm", device):
+            ws[:4].zero_()
         raise _lib.AptaiHipError("aptai_lstm: a cross-workgroup wait of the cooperative BiLSTM kernels timed out "
                                  "(not all 16 workgroups of a cluster were resident together?): hout / dgates are incomplete")
 
@@ -1438,7 +1426,9 @@ def lstm_fwd(xproj, whh, lens_i32, B, Tp, T, save=True):
     hout = torch.empty((B * Tp, 512), device=dev, dtype=torch.float32)
     gates = torch.empty((B * Tp, 2048), device=dev, dtype=torch.float32) if save else None
     cst = torch.empty((B * Tp, 512), device=dev, dtype=torch.float32) if save else None
-    ws = _lstm_workspace(B, dev)
+    # exchange area of the cooperating LSTM workgroups + status word, per (device, STREAM): two Force_APTAI models, or one model driven
+    # from two streams, never share one (zeroed once, at creation; every launch re-zeroes what it uses)
+    ws = SCRATCH.get("lstm", _lib.lib().aptai_lstm_workspace_bytes(B), dev, _stream(), torch.uint8, zero=True)
     _lib.call("aptai_lstm_fwd", xproj.data_ptr(), whh.data_ptr(), lens_i32.data_ptr(), hout.data_ptr(), _ptr(gates), _ptr(cst),
               ws.data_ptr(), B, Tp, T, 256, _stream())
     return hout, gates, cst
@@ -1447,7 +1437,7 @@ def lstm_fwd(xproj, whh, lens_i32, B, Tp, T, save=True):
 def lstm_bwd(dhout, whh, lens_i32, gates, cst, B, Tp, T):
     _dev(dhout, whh, lens_i32, gates, cst)
     dgates = torch.empty_like(gates)
-    ws = _lstm_workspace(B, dhout.device)
+    ws = SCRATCH.get("lstm", _lib.lib().aptai_lstm_workspace_bytes(B), dhout.device, _stream(), torch.uint8, zero=True)   # as lstm_fwd
     _lib.call("aptai_lstm_bwd", dhout.data_ptr(), whh.data_ptr(), lens_i32.data_ptr(), gates.data_ptr(), cst.data_ptr(),
               dgates.data_ptr(), ws.data_ptr(), B, Tp, T, 256, _stream())
     return dgates
@@ -1499,6 +1489,6 @@ def dropout_f32(x, p, seed):
 
 def colsum_f32(x, rows, N, ld=None):
     out = torch.empty(N, device=x.device, dtype=torch.float32)
-    ws = _scratch_f32("colsum", 64 * N, x.device)
+    ws = SCRATCH.get("colsum", 64 * N, x.device, _stream())
     _lib.call("aptai_colsum_f32", x.data_ptr(), ld if ld else x.stride(0), out.data_ptr(), ws.data_ptr(), rows, N, _stream())
     return out

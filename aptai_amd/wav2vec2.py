@@ -567,7 +567,7 @@ class Wav2Vec2Model(nn.Module):
         enc.layers = nn.ModuleList(ls)
         self.encoder = enc
         self._cache = {}
-        self._scratch_bufs = {}
+        self._scratch_pool = ops.ScratchPool()
         self._scratch_owner = {}
         self._step = 0
         self.base_seed = 0x5EED
@@ -762,15 +762,11 @@ class Wav2Vec2Model(nn.Module):
     def _scratch(self, key, numel, dev):
         """Persistent zero-initialised bf16 scratch (the zero gap rows of the packed positional-conv operands are
         written once here and never again)."""
-        # one buffer per (key, size): a buffer is NEVER replaced or freed while the model lives - captured hipGraphs (the
-        # graph runners, Force_APTAI.prefetch) hold its address, and a forward with another batch shape in between (validation
-        # at batch 1 between training epochs) used to swap it out from under them: the next replays read freed memory
-        full = (key, int(numel), str(dev))
-        cur = self._scratch_bufs.get(full)
-        if cur is None:
-            cur = torch.zeros(numel, device=dev, dtype=torch.bfloat16)
-            self._scratch_bufs[full] = cur
-        return cur
+        # one buffer per (key, size), whatever the stream, that dies with the model (ops.ScratchPool: NEVER replaced or freed before) -
+        # captured hipGraphs (the graph runners, Force_APTAI's encoder pass ahead) hold its address, and a forward with another batch
+        # shape in between (validation at batch 1 between training epochs) used to swap it out from under them: the next replays read
+        # freed memory
+        return self._scratch_pool.get(key, numel, dev, None, torch.bfloat16, exact=True, zero=True)
 
     # ------------------------------------------------------------------ geometry of one batch
     def _feature_axis_lens(self, B: int, dev) -> torch.Tensor:

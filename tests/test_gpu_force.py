@@ -399,7 +399,7 @@ def test_prefetch_graph_survives_forwards_of_other_batch_shapes():
         assert torch.isfinite(enc.ac).all() and torch.equal(enc.ac, ref.ac) and torch.equal(enc.ids, ref.ids), i
     for i in (0, 1, 2, 0):                       # eager, capture, replays
         check(i)
-    assert any(g is not None for g in model._enc_graphs.values())
+    assert any(g is not None for g in model.encoder_ahead.entries.values())
     model.eval()
     with torch.no_grad():
         for _ in range(2):
@@ -434,10 +434,12 @@ def test_lstm_timeout_status_raises_on_the_product_path():
         with torch.cuda.stream(side):
             model(0, **b, _phn_pred_list=lists)
         side.synchronize()
-        k_cur, k_side = ("cuda:0", cur.cuda_stream), ("cuda:0", side.cuda_stream)
-        assert k_cur in ops._LSTM_WS and k_side in ops._LSTM_WS        # the second stream got its own exchange area
-        assert ops._LSTM_WS[k_cur].data_ptr() != ops._LSTM_WS[k_side].data_ptr()
-        ws = ops._LSTM_WS[k_cur]
+        areas = {}
+        for st, t in ops.SCRATCH.buffers("lstm", "cuda:0"):
+            areas.setdefault(st, t)
+        assert cur.cuda_stream in areas and side.cuda_stream in areas  # the second stream got its own exchange area
+        assert areas[cur.cuda_stream].data_ptr() != areas[side.cuda_stream].data_ptr()
+        ws = areas[cur.cuda_stream]
         ws[:4].view(torch.int32).fill_(1)                              # what a timed-out wait leaves behind
         with pytest.raises(AptaiHipError, match="timed out"):
             model(0, **b, _phn_pred_list=lists)

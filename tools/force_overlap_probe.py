@@ -33,12 +33,13 @@ def main():
     torch.cuda.synchronize()
     ev = lambda: torch.cuda.Event(enable_timing=True)
     # each graph alone
-    es = r._enc_stream
+    ahead = model.encoder_ahead                    # owns the side stream and the captured encoder pass (one entry: this batch shape)
+    es, (enc_entry,) = ahead.stream, ahead.entries.values()
     a0, a1 = ev(), ev()
     with torch.cuda.stream(es):
         a0.record(es)
         for _ in range(10):
-            r.g_enc.replay()
+            enc_entry.graph.replay()
         a1.record(es)
     torch.cuda.synchronize()
     b0, b1 = ev(), ev()
@@ -49,7 +50,6 @@ def main():
     torch.cuda.synchronize()
     print(f"alone: encoder graph {a0.elapsed_time(a1) / 10:.3f} ms, heads graph {b0.elapsed_time(b1) / 10:.3f} ms")
     # side by side, as step() issues them
-    orig_enc, orig_heads = r.g_enc.replay, r.g_heads.replay
     rec = []
 
     class Wrap:
@@ -64,7 +64,7 @@ def main():
             e1.record(s)
             rec.append((self.tag, e0, e1))
 
-    r.g_enc = Wrap(r.g_enc, lambda: torch.cuda.current_stream(), "enc")
+    enc_entry.graph = Wrap(enc_entry.graph, lambda: torch.cuda.current_stream(), "enc")
     r.g_heads = Wrap(r.g_heads, lambda: torch.cuda.current_stream(), "heads")
     t0, t1 = ev(), ev()
     t0.record()
