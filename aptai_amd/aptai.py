@@ -14,7 +14,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import hostlogic, task_heads
+from . import hostlogic, longform, task_heads
 from .hostlogic import TV_NAMES
 from .modules import LowPassFilterLayer
 from .wav2vec2 import Wav2Vec2Model, batch_invariant_scope
@@ -132,5 +132,50 @@ class APTAI(nn.Module):
                 'phn_fc_logits': phn_logits[b, :T],
                 'phn_fc_pred': pred[b, :T],
                 'tvs_pred': {n: [row[i] for row in tvs[b, :T]] for i, n in enumerate(names)},
+            })
+        return out
+
+    def get_aptai_output_long(self, wav, window_frames=499, hop_frames=399, trim_frames=25, ramp="linear", windows_per_forward=16):
+        """`get_aptai_output` for a recording longer than the clips the model was trained on: the keys and shapes of that helper,
+        from overlapped windows of `window_frames` encoder frames every `hop_frames` (hostlogic.long_form_plan), stitched on the
+        device - `get_aptai_outputs_long` of one recording.  The waveform is taken as given: a caller who normalises does so over
+        the whole recording, never per window."""
+        return self.get_aptai_outputs_long([wav], window_frames, hop_frames, trim_frames, ramp, windows_per_forward)[0]
+
+    def get_aptai_outputs_long(self, wavs, window_frames=499, hop_frames=399, trim_frames=25, ramp="linear", windows_per_forward=16):
+        """`get_aptai_outputs` over recordings of any length.  The windows of ALL recordings run through the eval-mode,
+        batch-invariant forward in groups of `windows_per_forward` (what bounds the encoder's memory; a window's result does not
+        depend on its group), the filtered trajectories and the head logits of the windows are stitched per recording
+        (aptai_stitch_windows: `ramp` = "linear" fades over the overlap less `trim_frames` at either end, "cut" switches in its
+        middle), `phn_fc_pred` is the argmax of the stitched logits and `phn_fc_probs` their softmax; ONE device->host transfer.  A
+        recording of at most `window_frames` frames is one window: `get_aptai_output` with `batch_invariant` on ("Long
+        recordings")."""
+        self.eval()
+        device = next(self.parameters()).device
+        if not len(wavs):
+            return []
+        run = longform.LongFormRun(wavs, self.wav2vec2, device, window_frames, hop_frames, trim_frames, ramp)
+        n_tv, n_phn = self.n_tv, self.n_phn
+        tv_all = logits_all = None
+        with torch.no_grad(), batch_invariant_scope(self.wav2vec2, True):
+            for first, rows in run.groups(windows_per_forward):
+                audio, lens = run.gather(first, rows)
+                w2v2_out = self.wav2vec2(audio, attention_mask=lens[:, None], return_dict=True, output_hidden_states=True)
+                _, _, _, tvs, _, logits = self._heads(w2v2_out, None, None)
+                g = w2v2_out._geom
+                tv_all, logits_all = run.collect(tv_all, tvs, first, rows), run.collect(logits_all, logits, first, rows)
+            tv, _ = run.stitch(tv_all, n_tv, g.T, n_tv, want_argmax=False)                   # [W][T][n_tv] as the filter wrote them
+            phn_logits, pred = run.stitch(logits_all, logits_all.shape[1], g.Tp, n_phn)      # [W * Tp][64], the first n_phn columns
+            host = torch.cat([tv, phn_logits, F.softmax(phn_logits, dim=-1), pred[:, None].float()], dim=1).cpu().numpy()
+        names = TV_NAMES if n_tv == 9 else tuple(f"TV{i}" for i in range(n_tv))
+        out = []
+        for r0, T in zip(run.row_start, run.frames):
+            rows = host[r0:r0 + T]
+            tvs, lg, probs = rows[:, :n_tv], rows[:, n_tv:n_tv + n_phn], rows[:, n_tv + n_phn:n_tv + 2 * n_phn]
+            out.append({
+                'phn_fc_probs': np.ascontiguousarray(probs)[None].transpose(2, 1, 0),                      # (C, T, 1) as get_aptai_output
+                'phn_fc_logits': np.ascontiguousarray(lg),
+                'phn_fc_pred': rows[:, -1].astype(np.int64),                                               # an index below 64: exact in fp32
+                'tvs_pred': {n: [row[i] for row in tvs] for i, n in enumerate(names)},
             })
         return out

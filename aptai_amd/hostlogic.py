@@ -5,7 +5,7 @@ Every function cites the reference call site it mirrors.  "HF:" = the un-vendore
 """
 from __future__ import annotations
 
-from typing import Callable, Dict, List, Optional, Sequence
+from typing import Callable, Dict, List, NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
@@ -71,6 +71,100 @@ def frame_attention_mask(n_frames: int, frame_lengths: torch.Tensor) -> torch.Te
     """(B, T) bool mask of valid frames — same result as HF:1018-1036's flip/cumsum construction."""
     ar = torch.arange(n_frames, device=frame_lengths.device)
     return ar[None, :] < frame_lengths[:, None]
+
+
+# ----------------------------------------------------------------------------- long recordings: windows on the frame grid
+def conv_stride_and_field(conv_kernel: Sequence[int], conv_stride: Sequence[int]):
+    """(s, r) of the conv stack: frame j reads samples [s j, s j + r).  320 and 400 for wav2vec2's (10,3,3,3,3,2,2) / (5,2,2,2,2,2,2)."""
+    s, r = 1, 1
+    for k, st in zip(conv_kernel, conv_stride):
+        r += (k - 1) * s
+        s *= st
+    return s, r
+
+
+class LongFormPlan(NamedTuple):
+    """Windows 0 .. K of one recording (long_form_plan).  Per window: first global frame, frame count, first sample, sample count."""
+    n_samples: int
+    frames: int                  # F
+    K: int
+    stride: int                  # s
+    field: int                   # r
+    window_frames: int
+    hop_frames: int
+    trim_frames: int
+    overlap: int                 # window_frames - hop_frames
+    frame_start: tuple           # f0_k = k hop_frames
+    window_len: tuple            # frames_k = min(window_frames, F - f0_k)
+    sample_start: tuple          # s f0_k
+    sample_count: tuple          # s (window_frames - 1) + r, the last window: everything up to n_samples
+
+
+def long_form_plan(n_samples: int, conv_kernel: Sequence[int], conv_stride: Sequence[int], window_frames: int = 499,
+                   hop_frames: int = 399, trim_frames: int = 25) -> LongFormPlan:
+    """Overlapped windows of a recording of `n_samples`, laid on the encoder's frame grid (HF pipelines: chunk_length_s /
+    stride_length_s, there in samples).  F = conv_layer_lengths(n)[-1]; K = 0 if F <= window_frames else
+    ceil((F - window_frames) / hop_frames); window k starts at global frame k hop_frames = sample s k hop_frames and, unless it is
+    the last, carries exactly the s (window_frames - 1) + r samples of window_frames frames; the last carries the rest.  A valid
+    convolution stack is shift-invariant in steps of s samples, so frame j of window k is global frame f0_k + j computed from the
+    same samples; every frame lies in one or two windows and the last window owns more than `overlap` frames.  The defaults are a
+    10 s window (the longest training clip), 2 s of overlap and the low-pass filter's half width as trim (long_form_ramp)."""
+    W, hop, trim = int(window_frames), int(hop_frames), int(trim_frames)
+    if W < 1 or hop < 1 or trim < 0:
+        raise ValueError(f"long_form_plan: window_frames={W}, hop_frames={hop} must be positive and trim_frames={trim} not negative")
+    if 2 * hop < W:
+        raise ValueError(f"long_form_plan: hop_frames={hop} below half of window_frames={W}: a frame would lie in three windows")
+    s, r = conv_stride_and_field(conv_kernel, conv_stride)
+    n = int(n_samples)
+    F = conv_layer_lengths(n, conv_kernel, conv_stride)[-1]
+    if F < 1:
+        raise ValueError(f"long_form_plan: a recording of {n} samples is shorter than the receptive field of the feature encoder ({r})")
+    K = 0 if F <= W else -((W - F) // hop)
+    overlap = W - hop
+    if K > 0 and overlap <= 2 * trim:
+        raise ValueError(f"long_form_plan: an overlap of {overlap} frames leaves nothing between two trims of {trim}")
+    f0 = tuple(k * hop for k in range(K + 1))
+    return LongFormPlan(n, F, K, s, r, W, hop, trim, overlap, f0, tuple(min(W, F - f) for f in f0), tuple(s * f for f in f0),
+                        tuple(s * (W - 1) + r if k < K else n - s * f for k, f in enumerate(f0)))
+
+
+def long_form_ramp(plan: LongFormPlan, kind: str = "linear") -> np.ndarray:
+    """fp32 [overlap]: the weight of the LATER window at position j of an overlap, built in fp64 and rounded once.
+    "linear": clip((j - trim + 0.5) / (overlap - 2 trim), 0, 1) - the `trim` frames next to either window's edge are never used
+    at an interior seam (0 next to the later window's start, 1 next to the earlier window's end), a linear fade between them.
+    "cut": 0 below the middle of the overlap, 1 from it on (no blending: what HF's pipeline does with its strides).
+    A plan of one window has no seam: its table is all zeros and never read."""
+    if kind not in ("linear", "cut"):
+        raise ValueError(f"long_form_ramp: ramp must be 'linear' or 'cut', not {kind!r}")
+    n = max(plan.overlap, 0)
+    j = np.arange(n, dtype=np.float64)
+    if plan.K == 0 and n <= 2 * plan.trim_frames:
+        return np.zeros(n, dtype=np.float32)
+    if kind == "cut":
+        return (j + 0.5 >= n / 2).astype(np.float32)
+    return np.clip((j - plan.trim_frames + 0.5) / (n - 2 * plan.trim_frames), 0.0, 1.0).astype(np.float32)
+
+
+def long_form_stitch(windows, plan: LongFormPlan, ramp: np.ndarray):
+    """numpy restatement of aptai_stitch_windows for one recording: `windows[k]` holds the fp32 rows of window k (at least
+    window_len[k] of them, C channels).  Returns (stitched fp32 [F][C], frame argmax int64 [F], first maximum).  At position j of the
+    overlap between windows k-1 and k: x0 where ramp[j] <= 0, x1 where ramp[j] >= 1, else x0 + ramp[j] (x1 - x0) in three rounded
+    fp32 operations."""
+    if len(windows) != plan.K + 1:
+        raise ValueError(f"long_form_stitch: {len(windows)} windows for a plan of {plan.K + 1}")
+    ramp = np.asarray(ramp, dtype=np.float32)
+    wins = [np.asarray(w, dtype=np.float32)[:n] for w, n in zip(windows, plan.window_len)]
+    if any(w.ndim != 2 or w.shape != (n, wins[0].shape[1]) for w, n in zip(wins, plan.window_len)):
+        raise ValueError("long_form_stitch: every window needs its window_len rows of the same width")
+    out = np.empty((plan.frames, wins[0].shape[1]), dtype=np.float32)
+    for k, (f0, w) in enumerate(zip(plan.frame_start, wins)):
+        out[f0:f0 + len(w)] = w                                        # the overlap with window k+1 is rewritten below
+        if k > 0:
+            m = min(plan.overlap, len(w))                              # == overlap: the last window owns more than that
+            x0, x1, r = wins[k - 1][plan.hop_frames:plan.hop_frames + m], w[:m], ramp[:m, None]
+            blend = x0 + r * (x1 - x0)                                 # float32 arrays: each operation rounds on its own
+            out[f0:f0 + m] = np.where(r <= 0, x0, np.where(r >= 1, x1, blend))
+    return out, out.argmax(axis=-1).astype(np.int64)
 
 
 # ----------------------------------------------------------------------------- SpecAugment

@@ -1257,6 +1257,53 @@ def wave_normalize(x, lens_i64, ncols=None):
     return x
 
 
+# ----------------------------------------------------------------------------- long recordings (csrc/longform.hip)
+def window_gather(packed, table_i64, first, rows, S):
+    """Windows first .. first + rows - 1 of `table_i64` (int64 [n_windows][3] on the device: recording offset, sample start, sample
+    count) cut out of `packed` (1-D fp32: the recordings back to back) - see aptai_window_gather.  Returns (audio fp32 [rows][S]
+    zero-padded, lens int64 [rows]).  No synchronisation."""
+    _dev(packed, table_i64)
+    if packed.dtype != torch.float32 or packed.dim() != 1 or not packed.is_contiguous():
+        raise _lib.AptaiHipError("window_gather: the packed source must be a contiguous 1-D float32 tensor")
+    if table_i64.dtype != torch.int64 or table_i64.dim() != 2 or table_i64.shape[1] != 3 or not table_i64.is_contiguous():
+        raise _lib.AptaiHipError("window_gather: the window table must be a contiguous int64 [n_windows][3] device tensor")
+    first, rows, S = int(first), int(rows), int(S)
+    out = torch.empty((max(rows, 0), max(S, 0)), device=packed.device, dtype=torch.float32)
+    lens = torch.empty(max(rows, 0), device=packed.device, dtype=torch.int64)
+    _lib.call("aptai_window_gather", packed.data_ptr(), packed.numel(), table_i64.data_ptr(), table_i64.shape[0], first, rows,
+              out.data_ptr(), S, S, lens.data_ptr(), _stream())
+    return out, lens
+
+
+def stitch_windows(x, ldx, rows_per_window, n_windows, rec_i64, max_frames, window_frames, hop_frames, ramp_f32, C, *, out=None,
+                   out_rows=None, ldo=None, want_argmax=True):
+    """Per-window fp32 rows `x` (window w at rows w rows_per_window .., pitch ldx) stitched into the rows of their recordings -
+    see aptai_stitch_windows.  `rec_i64`: int64 [n_rec][3] on the device (first window, frame count, first output row);
+    `max_frames` >= every frame count; `ramp_f32`: fp32 [window_frames - hop_frames] on the device (hostlogic.long_form_ramp), None
+    when no recording has a second window.  `out` fp32 [out_rows][ldo] is made here (zeros) unless given.  Returns (out, argmax
+    int64 [out_rows] or None): the argmax rows that no recording owns stay 0.  No synchronisation, no host read-back."""
+    _dev(x, rec_i64, ramp_f32, out)
+    ldx, rows_per_window, n_windows, C = int(ldx), int(rows_per_window), int(n_windows), int(C)
+    if x.dtype != torch.float32 or not x.is_contiguous() or n_windows < 1 or x.numel() < (n_windows * rows_per_window - 1) * ldx + C:
+        raise _lib.AptaiHipError(f"stitch_windows: contiguous fp32 results of {n_windows} windows x {rows_per_window} rows of pitch {ldx} expected")
+    if rec_i64.dtype != torch.int64 or rec_i64.dim() != 2 or rec_i64.shape[1] != 3 or not rec_i64.is_contiguous():
+        raise _lib.AptaiHipError("stitch_windows: the recording table must be a contiguous int64 [n_rec][3] device tensor")
+    overlap = int(window_frames) - int(hop_frames)
+    if ramp_f32 is not None and (ramp_f32.dtype != torch.float32 or not ramp_f32.is_contiguous() or ramp_f32.numel() < overlap):
+        raise _lib.AptaiHipError(f"stitch_windows: a contiguous fp32 ramp of {overlap} entries expected")
+    if out is None:
+        if out_rows is None:
+            raise _lib.AptaiHipError("stitch_windows: out or out_rows expected")
+        ldo = C if ldo is None else int(ldo)
+        out = torch.zeros((int(out_rows), ldo), device=x.device, dtype=torch.float32)
+    if out.dtype != torch.float32 or out.dim() != 2 or out.stride(1) != 1 or out.shape[1] < C:
+        raise _lib.AptaiHipError(f"stitch_windows: the output must be fp32 [rows][>= {C}] with unit column stride")
+    argmax = torch.zeros(out.shape[0], device=x.device, dtype=torch.int64) if want_argmax else None
+    _lib.call("aptai_stitch_windows", x.data_ptr(), ldx, rows_per_window, n_windows, rec_i64.data_ptr(), rec_i64.shape[0], int(max_frames),
+              int(window_frames), int(hop_frames), _ptr(ramp_f32), C, out.data_ptr(), out.stride(0), out.shape[0], _ptr(argmax), _stream())
+    return out, argmax
+
+
 # ----------------------------------------------------------------------------- Force_APTAI heads (fp32)
 def sgemm(a, sam, sak, b, sbk, sbn, M, N, K, *, out=None, ldc=None, bias=None, alpha=1.0, accumulate=False, batch=1, bsa=0, bsb=0,
           bsc=0, split_k=None):

@@ -20,11 +20,13 @@ beams, and through ``decode_nbest`` / ``predict_nbest`` n-best lists with per-to
 """
 from __future__ import annotations
 
+from types import SimpleNamespace
+
 import numpy as np
 import torch
 import torch.nn as nn
 
-from . import hostlogic, ops, task_heads
+from . import hostlogic, longform, ops, task_heads
 from .modules import _LinearFn
 from .wav2vec2 import Wav2Vec2Model, _round_up, batch_invariant_scope
 
@@ -250,6 +252,53 @@ class Wav2Vec2_PR(nn.Module):
             frame_sec_ratio = len(wav) / logits.size(1) / 16000
             (idx, ts, _), = self._rows(*self._read_out(out, logits.size(1) + 2))       # tokens AND timesteps in one transfer
             return {'phn_seq_idx': idx, 'phn_seq_ipa': self._ipa(vocab, idx), 'phn_seq_dur': [t * frame_sec_ratio for t in ts]}
+
+    # ------------------------------------------------------------------ long recordings ("Long recordings")
+    def _long(self, wavs, window_frames, hop_frames, trim_frames, ramp, windows_per_forward):
+        """The stitched CTC logits of recordings of any length as `_read_out` takes them: (run, out) where `out._logits_full` is
+        fp32 [n_rec * max_frames][Np] (one block of rows per recording, zeros beyond its frames and beyond the vocabulary) and
+        `out._geom` says so (B = n_rec, T = Tp = max_frames, fir_lens = the frame counts).  The windows of all recordings run through
+        `_logits_eval` with `batch_invariant` on, `windows_per_forward` at a time (longform.LongFormRun)."""
+        self.eval()
+        run = longform.LongFormRun(wavs, self.wav2vec2, next(self.parameters()).device, window_frames, hop_frames, trim_frames, ramp)
+        prev, self.batch_invariant = self.batch_invariant, True
+        try:
+            with torch.no_grad():
+                full_all = None
+                for first, rows in run.groups(windows_per_forward):
+                    audio, lens = run.gather(first, rows)
+                    out, _ = self._logits_eval(audio, lens)
+                    full_all = run.collect(full_all, out._logits_full, first, rows)
+                Np = full_all.shape[1]
+                stitched, _ = run.stitch(full_all, Np, out._geom.Tp, self.pr_head.weight.shape[0], per_recording_rows=True, ldo=Np,
+                                         want_argmax=False)
+        finally:
+            self.batch_invariant = prev
+        geom = SimpleNamespace(B=run.n_rec, T=run.max_frames, Tp=run.max_frames, fir_lens=run.frames_i32())
+        return run, SimpleNamespace(_geom=geom, _logits_full=stitched)
+
+    def get_ctc_logits_long(self, wav, window_frames=499, hop_frames=399, trim_frames=25, ramp="linear", windows_per_forward=16):
+        """`get_ctc_logits` of a recording of any length: overlapped windows of `window_frames` encoder frames every `hop_frames`
+        (hostlogic.long_form_plan), their logits stitched on the device (aptai_stitch_windows).  The waveform is taken as given."""
+        run, out = self._long([wav], window_frames, hop_frames, trim_frames, ramp, windows_per_forward)
+        return out._logits_full[:run.frames[0], :self.pr_head.weight.shape[0]].cpu().numpy()
+
+    def pred_phn_seq_long(self, wav, vocab, window_frames=499, hop_frames=399, trim_frames=25, ramp="linear", windows_per_forward=16):
+        """`pred_phn_seq` over the stitched logits: the decode of `decoder`, the recording as ONE row of its own frame count."""
+        _, out = self._long([wav], window_frames, hop_frames, trim_frames, ramp, windows_per_forward)
+        with torch.no_grad():
+            idx = self._decode(out)[0]
+        return {'phn_seq_idx': idx, 'phn_seq_ipa': self._ipa(vocab, idx)}
+
+    def predict_phonemes_durations_long(self, wav, vocab, window_frames=499, hop_frames=399, trim_frames=25, ramp="linear",
+                                        windows_per_forward=16):
+        """`predict_phonemes_durations` over the stitched logits (same `frame_sec_ratio`: samples / frames / 16000)."""
+        run, out = self._long([wav], window_frames, hop_frames, trim_frames, ramp, windows_per_forward)
+        n_frames = run.frames[0]
+        frame_sec_ratio = run.plans[0].n_samples / n_frames / 16000
+        with torch.no_grad():
+            (idx, ts, _), = self._rows(*self._read_out(out, n_frames + 2))
+        return {'phn_seq_idx': idx, 'phn_seq_ipa': self._ipa(vocab, idx), 'phn_seq_dur': [t * frame_sec_ratio for t in ts]}
 
     # ------------------------------------------------------------------ forced alignment of a known transcript
     def force_align(self, audio_inputs, audio_lengths, phoneme_labels):

@@ -1145,7 +1145,8 @@ class Wav2Vec2Model(nn.Module):
             g.lens0 = hostlogic.conv0_frame_lengths(sample_lens, cfg.conv_kernel[0], cfg.conv_stride[0]).clamp(min=1, max=g.Tl[0])
         elif batch_invariant:
             g.lens0 = torch.full((g.B,), g.Tl[0], device=dev, dtype=torch.int32)
-        g.fir_lens = lens_i32 if batch_invariant else None
+        # (B,) whatever the mask's rank: APTAI.get_aptai_output hands in its (1, 1) length as a (1, 1, 1) mask
+        g.fir_lens = lens_i32.reshape(-1) if batch_invariant else None
         return frame_lens, lens_i32, sample_lens
 
     def _spec_masks(self, g, lens_i32, ragged_lens, seed, mask_time_indices, mask_feature_indices):

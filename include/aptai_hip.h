@@ -731,6 +731,44 @@ int aptai_warp_targets(const double* tracks, int64_t R_trk, const int64_t* label
 int aptai_wave_normalize(float* x, int64_t ld, const int64_t* lens, int64_t B, int64_t ncols, void* workspace, void* stream);
 int64_t aptai_wave_normalize_workspace_bytes(int64_t B, int64_t ncols);
 
+/* ------------------------------------------------------------------------------------------------ long recordings
+ * Overlapped-window inference over recordings longer than the clips the models were trained on (HF pipelines: chunk_length_s /
+ * stride_length_s; the reference has no such path, models/aptai.py:125 runs the whole waveform through one forward).  The window
+ * plan is hostlogic.long_form_plan: windows of window_frames encoder frames every hop_frames frames, K = 0 for a recording of
+ * F <= window_frames frames and ceil((F - window_frames) / hop_frames) otherwise, windows 0 .. K.  Caller-owned buffers, device
+ * int64 tables, the passed stream, no synchronisation, no atomics, no LDS: equal inputs give equal bits. */
+/* The windows first .. first + rows - 1 of `table` cut out of src into the zero-padded batch the encoder takes, one launch.  src:
+ * fp32, n_src elements, one or more recordings back to back.  table int64 [n_windows][3] on the device: {offset of the window's
+ * recording in src, first sample of the window within the recording, sample count}.  out fp32 [rows][ld]: column c < S of row i
+ * is src[offset + start + c] for c < count and exactly 0.0 beyond; columns S .. ld-1 are left alone.  lens_out int64 [rows]: the
+ * counts (what the encoder takes as the rows' lengths).  Nothing outside [offset + start, offset + start + count) is read for a
+ * window, so nothing past a recording's end when the table follows the plan; a count is cut to S and to what src holds, and an
+ * entry with a negative field or a start outside src counts as empty: no table makes the kernel read outside src.  16-byte stores
+ * when out is 16-byte aligned and ld % 4 == 0, scalar stores otherwise; first + rows <= n_windows, rows <= 65535. */
+int aptai_window_gather(const float* src, int64_t n_src, const int64_t* table, int64_t n_windows, int64_t first, int64_t rows,
+                        float* out, int64_t ld, int64_t S, int64_t* lens_out, void* stream);
+/* Per-window results stitched into one row of frames per recording, one launch.  x: fp32 rows of pitch ldx, window w at rows
+ * w rows_per_window .. (frame j of the window at row w rows_per_window + j), n_windows windows: the filtered trajectories
+ * [W][T][n_tv] (ldx = n_tv, rows_per_window = T) and the padded head or CTC logits [W * Tp][Np] (ldx = Np, rows_per_window = Tp) as
+ * they are.  rec int64 [n_rec][3] on the device: {first window of the recording in x, its frame count F, its first row in out};
+ * its windows are consecutive in x.  Output frame t < F of a recording, channel c < C, with k = min(t / hop_frames, K) and
+ * j = t - k hop_frames:
+ *     j >= overlap = window_frames - hop_frames, or k == 0:   x1 = frame j of window k
+ *     otherwise, x0 = frame j + hop_frames of window k - 1:   x0 where ramp[j] <= 0, x1 where ramp[j] >= 1, else
+ *                                                             __fadd_rn(x0, __fmul_rn(ramp[j], __fsub_rn(x1, x0)))
+ * - three rounded fp32 operations, no fused multiply-add (the rule of aptai_ema_multi).  ramp: fp32 [overlap] on the device
+ * (hostlogic.long_form_ramp; may be null when no recording has a second window).  out fp32 [out_rows][ldo]: row rec[r][2] + t,
+ * columns 0 .. C-1; columns C .. ldo-1 and rows no recording owns are left alone, every owned element is written exactly once.
+ * argmax (optional) int64 [out_rows]: the index of the largest of the C stitched values of the frame, the lowest index on ties
+ * (torch.argmax of a frame without ties; the rule of aptai_aptai_loss_fwd's phn_pred).  Non-finite inputs are not supported (a NaN
+ * loses every comparison).  One wavefront per output frame, lanes over channels: 1 <= C <= 256.  window_frames / 2 <= hop_frames
+ * <= window_frames (a frame is covered by one or two windows); max_frames >= every F (the grid) and rows_per_window >=
+ * min(window_frames, max_frames); n_rec <= 65535.  A recording whose table entry points outside x or out (F > max_frames, a window
+ * >= n_windows, a row >= out_rows) is skipped: no table makes the kernel write outside out. */
+int aptai_stitch_windows(const float* x, int64_t ldx, int64_t rows_per_window, int64_t n_windows, const int64_t* rec, int64_t n_rec,
+                         int64_t max_frames, int64_t window_frames, int64_t hop_frames, const float* ramp, int64_t C, float* out,
+                         int64_t ldo, int64_t out_rows, int64_t* argmax, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
