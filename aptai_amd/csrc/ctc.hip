@@ -460,18 +460,14 @@ __device__ __forceinline__ void vit_sizes(const VitArgs& a, int b, int& Tb, int&
     S = a.topology == 0 ? 2 * L + 1 : L;
 }
 
-// ---- 1. raw logit per extended state + log-normaliser per frame.  grid = ceil(B*T/4) blocks of 4 waves, one frame per wave.
-__global__ __launch_bounds__(256) void vit_gather_kernel(VitArgs a, float* __restrict__ xe, float* __restrict__ lz) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const long f = (long)blockIdx.x * 4 + wave;
-    if (f >= (long)a.B * a.T) return;
-    const int b = (int)(f / a.T), t = (int)(f % a.T);
-    int Tb, L, S;
-    vit_sizes(a, b, Tb, L, S);
-    if (t >= Tb) return;                                          // the recursion never reads frames beyond the utterance
-    int Vb = a.vocab_sizes ? a.vocab_sizes[b] : a.V;
-    Vb = Vb < 0 ? 0 : (Vb < a.V ? Vb : a.V);
-    const float* row = a.logits + ((long)b * a.rows_per_b + t) * a.ldl;
+__device__ __forceinline__ int vit_vocab(const VitArgs& a, int b) {
+    const int Vb = a.vocab_sizes ? a.vocab_sizes[b] : a.V;
+    return Vb < 0 ? 0 : (Vb < a.V ? Vb : a.V);
+}
+
+// The log-normaliser of one frame over its first Vb classes, by one wave (every lane returns it).  The narrow and the wide
+// alignment both take it from here, so their scores are built from the same bits.
+__device__ __forceinline__ float vit_frame_lz(const float* __restrict__ row, int Vb, int lane) {
     float x[MAXV / 64];
     float mx = NEG_INF;
 #pragma unroll
@@ -485,7 +481,22 @@ __global__ __launch_bounds__(256) void vit_gather_kernel(VitArgs a, float* __res
 #pragma unroll
     for (int j = 0; j < MAXV / 64; ++j) se += (j * 64 + lane < Vb) ? expf(x[j] - mx) : 0.f;
     se = wave_sum(se);
-    if (lane == 0) lz[f] = mx + logf(se);
+    return mx + logf(se);
+}
+
+// ---- 1. raw logit per extended state + log-normaliser per frame.  grid = ceil(B*T/4) blocks of 4 waves, one frame per wave.
+__global__ __launch_bounds__(256) void vit_gather_kernel(VitArgs a, float* __restrict__ xe, float* __restrict__ lz) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long f = (long)blockIdx.x * 4 + wave;
+    if (f >= (long)a.B * a.T) return;
+    const int b = (int)(f / a.T), t = (int)(f % a.T);
+    int Tb, L, S;
+    vit_sizes(a, b, Tb, L, S);
+    if (t >= Tb) return;                                          // the recursion never reads frames beyond the utterance
+    const int Vb = vit_vocab(a, b);
+    const float* row = a.logits + ((long)b * a.rows_per_b + t) * a.ldl;
+    const float z = vit_frame_lz(row, Vb, lane);
+    if (lane == 0) lz[f] = z;
     float* out = xe + f * a.S_max;
     for (int s = lane; s < a.S_max; s += 64) {
         float l = NEG_INF;
@@ -717,5 +728,338 @@ extern "C" int aptai_ctc_viterbi(const float* logits, int64_t ldl, int64_t rows_
     APTAI_LAUNCH(vit_spans_kernel, dim3((unsigned)B), dim3(256), 0, stream, a, (const float*)xe, (const float*)lz,
                  (const int*)frame_token, spans, score, token_score);
     APTAI_CHECK_LAUNCH("vit_spans_kernel");
+    return APTAI_OK;
+}
+
+// ================================================================================================ forced alignment, wide lattice
+// aptai_ctc_viterbi_wide: the contract of aptai_ctc_viterbi with topology 0 for transcripts of up to
+// APTAI_CTC_VITERBI_WIDE_MAX_LABELS labels (a long recording against its whole transcript).  Three launches:
+//   1. vitw_lz_kernel (parallel, one wave per frame): lz[b][t] through vit_frame_lz, the narrow kernel's own reduction.  There is
+//      no per-state emission matrix: every state fetches its raw logit from the frame's row.
+//   2. vitw_recur_kernel (one workgroup per recording, up to 16 waves): NS consecutive states per thread in registers, the labels
+//      of its odd states beside them; the even states all read the one blank logit.  Neighbours: lane to lane by shuffle, wave to
+//      wave through a double-buffered LDS pair per wave, so ONE barrier per frame orders everything.  The logits rows are staged
+//      into an LDS ring by wave 0, four frames at a time and four frames ahead, with the next four in flight in registers.
+//      Backpointers: two bits per state, packed from state 0 upwards into rows of ceil(S_max / 16) words, written coalesced, four
+//      frames at a time.  The backtrace never
+//      reads global memory in its chain: a path moves at most two states per frame, so a chunk of VITW_CHUNK frames ending in
+//      state s can only visit states [s - 2 (VITW_CHUNK - 1), s], at most VITW_BAND words per frame; the whole group stages that
+//      band into LDS, then one wave walks it and writes frame_token in 64-frame pieces.
+//   3. vitw_spans_kernel (parallel, one workgroup per recording): spans from the frames where frame_token changes, score and
+//      token_score in the summation orders of vit_spans_kernel, so that for ldt <= 255 all four outputs equal the narrow kernel's.
+// Tie rule: as above.  No atomics; same inputs -> same bits; 64-bit offsets wherever B, T and the row width multiply.
+namespace {
+
+constexpr int VITW_CHUNK = 256;                                   // frames per backtrace chunk
+constexpr int VITW_BAND = 33;                                     // 2 (VITW_CHUNK - 1) + 1 = 511 states touch at most 33 words of 16
+constexpr int VITW_RING = 8;                                      // staged logits rows: the turn being read and the next
+constexpr int VITW_ROW = MAXV + 1;                                // [MAXV] holds -inf: where a label outside [0, MAXV) points
+constexpr int VITW_MAX_THREADS = 1024;
+
+// ---- 1. log-normaliser per frame.  grid = ceil(B*T/4) blocks of 4 waves, one frame per wave.
+__global__ __launch_bounds__(256) void vitw_lz_kernel(VitArgs a, float* __restrict__ lz) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long f = (long)blockIdx.x * 4 + wave;
+    if (f >= (long)a.B * a.T) return;
+    const int b = (int)(f / a.T), t = (int)(f % a.T);
+    int Tb, L, S;
+    vit_sizes(a, b, Tb, L, S);
+    if (t >= Tb) return;
+    const float z = vit_frame_lz(a.logits + ((long)b * a.rows_per_b + t) * a.ldl, vit_vocab(a, b), lane);
+    if (lane == 0) lz[f] = z;
+}
+
+// this wave's LDS traffic done, then the group's barrier: vector loads and stores stay in flight across it
+__device__ __forceinline__ void vitw_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+// Rows f0 .. f0 + 3 of the logits, columns j * 64 + lane for j < NJ, into registers: unconditional loads from clamped addresses
+// (a frame at or beyond Tb repeats the last one and is never read; a class at or beyond Vb becomes -inf when staged), so that
+// nothing branches around a load or waits for it here.  Needs Tb >= 1.
+template <int NJ>
+__device__ __forceinline__ void vitw_fetch4(const float* __restrict__ logits, long ldl, int f0, int Tb, int Vb, int lane,
+                                            float (&q)[4][MAXV / 64]) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const long f = f0 + k < Tb ? f0 + k : Tb - 1;
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            const int v = j * 64 + lane;
+            q[k][j] = logits[f * ldl + (v < Vb ? v : 0)];          // masked when staged: nothing here touches the loaded value
+        }
+    }
+}
+template <int NJ>
+__device__ __forceinline__ void vitw_stage4(float (&rows)[VITW_RING][VITW_ROW], int f0, int Vb, int lane, const float (&q)[4][MAXV / 64]) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) rows[(f0 + k) & (VITW_RING - 1)][j * 64 + lane] = j * 64 + lane < Vb ? q[k][j] : NEG_INF;
+}
+
+// ---- 2. max-plus recursion + backtrace.  grid B, blockDim.x = 64 * ceil(S_max / (64 NS)) threads.
+// NJ = ceil(V / 64) columns per lane of a staged row, 1 or 4: a template parameter so that the staged values have one home in the
+// registers (a runtime choice made the compiler copy them at the join, and wait for the loads it had just issued).
+template <int NS, int NJ>
+__global__ __launch_bounds__(VITW_MAX_THREADS) void vitw_recur_kernel(VitArgs a, uint32_t* __restrict__ bp_ws, int* __restrict__ frame_token) {
+    constexpr int NL = NS / 2;                                    // labels (odd states) per thread
+    __shared__ float rows[VITW_RING][VITW_ROW];
+    __shared__ float edge[2][VITW_MAX_THREADS / 64][2];           // [frame parity][wave]{last state, the one before it}
+    __shared__ uint32_t band[VITW_CHUNK * VITW_BAND];
+    __shared__ float fin[2];
+    __shared__ int s_next;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nthreads = blockDim.x;
+    int Tb, L, S;
+    vit_sizes(a, b, Tb, L, S);
+    const int Vb = vit_vocab(a, b);
+    const long W = (a.S_max + 15) >> 4;                           // backpointer words per frame
+    uint32_t* bp = bp_ws + (long)b * a.T * W;
+    int* ft = frame_token + (long)b * a.T;
+    const float* logits = a.logits + (long)b * a.rows_per_b * a.ldl;
+    const int* tg = a.targets + (long)b * a.ldt;
+    const int s0 = tid * NS;                                      // even: state s0 + i is blank for even i, label (s0 + i) >> 1 for odd i
+    const int nvalid = S - s0;                                    // states i < nvalid exist
+    int lab[NL];
+    unsigned skip = 0;                                            // bit j: state s0 + 2j + 1 may come from two states below
+#pragma unroll
+    for (int j = 0; j < NL; ++j) {
+        const int k = (s0 >> 1) + j;
+        const int kc = k < L ? k : 0;                             // loads from clamped positions: no branch around them (L == 0: slot 0, unused)
+        const int tk = tg[kc], tp = tg[kc > 0 ? kc - 1 : 0];
+        lab[j] = (k < L && tk >= 0 && tk < MAXV) ? tk : MAXV;     // classes at or beyond Vb hold -inf in the staged row
+        if (k < L && k >= 1 && tk != tp) skip |= 1u << j;
+    }
+    for (int i = tid; i < VITW_RING * VITW_ROW; i += nthreads) (&rows[0][0])[i] = NEG_INF;
+    if (tid < 2) fin[tid] = NEG_INF;
+    __syncthreads();
+    // Wave 0 stages the logits rows, four frames (one turn of the loop below) at a time.  At the head of a turn it writes the rows it
+    // requested a turn ago into the half of the ring that no frame of this turn reads and requests the next four; right behind
+    // that every wave stores the backpointer words of the turn before.  The vector-memory counter counts loads and stores
+    // together, so the compiler's wait in front of the staged values is a wait for everything: placed here, it finds loads and
+    // stores that have had a whole turn to complete, and no frame inside the turn waits for memory.
+    float q[4][MAXV / 64];
+    if (wave == 0 && Tb > 0) {
+        vitw_fetch4<NJ>(logits, a.ldl, 0, Tb, Vb, lane, q);
+        vitw_stage4<NJ>(rows, 0, Vb, lane, q);
+        vitw_fetch4<NJ>(logits, a.ldl, 4, Tb, Vb, lane, q);
+    }
+    __syncthreads();
+    float st[NS];
+#pragma unroll
+    for (int i = 0; i < NS; ++i) st[i] = NEG_INF;
+    // two bits per state from state 0 upwards: thread tid owns bits [2 NS tid, 2 NS (tid + 1)) of the frame's row
+    auto store_word = [&](int t, unsigned word) {
+        uint32_t* bpr = bp + (long)t * W;
+        if (s0 < a.S_max) {
+            if (NS == 16) bpr[tid] = word;
+            else if (NS == 8) ((uint16_t*)bpr)[tid] = (uint16_t)word;
+            else if (NS == 4) ((uint8_t*)bpr)[tid] = (uint8_t)word;
+            else if (!(tid & 1)) ((uint8_t*)bpr)[tid >> 1] = (uint8_t)word;      // NS == 2: the even thread holds the pair's byte
+        }
+    };
+    // one frame: reads rows[t & 7] and edge[(t - 1) & 1], writes edge[t & 1]; the barrier at its end makes that visible, and what the
+    // next frame overwrites (edge[(t + 1) & 1]) was last read before that barrier.  LDS only: loads and stores stay in flight.
+    auto advance = [&](int t, unsigned& kept) {
+        const float* row = rows[t & (VITW_RING - 1)];
+        const float xb = row[a.blank];
+        float xl[NL];
+#pragma unroll
+        for (int j = 0; j < NL; ++j) xl[j] = row[lab[j]];
+        float nw[NS];
+        unsigned word = 0;
+        if (t == 0) {
+#pragma unroll
+            for (int i = 0; i < NS; ++i) nw[i] = (s0 + i < 2 && i < nvalid) ? ((i & 1) ? xl[i >> 1] : xb) : NEG_INF;
+        } else {
+            const int pw = wave > 0 ? wave - 1 : 0;
+            const float e1 = edge[(t - 1) & 1][pw][0], e2 = edge[(t - 1) & 1][pw][1];
+            float p1 = __shfl_up(st[NS - 1], 1, 64), p2 = __shfl_up(st[NS - 2], 1, 64);
+            if (lane == 0) { p1 = wave > 0 ? e1 : NEG_INF; p2 = wave > 0 ? e2 : NEG_INF; }
+#pragma unroll
+            for (int i = 0; i < NS; ++i) {
+                const float a1 = i >= 1 ? st[i >= 1 ? i - 1 : 0] : p1;
+                const float a2 = i >= 2 ? st[i >= 2 ? i - 2 : 0] : (i == 1 ? p1 : p2);
+                float best = st[i];
+                unsigned c = 0;
+                if (a1 > best) { best = a1; c = 1; }
+                if ((i & 1) && ((skip >> (i >> 1)) & 1u) && a2 > best) { best = a2; c = 2; }
+                nw[i] = i < nvalid ? best + ((i & 1) ? xl[i >> 1] : xb) : NEG_INF;   // the ONE fp32 addition per state and frame
+                word |= c << (2 * i);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < NS; ++i) st[i] = nw[i];
+        if (lane == 63) { edge[t & 1][wave][0] = nw[NS - 1]; edge[t & 1][wave][1] = nw[NS - 2]; }
+        kept = NS == 2 ? (word | (__shfl_down(word, 1, 64) << 4)) : word;
+        vitw_lds_barrier();
+    };
+    unsigned w0 = 0, w1 = 0, w2 = 0, w3 = 0;
+    for (int t = 0; t < Tb; t += 4) {                             // Tb is uniform over the group: every barrier is reached by all
+        if (wave == 0) {                                          // rows t + 4 .. t + 7 replace those of the turn before in the ring
+            vitw_stage4<NJ>(rows, t + 4, Vb, lane, q);
+            vitw_fetch4<NJ>(logits, a.ldl, t + 8, Tb, Vb, lane, q);
+        }
+        if (t > 0) { store_word(t - 4, w0); store_word(t - 3, w1); store_word(t - 2, w2); store_word(t - 1, w3); }
+        advance(t, w0);
+        if (t + 1 < Tb) advance(t + 1, w1);
+        if (t + 2 < Tb) advance(t + 2, w2);
+        if (t + 3 < Tb) advance(t + 3, w3);
+    }
+    if (Tb > 0) {
+        const int t = ((Tb - 1) >> 2) << 2;                       // the last turn's words
+        store_word(t, w0);
+        if (t + 1 < Tb) store_word(t + 1, w1);
+        if (t + 2 < Tb) store_word(t + 2, w2);
+        if (t + 3 < Tb) store_word(t + 3, w3);
+    }
+    // final state: the last one unless the one before it is strictly greater
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+        if (s0 + i == S - 1) fin[0] = st[i];
+        if (s0 + i == S - 2) fin[1] = st[i];
+    }
+    __syncthreads();
+    int s = S - 1;
+    float best = fin[0];
+    if (fin[1] > best) { s = S - 2; best = fin[1]; }
+    const bool feasible = Tb > 0 && best > NEG_INF;
+    for (int t = (feasible ? Tb : 0) + tid; t < a.T; t += nthreads) ft[t] = -2;
+    if (!feasible) return;                                        // uniform over the group
+    __threadfence();                                              // the group's backpointer stores before its own loads below
+    __syncthreads();
+    int mine = -2;
+    for (int c0 = ((Tb - 1) / VITW_CHUNK) * VITW_CHUNK; c0 >= 0; c0 -= VITW_CHUNK) {
+        const int c1 = Tb < c0 + VITW_CHUNK ? Tb : c0 + VITW_CHUNK, n = c1 - c0;
+        const int low = s - 2 * (n - 1);
+        const int wlo = (low < 0 ? 0 : low) >> 4, bw = (s >> 4) - wlo + 1;        // bw <= VITW_BAND
+        for (int i = tid; i < n * bw; i += nthreads) {
+            const int r = i / bw, c = i - r * bw;
+            band[r * VITW_BAND + c] = bp[(long)(c0 + r) * W + wlo + c];
+        }
+        __syncthreads();
+        if (wave == 0) {
+            for (int t = c1 - 1; t >= c0; --t) {
+                const int tok = (s & 1) ? (s >> 1) : -1;
+                if (lane == (t & 63)) mine = tok;
+                if ((t & 63) == 0 && t + lane < Tb) ft[t + lane] = mine;
+                if (t > 0) {
+                    const unsigned w = band[(t - c0) * VITW_BAND + (s >> 4) - wlo];
+                    s -= (int)((w >> (2 * (s & 15))) & 3u);
+                    s = __builtin_amdgcn_readfirstlane(s < 0 ? 0 : s);
+                }
+            }
+            if (lane == 0) s_next = s;
+        }
+        __syncthreads();
+        s = s_next;
+    }
+}
+
+// ---- 3. spans, score, token_score from frame_token, for any ldt.  grid B, 256 threads; the orders of vit_spans_kernel.
+__global__ __launch_bounds__(256) void vitw_spans_kernel(VitArgs a, const float* __restrict__ lz, const int* __restrict__ frame_token,
+                                                         int* spans, float* __restrict__ score, float* __restrict__ token_score) {
+    __shared__ float red[256];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    int Tb, L, S;
+    vit_sizes(a, b, Tb, L, S);
+    const int Vb = vit_vocab(a, b);
+    const int* ft = frame_token + (long)b * a.T;
+    const int* tg = a.targets + (long)b * a.ldt;
+    int* sp = spans + (long)b * a.ldt * 2;
+    const float* logits = a.logits + (long)b * a.rows_per_b * a.ldl;
+    const long base = (long)b * a.T;
+    auto logp = [&](int t, int e) {                               // a frame of a feasible path only meets classes with a logit
+        const float x = (e >= 0 && e < Vb) ? logits[(long)t * a.ldl + e] : NEG_INF;
+        return x - lz[base + t];
+    };
+    for (long i = tid; i < 2 * a.ldt; i += 256) sp[i] = -1;
+    __syncthreads();
+    const bool feasible = Tb > 0 ? ft[0] != -2 : L == 0;
+    float part = 0.f;
+    if (feasible) {
+        for (int t = tid; t < Tb; t += 256) {
+            const int k = ft[t];
+            part += logp(t, k < 0 ? a.blank : tg[k]);
+            if (k >= 0) {
+                if (t == 0 || ft[t - 1] != k) sp[2 * k] = t;
+                if (t == Tb - 1 || ft[t + 1] != k) sp[2 * k + 1] = t + 1;
+            }
+        }
+    }
+    red[tid] = part;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o) red[tid] += red[tid + o];
+        __syncthreads();
+    }
+    if (tid == 0) score[b] = feasible ? red[0] : NEG_INF;
+    if (!token_score) return;
+    for (int k = tid; k < (int)a.ldt; k += 256) {
+        const int f0 = sp[2 * k], f1 = sp[2 * k + 1];
+        float v = NEG_INF;
+        if (f0 >= 0) {
+            const int e = tg[k];
+            float acc = 0.f;
+            for (int t = f0; t < f1; ++t) acc += logp(t, e);
+            v = acc / (float)(f1 - f0);
+        }
+        token_score[(long)b * a.ldt + k] = v;
+    }
+}
+
+// workspace: lz [B*T] fp32 | backpointers [B][T][ceil(S_max / 16)] words; both parts 16-byte aligned
+struct VitwLayout { int64_t lz, bp, total; };
+VitwLayout vitw_layout(int64_t B, int64_t T, int64_t ldt) {
+    VitwLayout l;
+    l.lz = 0;
+    l.bp = (B * T * 4 + 15) / 16 * 16;
+    l.total = l.bp + B * T * ((2 * ldt + 1 + 15) / 16) * 4;
+    return l;
+}
+
+template <int NS>
+void launch_vitw(const VitArgs& a, uint32_t* bp, int32_t* frame_token, hipStream_t stream) {
+    const int threads = (int)ceil_div(ceil_div(a.S_max, NS), 64) * 64;
+    if (a.V <= 64) APTAI_LAUNCH((vitw_recur_kernel<NS, 1>), dim3((unsigned)a.B), dim3((unsigned)threads), 0, stream, a, bp, frame_token);
+    else APTAI_LAUNCH((vitw_recur_kernel<NS, 4>), dim3((unsigned)a.B), dim3((unsigned)threads), 0, stream, a, bp, frame_token);
+}
+
+}  // namespace
+
+extern "C" int64_t aptai_ctc_viterbi_wide_workspace_bytes(int64_t B, int64_t T, int64_t ldt) { return vitw_layout(B, T, ldt).total; }
+
+extern "C" int aptai_ctc_viterbi_wide(const float* logits, int64_t ldl, int64_t rows_per_b, const int32_t* targets, int64_t ldt,
+                                      const int32_t* input_lens, const int32_t* target_lens, const int32_t* vocab_sizes, int64_t B,
+                                      int64_t T, int64_t V, int blank, int topology, void* workspace, int32_t* frame_token,
+                                      int32_t* spans, float* score, float* token_score, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    const char* who = "aptai_ctc_viterbi_wide";
+    APTAI_REQUIRE(logits && targets && input_lens && target_lens && workspace && frame_token && spans && score, "%s: null pointer", who);
+    APTAI_REQUIRE(topology == 0, "%s: only topology 0 (CTC) has a wide lattice; topology %d goes through aptai_ctc_viterbi", who, topology);
+    APTAI_REQUIRE(B > 0 && T > 0 && B <= INT32_MAX / T && V > 0 && V <= MAXV && ldl >= V && rows_per_b >= T,
+                  "%s: bad sizes (B*T=%ld*%ld must stay below 2^31, V=%ld, max %d)", who, (long)B, (long)T, (long)V, MAXV);
+    APTAI_REQUIRE(ldt >= 1 && ldt <= APTAI_CTC_VITERBI_WIDE_MAX_LABELS, "%s: at most %d labels per recording (got row length %ld)", who,
+                  APTAI_CTC_VITERBI_WIDE_MAX_LABELS, (long)ldt);
+    APTAI_REQUIRE(blank >= 0 && blank < V, "%s: blank out of range", who);
+    APTAI_REQUIRE(((uintptr_t)workspace & 15) == 0, "%s: workspace must be 16-byte aligned", who);
+    VitArgs a;
+    memset(&a, 0, sizeof(a));
+    a.logits = logits; a.ldl = ldl; a.rows_per_b = rows_per_b; a.targets = targets; a.ldt = ldt;
+    a.input_lens = input_lens; a.target_lens = target_lens; a.vocab_sizes = vocab_sizes;
+    a.B = (int)B; a.T = (int)T; a.V = (int)V; a.blank = blank; a.topology = 0;
+    a.S_max = (int)(2 * ldt + 1);
+    const VitwLayout l = vitw_layout(B, T, ldt);
+    float* lz = (float*)((char*)workspace + l.lz);
+    uint32_t* bp = (uint32_t*)((char*)workspace + l.bp);
+    APTAI_LAUNCH(vitw_lz_kernel, dim3((unsigned)ceil_div(B * T, 4)), dim3(256), 0, stream, a, lz);
+    APTAI_CHECK_LAUNCH("vitw_lz_kernel");
+    // eight waves where 16 states per thread allow it: NS = the fewest states per thread that keep the group at 512 threads
+    if (a.S_max <= 512 * 2) launch_vitw<2>(a, bp, frame_token, stream);
+    else if (a.S_max <= 512 * 4) launch_vitw<4>(a, bp, frame_token, stream);
+    else if (a.S_max <= 512 * 8) launch_vitw<8>(a, bp, frame_token, stream);
+    else launch_vitw<16>(a, bp, frame_token, stream);
+    APTAI_CHECK_LAUNCH("vitw_recur_kernel");
+    APTAI_LAUNCH(vitw_spans_kernel, dim3((unsigned)B), dim3(256), 0, stream, a, (const float*)lz, (const int*)frame_token, spans, score,
+                 token_score);
+    APTAI_CHECK_LAUNCH("vitw_spans_kernel");
     return APTAI_OK;
 }

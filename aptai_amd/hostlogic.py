@@ -576,6 +576,18 @@ def alignment_spans(frame_token, n_tokens: int) -> np.ndarray:
     return spans
 
 
+def long_form_force_align(window_logits, plan: LongFormPlan, ramp, targets, blank: int = 0):
+    """Forced alignment of a long recording in numpy: the per-window logits stitched (long_form_stitch; `ramp` is the table of
+    long_form_ramp or its kind, "linear" / "cut"), then ctc_forced_align of the whole transcript over the `plan.frames` stitched
+    frames, then alignment_spans.  Returns (frame_token int32 [F], spans int32 [len(targets)][2], score, stitched fp32 [F][V]):
+    what Wav2Vec2_PR.force_align_long computes on the device, for host-side tools and as its oracle."""
+    table = long_form_ramp(plan, ramp) if isinstance(ramp, str) else ramp
+    stitched, _ = long_form_stitch(window_logits, plan, table)
+    tg = np.asarray(targets, dtype=np.int64).reshape(-1)
+    frame_token, score = ctc_forced_align(stitched, plan.frames, tg, blank=blank)
+    return frame_token, alignment_spans(frame_token, len(tg)), score, stitched
+
+
 def fill_blank_frames(frame_token) -> np.ndarray:
     """A transcript position for EVERY valid frame of a CTC alignment (what per-frame labels such as `phn_frames_49hz` need).
     This is OUR rule - the reference takes its frame labels from MAUS boundaries, which are not reproducible here: a run of

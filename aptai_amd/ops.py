@@ -1076,6 +1076,30 @@ def ctc_viterbi(logits, ldl, rows_per_b, targets_i32, input_lens_i32, target_len
     return frame_token, spans, score, token_score
 
 
+CTC_VITERBI_WIDE_MAX_LABELS = _C["APTAI_CTC_VITERBI_WIDE_MAX_LABELS"]
+
+
+def ctc_viterbi_wide(logits, ldl, rows_per_b, targets_i32, input_lens_i32, target_lens_i32, B, T, V, *, blank=0, topology="ctc",
+                     vocab_sizes_i32=None, want_token_score=True):
+    """`ctc_viterbi` for a wide lattice (aptai_ctc_viterbi_wide): label rows of up to CTC_VITERBI_WIDE_MAX_LABELS slots, the CTC
+    topology only (any other is refused by the library).  Same four tensors, same fill values, the same bits as `ctc_viterbi` where
+    both take the shape.  Nothing here synchronises host and device."""
+    _dev(logits, targets_i32, input_lens_i32, target_lens_i32, vocab_sizes_i32)
+    dev = logits.device
+    if targets_i32.shape[1] == 0:                      # an all-empty batch still needs one (unread) label slot per row
+        targets_i32 = torch.zeros((B, 1), device=dev, dtype=torch.int32)
+    ldt = targets_i32.shape[1]
+    ws = torch.empty(max(_lib.lib().aptai_ctc_viterbi_wide_workspace_bytes(B, T, ldt), 16), device=dev, dtype=torch.uint8)
+    frame_token = torch.empty((B, T), device=dev, dtype=torch.int32)
+    spans = torch.empty((B, ldt, 2), device=dev, dtype=torch.int32)
+    score = torch.empty(B, device=dev, dtype=torch.float32)
+    token_score = torch.empty((B, ldt), device=dev, dtype=torch.float32) if want_token_score else None
+    _lib.call("aptai_ctc_viterbi_wide", logits.data_ptr(), ldl, rows_per_b, targets_i32.data_ptr(), ldt, input_lens_i32.data_ptr(),
+              target_lens_i32.data_ptr(), _ptr(vocab_sizes_i32), B, T, V, blank, _TOPOLOGY[topology], ws.data_ptr(),
+              frame_token.data_ptr(), spans.data_ptr(), score.data_ptr(), _ptr(token_score), _stream())
+    return frame_token, spans, score, token_score
+
+
 # ----------------------------------------------------------------------------- evaluation metrics (csrc/eval.hip)
 EVAL_EDIT_MAX_LANE_SIDE = _C["APTAI_EVAL_EDIT_MAX_LANE_SIDE"]
 

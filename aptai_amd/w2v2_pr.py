@@ -330,10 +330,14 @@ class Wav2Vec2_PR(nn.Module):
             blank = self._blank()
             ft, spans, score, token_score = ops.ctc_viterbi(full, full.shape[1], g.Tp, labels, frame_lens, target_lens, g.B, g.T, V,
                                                             blank=blank, topology="ctc")
-            lab = torch.gather(labels, 1, ft.clamp(min=0).long())
-            frame_phns = torch.where(ft >= 0, lab, torch.where(ft == -1, blank, 0)).to(torch.int32)
-            return {'frame_token': ft, 'frame_phns': frame_phns, 'spans': spans, 'score': score, 'token_score': token_score,
-                    'frame_seq_lens': frame_lens}
+            return {'frame_token': ft, 'frame_phns': self._frame_phns(labels, ft, blank), 'spans': spans, 'score': score,
+                    'token_score': token_score, 'frame_seq_lens': frame_lens}
+
+    @staticmethod
+    def _frame_phns(labels, ft, blank):
+        """Vocabulary id of every frame of an alignment: the label of its position, the blank id on blank frames, 0 beyond the length."""
+        lab = torch.gather(labels, 1, ft.clamp(min=0).long())
+        return torch.where(ft >= 0, lab, torch.where(ft == -1, blank, 0)).to(torch.int32)
 
     def align_phonemes_durations(self, wav, phn_seq_idx, vocab):
         """`predict_phonemes_durations` for a KNOWN phoneme sequence: start and end of every phoneme in seconds (same
@@ -358,6 +362,75 @@ class Wav2Vec2_PR(nn.Module):
                     'phn_end': [int(b) * frame_sec_ratio for b in spans[:, 1]],
                     'phn_score': res['token_score'][0, :len(idx)].cpu().numpy().tolist(), 'score': score,
                     'phn_frames': [int(idx[k]) if k >= 0 else self._blank() for k in filled]}
+
+    # ------------------------------------------------------------------ forced alignment of long recordings
+    def _force_align_long(self, wavs, phoneme_seqs, window_frames, hop_frames, trim_frames, ramp, windows_per_forward):
+        """(run, result dictionary) of `force_align_long`: one `_long` pass for all recordings, one wide Viterbi over its rows."""
+        seqs = [np.asarray(q, dtype=np.int64).reshape(-1) for q in phoneme_seqs]
+        if len(seqs) != len(wavs):
+            raise ValueError(f"force_align_long: {len(wavs)} recordings but {len(seqs)} phoneme sequences")
+        cap = ops.CTC_VITERBI_WIDE_MAX_LABELS
+        if max((len(q) for q in seqs), default=0) > cap:
+            raise ValueError(f"force_align_long: at most {cap} labels per recording (got {max(len(q) for q in seqs)})")
+        run, out = self._long(wavs, window_frames, hop_frames, trim_frames, ramp, windows_per_forward)
+        with torch.no_grad():
+            full = out._logits_full                                   # [n_rec * max_frames][Np] fp32
+            n, ldt = run.n_rec, max([len(q) for q in seqs] + [1])
+            host = np.full(n * ldt + n, -100, dtype=np.int32)         # label rows, then their lengths: one upload
+            for r, q in enumerate(seqs):
+                host[r * ldt:r * ldt + len(q)] = q
+                host[n * ldt + r] = len(q)
+            both = torch.from_numpy(host).to(full.device)
+            labels, target_lens = both[:n * ldt].view(n, ldt), both[n * ldt:]
+            frame_lens = run.frames_i32()
+            blank = self._blank()
+            ft, spans, score, token_score = ops.ctc_viterbi_wide(full, full.shape[1], run.max_frames, labels, frame_lens, target_lens, n,
+                                                                 run.max_frames, self.pr_head.weight.shape[0], blank=blank)
+            return run, {'frame_token': ft, 'frame_phns': self._frame_phns(labels, ft, blank), 'spans': spans, 'score': score,
+                         'token_score': token_score, 'frame_seq_lens': frame_lens}
+
+    def force_align_long(self, wavs, phoneme_seqs, window_frames=499, hop_frames=399, trim_frames=25, ramp="linear",
+                         windows_per_forward=16):
+        """`force_align` for recordings of any length against their whole transcripts: `wavs` is a list of 1-D waveforms,
+        `phoneme_seqs` one id sequence per recording (at most ops.CTC_VITERBI_WIDE_MAX_LABELS = 8191 labels, ValueError beyond).
+        The windows run as in the other `*_long` helpers (same plan arguments, precisions and refusals), their logits are stitched
+        on the device and aptai_ctc_viterbi_wide aligns each recording's row block to its transcript: same contract and tie rule as
+        `force_align`, no T^2 attention over the recording and no limit of 255 labels.  Eval mode, no gradients.  Returns the
+        dictionary of `force_align` as DEVICE tensors, never synchronising: frame_token / frame_phns int32 [n][max frames], spans
+        int32 [n][L][2], score fp32 [n], token_score fp32 [n][L], frame_seq_lens int32 [n] = the recordings' frame counts.
+        hostlogic.long_form_force_align is the same in numpy.  Accuracy at the seams and parity with torchaudio's forced_align
+        are unmeasured (no trained checkpoint and no torchaudio here)."""
+        return self._force_align_long(wavs, phoneme_seqs, window_frames, hop_frames, trim_frames, ramp, windows_per_forward)[1]
+
+    def align_phonemes_durations_long(self, wav, phn_seq_idx, vocab, **plan):
+        """`align_phonemes_durations` of a recording of any length (`plan`: the keywords of `force_align_long`; same
+        `frame_sec_ratio` as `predict_phonemes_durations_long`: samples / frames / 16000).  One device->host transfer.  Raises
+        ValueError when the sequence does not fit the recording."""
+        idx = np.asarray(phn_seq_idx, dtype=np.int64).reshape(-1)
+        keys = ("window_frames", "hop_frames", "trim_frames", "ramp", "windows_per_forward")
+        unknown = sorted(set(plan) - set(keys))
+        if unknown:
+            raise TypeError(f"align_phonemes_durations_long: unknown keyword(s) {unknown}")
+        args = dict(window_frames=499, hop_frames=399, trim_frames=25, ramp="linear", windows_per_forward=16)
+        args.update(plan)
+        run, res = self._force_align_long([wav], [idx], *(args[k] for k in keys))
+        n_frames, n = run.frames[0], len(idx)
+        frame_sec_ratio = run.plans[0].n_samples / n_frames / 16000
+        with torch.no_grad():                                         # int32 and fp32 values are exact in fp64
+            packed = torch.cat([res['frame_token'][0, :n_frames].double(), res['spans'][0, :n].reshape(-1).double(),
+                                res['token_score'][0, :n].double(), res['score'][:1].double()]).cpu().numpy()
+        score = float(packed[-1])
+        if not np.isfinite(score):
+            raise ValueError(f"align_phonemes_durations_long: {n} phonemes do not fit the recording's {n_frames} frames "
+                             f"(or a phoneme id is outside the vocabulary)")
+        ft = packed[:n_frames].astype(np.int32)
+        spans = packed[n_frames:n_frames + 2 * n].astype(np.int64).reshape(n, 2)
+        filled = hostlogic.fill_blank_frames(ft)
+        return {'phn_seq_idx': idx, 'phn_seq_ipa': self._ipa(vocab, idx),
+                'phn_start': [int(a) * frame_sec_ratio for a in spans[:, 0]],
+                'phn_end': [int(b) * frame_sec_ratio for b in spans[:, 1]],
+                'phn_score': packed[n_frames + 2 * n:n_frames + 3 * n].astype(np.float32).tolist(), 'score': score,
+                'phn_frames': [int(idx[k]) if k >= 0 else self._blank() for k in filled]}
 
     def get_config(self):
         return {'huggingface_model_id': self.huggingface_model_id, 'cache_dir': self.cache_dir, 'pretrain_cfg': self.pretrain_cfg}

@@ -508,6 +508,22 @@ int aptai_ctc_viterbi(const float* logits, int64_t ldl, int64_t rows_per_b, cons
                       int64_t V, int blank, int topology, void* workspace, int32_t* frame_token, int32_t* spans, float* score,
                       float* token_score, void* stream);
 int64_t aptai_ctc_viterbi_workspace_bytes(int64_t B, int64_t T, int64_t ldt);
+/* aptai_ctc_viterbi for a WIDE lattice: a long recording against its whole transcript (the stitched logits of the long-form
+ * helpers, one block of rows per recording).  Operands, outputs, fill values and TIE RULE are exactly those of aptai_ctc_viterbi
+ * with topology 0, so frame_token is the same pure function of the fp32 inputs (hostlogic.ctc_forced_align) and for ldt <= 255
+ * all four outputs equal aptai_ctc_viterbi's bit for bit.  Limits: 1 <= ldt <= APTAI_CTC_VITERBI_WIDE_MAX_LABELS (at most
+ * 2 * 8191 + 1 = 16383 states); V <= 256; topology must be 0 (1 is refused: the monotonic lattice stays with aptai_ctc_viterbi).
+ * One workgroup per recording walks the frames with one barrier per frame; there is no per-state emission matrix.
+ * Workspace (aptai_ctc_viterbi_wide_workspace_bytes, 16-byte aligned, caller-owned):
+ *   lz fp32 [B*T] (rounded up to 16 bytes) | backpointers [B][T][ceil((2 ldt + 1) / 16)] 32-bit words, two bits per state
+ *   (0 stay, 1 from s-1, 2 from s-2), state s in bits [2 (s % 16), 2 (s % 16) + 2) of word s / 16.
+ * About 30 MB for 15 000 frames and 4 000 labels.  No synchronisation, no atomics, same inputs -> same bits. */
+#define APTAI_CTC_VITERBI_WIDE_MAX_LABELS 8191
+int aptai_ctc_viterbi_wide(const float* logits, int64_t ldl, int64_t rows_per_b, const int32_t* targets, int64_t ldt,
+                           const int32_t* input_lens, const int32_t* target_lens, const int32_t* vocab_sizes, int64_t B, int64_t T,
+                           int64_t V, int blank, int topology, void* workspace, int32_t* frame_token, int32_t* spans, float* score,
+                           float* token_score, void* stream);
+int64_t aptai_ctc_viterbi_wide_workspace_bytes(int64_t B, int64_t T, int64_t ldt);
 /* Best-path CTC decode on the device (stand-in for the torchaudio beam decoder the reference calls at models/w2v2_pr.py:143-159,
  * which is absent here: parity unpinned).  Row b is exactly hostlogic.ctc_bracketed_best_path(logits[b], T_b, blank, sil)
  * (aptai_amd/hostlogic.py, the oracle of the tests): frame argmax (first maximum) over the first T_b = clamp(input_lens[b], 0, T)
